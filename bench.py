@@ -14,10 +14,15 @@ Workload = BASELINE.json's metric: "env-steps/sec (whole node), 4096 OP3 walkers
 configs[2] (4096 OP3 LIPM walking) at N = 1, and for N > 1 the SAME 4096 walkers split evenly over the
 ranks (strong scaling: 2048 / 1024 / 512 per GPU).  `--weak` keeps --envs walkers on EVERY
 GPU instead (configs[3]: 8 x 4096 = 32768 at N = 8).  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line; at N = 1 it also carries `secondary`: the unfavourable paths
-measured beside the headline (cfg2 stand at 1024 and 4096 envs, a de-phased walking batch that mixes
-50- and 38-variable QPs in one launch, and a walking batch with tightened torque bounds that drives
-envs into the dual active-set loop).
+region.  Rank 0 prints ONE JSON line.  A plain run measures the headline only; with `--full` (N = 1) the
+line also carries `cpu_baseline` (the CPU oracle on a sample of the same workload) and `secondary`: the
+unfavourable paths measured beside the headline (cfg2 stand at 1024 and 4096 envs, a de-phased walking
+batch that mixes 50- and 38-variable QPs in one launch, and a walking batch with tightened torque bounds
+that drives envs into the dual active-set loop).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (the state, torques, forces,
+observations, reward and done flags a caller of WalkController.step_pipelined receives) as DIR/<name>.npy,
+so that two builds can be compared output for output; the inputs are seeded, identical from run to run.
 """
 import argparse
 import json
@@ -69,7 +74,13 @@ def parse():
     ap.add_argument("--robot", choices=["v1", "v0"], default="v1",
                     help="v0: the reference's second robot (robot/v0, libtsidb_v0.so; SURVEY 8f-4) - standing workload only "
                          "(the reference has no walking configuration for it)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget; 0 disables it")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the headline also run the CPU baseline and the secondary measurements (and, with "
+                         "--graph, the eager run that times the kernels); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: a fixed, seeded sample of envs beyond that)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (--full); 0 disables it")
     ap.add_argument("--cpu-sample", type=int, default=256)
     ap.add_argument("--randomize", action="store_true",
                     help="BASELINE configs[4] (not the headline): per-env mass scale U(0.8,1.2), friction U(0.4,1.0), a floor "
@@ -91,7 +102,7 @@ def parse():
                          "polynomials, DCM / LIPM CoM plan per env, path scales U(0.5, 1) drawn per env) and the episode lifecycle "
                          "runs there as well (tsidb_reset_done + replan every 50 steps: envs that fell restart on a new path) - "
                          "the path an RL user runs; default: the host-planned schedule (WalkSchedule.from_demo_paths)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (N = 1 only)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (--full, N = 1 only)")
     ap.add_argument("--secondary-steps", type=int, default=200)
     ap.add_argument("--event-every", type=int, default=int(os.environ.get("TSIDB_EVENT_EVERY", "8")),
                     help="bracket the kernels with HIP timing events on every k-th timed step only")
@@ -417,6 +428,32 @@ def kernel_words(wc):
     return tick_words, sim_words
 
 
+DUMP_FIELDS = ("q", "v", "tau", "dv", "f", "status", "obs", "reward", "done", "qpos", "qvel", "qacc_warmstart",
+               "contact_active", "ncon", "con_pairs", "info")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(wc, out_dir, prefix=""):
+    """The arrays a caller of the timed path holds after its last step, one DIR/<prefix><name>.npy each: floating state in
+    the run's dtype, integer flags / counts as float64 (exact).  Beyond DUMP_MAX_BYTES in all, a fixed sample of envs (seed
+    0, ascending; the env indices go to <prefix>env_index.npy) is written instead of the whole batch."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for k in DUMP_FIELDS:
+        t = getattr(wc, k).detach()
+        arrs[k] = t.cpu().numpy() if t.is_floating_point() else t.double().cpu().numpy()
+    n = wc.num_envs
+    per_env = sum(a.nbytes for a in arrs.values()) / n
+    if per_env * n > DUMP_MAX_BYTES:
+        k = int((DUMP_MAX_BYTES - 8 * n - 256 * (len(arrs) + 1)) // per_env)   # (room for the indices and the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrs = {name: a[idx] for name, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    for name, a in arrs.items():
+        np.save(out_dir / f"{prefix}{name}.npy", np.ascontiguousarray(a))
+
+
 def secondary_runs(a, dev):
     """The unfavourable paths beside the headline, each a short run of its own."""
     out = {}
@@ -548,10 +585,13 @@ def main():
         n = hi - lo
     res, wc, sched, t_next = run_workload(args, dev, rank, world, n)
     el, tick_ms, sim_ms = res["el"], res["tick_ms"], res["sim_ms"]
+    if args.dump_outputs:
+        dump_outputs(wc, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
 
     wsz = 8 if args.dtype == "f64" else 4
-    if res["graph_steps"]:
+    if res["graph_steps"] and args.full:
         # no HIP events inside a captured graph: take the per-kernel times from a short eager run of the same workload
+        # (without --full the per-kernel figures of a --graph run stay NaN)
         import copy
         ea = copy.copy(args)
         ea.graph, ea.steps = 0, 64
@@ -639,9 +679,9 @@ def main():
                          "valu_issue_from_profiles": pmc, "vector_roofline_from_profiles": vec,
                          "valu_frac_nominal": (n * NOMINAL_FLOP_PER_ENV_STEP / ((tick_ms + sim_ms) * 1e-3)) / (VALU_PEAK_TFLOPS[args.dtype] * 1e12)},
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(wc, sched, t_next, args.cpu_seconds, args.cpu_sample)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             del wc
             torch.cuda.empty_cache()
             out["secondary"] = secondary_runs(args, dev)

@@ -113,9 +113,13 @@ def test_bench_contract_and_execution_options():
         a = bench.parse()
         assert (a.gpus, a.steps, a.warmup, a.envs, a.dtype, a.workload) == (1, 5000, 20, 4096, "f64", "walk")
         assert a.device_plan is False and a.no_overlap is False and a.closed_loop is False
+        assert a.full is False and a.dump_outputs is None   # a plain run measures the headline only
         sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--device-plan"]
         b = bench.parse()
         assert (b.steps, b.warmup, b.device_plan) == (20, 5, True)
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "out"]
+        c = bench.parse()
+        assert (c.steps, c.warmup, c.full, c.dump_outputs) == (7, 2, True, "out")
     finally:
         sys.argv = argv
     assert bench.TICK_WORDS == 347 and bench.SIM_WORDS == 185 and bench.HBM_PEAK_GBS == 8000.0
@@ -133,3 +137,44 @@ def test_bench_contract_and_execution_options():
         v = t["valu"][k]
         assert 0.3 < 2.0 * v["issue_floor_cycles_per_env"] / (4.0 * v["wave_cycles_per_env"]) < 0.7
         assert 100.0 < v["launch_us_back_to_back"] < 200.0 and 0.8 < t[k]["bytes_per_launch"] / (4096 * 8 * (347 if k == "k_tick" else 185)) < 1.4
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: one .npy per array of the last step, float32 / float64 only, integers exact; a batch whose
+    arrays exceed 64 MB is written as a fixed, seeded sample of envs with their indices."""
+    import sys
+    import importlib
+    from types import SimpleNamespace
+    import torch
+    sys.path.insert(0, str(ROOT))
+    bench = importlib.import_module("bench")
+
+    def fake_wc(n, dtype):
+        g = torch.Generator().manual_seed(n)
+        r = lambda *s: torch.rand(*s, generator=g, dtype=dtype)
+        i = lambda *s, dt=torch.int32: torch.randint(0, 50, s, generator=g, dtype=dt)
+        rows = r(n, 67)
+        return SimpleNamespace(num_envs=n, q=r(n, 27), v=r(n, 26), tau=r(n, 20), dv=r(n, 26), f=r(n, 24), status=i(n),
+                               obs=rows[:, :65], reward=rows[:, 65], done=rows[:, 66], qpos=r(n, 27), qvel=r(n, 26),
+                               qacc_warmstart=r(n, 26), contact_active=i(n, 2, dt=torch.uint8), ncon=i(n),
+                               con_pairs=i(n, 32), info=i(n, 4))
+
+    wc = fake_wc(64, torch.float32)
+    bench.dump_outputs(wc, tmp_path / "small")
+    got = {p.stem: np.load(p) for p in (tmp_path / "small").glob("*.npy")}
+    assert set(got) == set(bench.DUMP_FIELDS)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["q"].dtype == np.float32 and np.array_equal(got["q"], wc.q.numpy())
+    assert np.array_equal(got["reward"], wc.reward.numpy()) and np.array_equal(got["con_pairs"], wc.con_pairs.double().numpy())
+
+    n = 32768                       # 32768 envs x 283 float64 words = 74 MB: sampled
+    wc = fake_wc(n, torch.float64)
+    bench.dump_outputs(wc, tmp_path / "a")
+    bench.dump_outputs(wc, tmp_path / "b")
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sum(p.stat().st_size for p in files) <= bench.DUMP_MAX_BYTES
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "tau.npy"), wc.tau.numpy()[idx])
+    for p in files:
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name))

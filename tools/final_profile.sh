@@ -8,8 +8,8 @@ O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_window.json 2>> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_window.json 2>> $O/${TAG}_bench.err
 python3 bench.py --no-overlap --cpu-seconds 0 --no-secondary > $O/${TAG}_bench_no_overlap.json 2>> $O/${TAG}_bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -- python3 $R/bench.py --steps 1000 --warmup 20 --cpu-seconds 0 --no-secondary > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_trace.err
