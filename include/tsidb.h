@@ -115,6 +115,19 @@ int tsidb_set_cop_ref(tsidb_handle h, const void *cop_ref);
  * are remembered, not copied. */
 int tsidb_set_env_params(tsidb_handle h, const void *env_params, const void *terrain);
 
+/* external body wrenches of the sim stage: mj_data.xfrc_applied, the field a caller of mj_step (main.py:195) writes to push
+ * the robot.  xfrc [N, NB, 6] (device, the path's arithmetic type; NB = sim bodies, tsidb_dims out9[4]) in the blob's sim body
+ * order - mj_parent order, MJCF document order without the world body, body 0 = the torso with the free joint - so
+ * xfrc[e, b] is xfrc_applied[b + 1] of env e.  Each row is force (3) then torque (3), both in the world frame, applied at the
+ * body's centre of mass.  As in MuJoCo the values persist until the caller changes them: every sim step reads them (every
+ * step of a tsidb_sim_batch launch, every substep of tsidb_step).  They enter the smooth force (qfrc_smooth += sum_b J_b^T
+ * w_b): the unconstrained acceleration, the contact solve and the damped-Euler integration all see them.  In the open-loop
+ * teleport mode (main.py:192 overwrites the base pose every step) a wrench on the torso moves it for that one step only;
+ * pushes on limbs do act.  A non-finite value skips the env's step like a non-finite joint target (info flag bit 4).
+ * tsidb_reset / tsidb_reset_done zero the rows of the envs they reset (mj_resetData).  NULL (the default) = no external
+ * wrenches.  Rejected by a library built without the sim stage.  The pointer is remembered, not copied. */
+int tsidb_set_xfrc(tsidb_handle h, void *xfrc);
+
 /* reset: WalkController.py:22-26,72-79 (standing state, soles onto z = 0), the references of
  * :81,122,151-152,164-165, and main.py:57-64 (mj_data.qpos = q).  env_ids (device, int32) selects
  * envs; NULL = all (a non-NULL list with n_ids = 0 resets nothing).  Writes state AND the reference buffers

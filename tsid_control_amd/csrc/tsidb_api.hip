@@ -227,9 +227,11 @@ template <typename T> struct SimRing { const T *q, *v; unsigned long long slots;
 // pipelined 18.9 -> 23.6 M env-steps/s at 4096 walkers, 21.3 -> 24.9 M at 16 384; below ~3000 envs, where a step is one
 // wavefront's latency, and in the closed loop (tick and sim back to back) the spills cost 2-9 %, so launch_sim picks it for
 // open-loop steps of 3072 envs and more (profiles/r04_f32_wpe3.txt, r04_f32_wpe3_sizes.txt).  Same arithmetic: bit-identical.
-template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE>
+// XF = the step reads the external wrenches xfrc (tsidb_set_xfrc); launch_sim selects it only while a buffer is registered,
+// so the kernels without it are unchanged (xfrc is then not read).
+template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false>
 __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))) void k_sim(const DevModel<T> *__restrict__ mp, int n, int B, SimRing<T> ring, T *qpos, T *qvel,
-                                              T *qacc_ws, const T *env_params, const T *terrain, const T *motor_tau, T *qacc, int *ncon,
+                                              T *qacc_ws, const T *env_params, const T *terrain, const T *xfrc, const T *motor_tau, T *qacc, int *ncon,
                                               int *con, int *info) {
   __shared__ SimLds<T> L;
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
@@ -244,6 +246,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
     if constexpr (MULTI) {
       asm volatile("" : "+s"(mq), "+s"(qpos), "+s"(qvel), "+s"(qacc_ws), "+s"(env_params), "+s"(terrain), "+s"(motor_tau) : : "memory");
       asm volatile("" : "+s"(qacc), "+s"(ncon), "+s"(con), "+s"(info) : : "memory");
+      if constexpr (XF) asm volatile("" : "+s"(xfrc) : : "memory");
     }
     const size_t slot = (size_t)((ring.slots >> (4 * b)) & 15ull);
     const T *q_tsid = ring.q ? ring.q + slot * (size_t)n * NQ : nullptr, *v_tsid = ring.v ? ring.v + slot * (size_t)n * NV : nullptr;
@@ -256,6 +259,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       if (lane < NQ) { big += fabs(qpos[E * NQ + lane]); chk += q_tsid ? fabs(q_tsid[E * NQ + lane]) : T(0); }
       if (lane < NV) { big += fabs(qvel[E * NV + lane]); chk += fabs(qacc_ws[E * NV + lane]) + (v_tsid ? fabs(v_tsid[E * NV + lane]) : T(0)); }
       if (lane < NA && motor_tau) chk += fabs(motor_tau[E * NA + lane]);
+      if constexpr (XF) for (int i = lane; i < NB * 6; i += WAVE) chk += fabs(xfrc[E * NB * 6 + i]); // (external wrenches)
       big = wave_sum(big);
       skip = __ballot(!(chk <= Eps<T>::inf)) || !(big <= T(SIM_STATE_BOUND));
       if (skip && wv == 0) {
@@ -267,9 +271,9 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       }
     }
     if (!skip)
-      sim_step_env<T, NW>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
-                          env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, motor_tau ? motor_tau + E * NA : nullptr,
-                          qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
+      sim_step_env<T, NW, XF>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+                          env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
+                          motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
                           info ? info + E * 4 : nullptr);
     if constexpr (MULTI) __syncthreads(); // both wavefronts; the step's state is written before the next step reads it
   }
@@ -278,9 +282,9 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
 // Two envs per wavefront (tsidb_sim2.hpp; TSIDB_OPT_SIM_PACK): env 2 p + h on lanes [32 h, 32 h + 32) of workgroup p's one
 // wavefront, each half with its own SimLds (2 x 20 KB: four workgroups = eight envs per CU, one wavefront per SIMD with the
 // whole register file).  One step per launch.  Per env bit-identical to k_sim<T, 1, false>.
-template <typename T>
+template <typename T, bool XF = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_sim2(const DevModel<T> *__restrict__ mp, int n, SimRing<T> ring, T *qpos, T *qvel,
-                                              T *qacc_ws, const T *env_params, const T *terrain, const T *motor_tau, T *qacc, int *ncon,
+                                              T *qacc_ws, const T *env_params, const T *terrain, const T *xfrc, const T *motor_tau, T *qacc, int *ncon,
                                               int *con, int *info) {
   if constexpr (SIM_PACKABLE) {
     __shared__ SimLds<T> Ls[2];
@@ -297,6 +301,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
     if (hl < NQ) { big += fabs(qpos[E * NQ + hl]); chk += q_tsid ? fabs(q_tsid[E * NQ + hl]) : T(0); }
     if (hl < NV) { big += fabs(qvel[E * NV + hl]); chk += fabs(qacc_ws[E * NV + hl]) + (v_tsid ? fabs(v_tsid[E * NV + hl]) : T(0)); }
     if (hl < NA && motor_tau) chk += fabs(motor_tau[E * NA + hl]);
+    if constexpr (XF) for (int i = hl; i < NB * 6; i += pk::LPE) chk += fabs(xfrc[E * NB * 6 + i]);
     big = pk::sum(big);
     const bool skip = pk::ballot(!(chk <= Eps<T>::inf), lane) != 0u || !(big <= T(SIM_STATE_BOUND));
     if (!live) return;
@@ -308,9 +313,10 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(1, 1))) vo
       if (con && hl < MAXCON) con[E * MAXCON + hl] = -1;
       return;
     }
-    sim_step_pair<T>(*mp, Ls[hf], lane, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
-                     env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, motor_tau ? motor_tau + E * NA : nullptr,
-                     qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr, info ? info + E * 4 : nullptr);
+    sim_step_pair<T, XF>(*mp, Ls[hf], lane, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+                     env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
+                     motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr,
+                     con ? con + E * MAXCON : nullptr, info ? info + E * 4 : nullptr);
   }
 }
 
@@ -343,7 +349,7 @@ template <typename T>
 __global__ __launch_bounds__(WAVE) void k_reset(const DevModel<T> *__restrict__ mp, int n, const int *env_ids, int n_ids, T *q,
                                                 T *v, T *qpos, T *qvel, T *qacc_ws, T *com_ref, T *posture_ref,
                                                 T *foot_ref, T *contact_ref, uint8_t *cact, T *cop_frames, T *cop_ref,
-                                                const T *done_rows, int rows_ld, const T *posture_bias, T *frames) {
+                                                const T *done_rows, int rows_ld, const T *posture_bias, T *frames, T *xfrc) {
   __shared__ TickLds<T> L;
   const DevModel<T> &m = *mp;
   const int lane = threadIdx.x;
@@ -393,6 +399,8 @@ __global__ __launch_bounds__(WAVE) void k_reset(const DevModel<T> *__restrict__ 
   if (lane < 2) cact[E * 2 + lane] = 1;
   // CoP task reference: between the soles, on the floor
   if (cop_ref && lane < 3) cop_ref[E * 3 + lane] = lane < 2 ? T(0.5) * (L.oMf[0][9 + lane] + L.oMf[1][9 + lane]) : T(0);
+  // external wrenches (tsidb_set_xfrc) end with the episode, as mj_resetData clears xfrc_applied
+  if (xfrc) for (int i = lane; i < NB * 6; i += WAVE) xfrc[E * NB * 6 + i] = 0;
 }
 
 template <typename T>
@@ -704,6 +712,7 @@ struct tsidb_ctx {
   const void *com_ref = nullptr, *posture_ref = nullptr, *foot_ref = nullptr, *contact_ref = nullptr, *cop_frames = nullptr;
   const uint8_t *contact_active = nullptr;
   const void *env_params = nullptr, *terrain = nullptr, *cop_ref = nullptr, *posture_bias = nullptr;
+  void *xfrc = nullptr; // [N, NB, 6] external body wrenches (tsidb_set_xfrc); k_reset zeroes the reset envs' rows
   int foot_body[2] = {-1, -1}; // sim bodies that carry the left / right sole frame
   unsigned long long foot_geoms[2] = {0, 0}; // bit g: collision geom g is on that body
   std::string err;
@@ -957,6 +966,16 @@ extern "C" int tsidb_set_env_params(tsidb_handle h, const void *env_params, cons
   return 0;
 }
 
+extern "C" int tsidb_set_xfrc(tsidb_handle h, void *xfrc) {
+  if (!h) return -1;
+  if (!TOPO_HAS_SIM && xfrc) {
+    h->err = "tsidb_set_xfrc: this library was built without the sim stage";
+    return 1;
+  }
+  h->xfrc = xfrc; // NULL = no external wrenches
+  return 0;
+}
+
 static void need_refs(tsidb_ctx *h) {
   if (!h->com_ref) throw std::string("reference buffers not registered (call tsidb_set_refs first)");
   if (h->params[P_W_COP] != 0.0 && !h->cop_ref) throw std::string("w_cop != 0 needs a CoP reference (tsidb_set_cop_ref)");
@@ -1005,19 +1024,26 @@ static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ri
     // take every wave slot of the GPU (2 per SIMD) for the whole batch, and the tick launched beside it "runs" 338-526 us
     // instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
     // neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
-#define TSIDB_LAUNCH_SIM(NW, MULTI)                                                                                                    \
-    hipLaunchKernelGGL((k_sim<T, NW, MULTI>), dim3(h->num_envs), dim3(WAVE * NW), h->lds_pad, s, (const DevModel<T> *)h->d_model, h->num_envs, B, ring, \
-                       (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)motor_tau,     \
+    // (a registered xfrc buffer selects the XF = true instantiations; the float32 build for three wavefronts per SIMD has none:
+    //  the default build, bit-identical to it, runs instead)
+#define TSIDB_LAUNCH_SIM_XF(NW, MULTI, XF)                                                                                                    \
+    hipLaunchKernelGGL((k_sim<T, NW, MULTI, TSIDB_WPE, XF>), dim3(h->num_envs), dim3(WAVE * NW), h->lds_pad, s, (const DevModel<T> *)h->d_model, h->num_envs, B, ring, \
+                       (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau,     \
                        (T *)qacc, ncon, con, info)
-    if (sizeof(T) == 4 && B == 1 && h->sim_waves == 1 && !h->sim_pack && !motor_tau && h->num_envs >= 3072 && !h->lds_pad)
+#define TSIDB_LAUNCH_SIM(NW, MULTI) do { if (h->xfrc) TSIDB_LAUNCH_SIM_XF(NW, MULTI, true); else TSIDB_LAUNCH_SIM_XF(NW, MULTI, false); } while (0)
+    if (sizeof(T) == 4 && B == 1 && h->sim_waves == 1 && !h->sim_pack && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc)
       hipLaunchKernelGGL((k_sim<T, 1, false, (sizeof(T) == 4 ? 3 : TSIDB_WPE)>), dim3(h->num_envs), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, B, ring,
-                         (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)motor_tau, (T *)qacc, ncon, con, info);
+                         (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau, (T *)qacc, ncon, con, info);
+    else if (B == 1 && h->sim_pack && SIM_PACKABLE && h->xfrc)
+      hipLaunchKernelGGL((k_sim2<T, true>), dim3((h->num_envs + 1) / 2), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, ring, (T *)qpos, (T *)qvel,
+                         (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau, (T *)qacc, ncon, con, info);
     else if (B == 1 && h->sim_pack && SIM_PACKABLE)
       hipLaunchKernelGGL((k_sim2<T>), dim3((h->num_envs + 1) / 2), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, ring, (T *)qpos, (T *)qvel,
-                         (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)motor_tau, (T *)qacc, ncon, con, info);
+                         (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau, (T *)qacc, ncon, con, info);
     else if (B > 1) { if (h->sim_waves == 2) TSIDB_LAUNCH_SIM(2, true); else TSIDB_LAUNCH_SIM(1, true); }
     else { if (h->sim_waves == 2) TSIDB_LAUNCH_SIM(2, false); else TSIDB_LAUNCH_SIM(1, false); }
 #undef TSIDB_LAUNCH_SIM
+#undef TSIDB_LAUNCH_SIM_XF
   }
   HIP_OK(hipGetLastError());
 }
@@ -1051,7 +1077,7 @@ static void launch_reset(tsidb_ctx *h, const int32_t *env_ids, int n_ids, void *
   hipLaunchKernelGGL(k_reset<T>, dim3(grid), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, env_ids, n_ids, (T *)q,
                      (T *)v, (T *)qpos, (T *)qvel, (T *)qacc_ws, (T *)h->com_ref, (T *)h->posture_ref, (T *)h->foot_ref,
                      (T *)h->contact_ref, (uint8_t *)h->contact_active, (T *)h->cop_frames, (T *)h->cop_ref, (const T *)done_rows,
-                     rows_ld, (const T *)h->posture_bias, (T *)frames);
+                     rows_ld, (const T *)h->posture_bias, (T *)frames, (T *)h->xfrc);
   HIP_OK(hipGetLastError());
 }
 

@@ -961,10 +961,25 @@ __device__ __forceinline__ void rows_eval(const RowState<T> &rs, T alpha, T &c, 
 // run, redundantly and in lockstep - wavefront 1 does the collision phase while wavefront 0 builds bias forces and the mass
 // matrix, factors it and solves for the unconstrained acceleration; they join before the constraint rows, and wavefront 0
 // finishes the step alone.  Same operations on the same data: results are bit-identical to NW = 1.
-template <typename T, int NW>
+// External wrench on a body (tsidb_set_xfrc; MuJoCo's xfrc_applied[b + 1]): w = force (3) then torque (3), world frame,
+// applied at the body's centre of mass cw.  The bias force fb is a spatial force about the world origin, [linear; angular]
+// like the dof axes S (hk = S . f: rows 0-2 of S are the world-frame linear dofs, rows 3-5 of the root's angular dofs are
+// its body axes in world coordinates): the wrench is [F; tau + cw x F] there.  It acts ON the body, so it leaves the bias:
+// qfrc_smooth = -S . (fb - w) gains J_b^T w.  (An all-zero w leaves fb bit-identical: F = +0, tau + cw x F = +0.)
+template <typename T> __device__ __forceinline__ void sub_xfrc(const T *w, const T *cw, T *fb) {
+  const T F[3] = {w[0], w[1], w[2]};
+  T cxf[3];
+  cross3(cw, F, cxf);
+#pragma unroll
+  for (int i = 0; i < 3; i++) { fb[i] -= F[i]; fb[3 + i] -= w[3 + i] + cxf[i]; }
+}
+
+// XF: the kernel reads external wrenches (xfrc, the env's [NB, 6] rows; tsidb_set_xfrc).  A template parameter rather than a
+// runtime NULL test: the test alone cost the multi-step and the three-wavefront float32 kernels VGPR spills.
+template <typename T, int NW, bool XF>
 __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
-                             T *qacc_ws_g, const T *envp, const T *terr_g, const T *motor_tau, T *qacc_out, int *ncon_out, int *con_out,
-                             int *info) {
+                             T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
+                             int *con_out, int *info) {
   // per-env randomisation (BASELINE config 5), NULL = nominal: mass scale, contact friction, floor plane
   const T mscale = envp ? envp[0] : T(1);
   Floor<T> &fl = L.fl;
@@ -1116,6 +1131,12 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
       cross_mf(Vb, Yv, vx);
 #pragma unroll
       for (int i = 0; i < 6; i++) fb[i] = Ya[i] + vx[i];
+      if constexpr (XF) {
+        T w[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) w[i] = xfrc[6 * b + i];
+        sub_xfrc(w, cw, fb);
+      }
     }
     const int mylast = lane < NB ? m.mj_last[lane] : lane;
 #pragma unroll

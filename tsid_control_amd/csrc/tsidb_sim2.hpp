@@ -299,9 +299,9 @@ __device__ __noinline__ NewtonDir<T> newton_direction_p(const DevModel<T> &m, Si
 }
 
 // sim_step_env<T, 1> (tsidb_sim.hpp) for the env on the caller's half of the wavefront.  lane = 0..63; L = the env's LDS.
-template <typename T>
+template <typename T, bool XF>
 __device__ __forceinline__ void sim_step_pair(const DevModel<T> &m, SimLds<T> &L, int lane, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
-                                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *motor_tau, T *qacc_out, int *ncon_out,
+                                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
                                               int *con_out, int *info) {
   static_assert(SIM_PACKABLE, "two envs per wavefront need the robot's bodies, dofs, geoms and contacts on 32 lanes");
   constexpr int LPE = pk::LPE;
@@ -445,6 +445,12 @@ __device__ __forceinline__ void sim_step_pair(const DevModel<T> &m, SimLds<T> &L
       cross_mf(Vb, Yv, vx);
 #pragma unroll
       for (int i = 0; i < 6; i++) fb[i] = Ya[i] + vx[i];
+      if constexpr (XF) {
+        T w[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) w[i] = xfrc[6 * b + i];
+        sub_xfrc(w, cw, fb);
+      }
     }
     const int mylast = (hl < NB ? m.mj_last[hl] : hl) | hbase; // (a lane of this env's half)
 #pragma unroll

@@ -54,7 +54,7 @@ class WalkController:
         self.params = pack_params(conf, self.model.effort_limit, self.model.velocity_limit)
         # one library per robot: pick the build whose dimensions are the blob's (libtsidb.so = v1, libtsidb_v0.so = robot/v0)
         self._L = L = _lib.load_for(self.model["model_dims"])
-        NJ_, NQ, NV, NA, _nb, self.has_sim = _lib.dims(L)
+        NJ_, NQ, NV, NA, self.NB, self.has_sim = _lib.dims(L)
         NOBS, NROW = NQ + NV + 12, NQ + NV + 14
         self.NQ, self.NV, self.NA, self.NOBS, self.NROW = NQ, NV, NA, NOBS, NROW
         self._h = C.c_void_p()
@@ -83,6 +83,7 @@ class WalkController:
         self.info = z(N, 4, dt=torch.int32)
         self.env_params = None
         self.terrain = None
+        self.xfrc = None   # external body wrenches [N, NB, 6] (set_xfrc / apply_push); None = none registered
         rc = L.tsidb_set_refs(self._h, _ptr(self.com_ref), _ptr(self.posture_ref), _ptr(self.foot_ref),
                               _ptr(self.contact_ref), _ptr(self.contact_active), _ptr(self.cop_frames))
         _lib.check(L, self._h, rc, "tsidb_set_refs")
@@ -190,6 +191,64 @@ class WalkController:
         rc = self._L.tsidb_set_env_params(self._h, _ptr(self.env_params), _ptr(self.terrain))
         _lib.check(self._L, self._h, rc, "tsidb_set_env_params")
 
+    # ------------------------------------------------------------------ external wrenches (push recovery)
+    def set_xfrc(self, t=None):
+        """Register t [N, NB, 6] (self.dtype, on self.device, contiguous) as the sim stage's external body wrenches -
+        MuJoCo's mj_data.xfrc_applied[1:] (include/tsidb.h tsidb_set_xfrc): per sim body (the blob's order, body 0 = the
+        torso) force (3) then torque (3), world frame, at the body's centre of mass; read by every sim step until changed.
+        The tensor is used in place, not copied: self.xfrc is it.  None unregisters (no external wrenches).
+        A caller that writes self.xfrc in place while step_pipelined() / capture_steps() is in use must call sync_sim()
+        first, as the methods here do: a sim stage left unlaunched would otherwise read the new values."""
+        self.sync_sim()   # sim stages step_pipelined() has not launched yet belong to the old wrenches
+        if t is not None:
+            shape = (self.num_envs, self.NB, 6)
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device \
+                    or not t.is_contiguous():
+                what = (tuple(t.shape), t.dtype, t.device, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)
+                raise _lib.TsidbError(f"set_xfrc: need a contiguous {shape} {self.dtype} tensor on {self.device}, got {what}")
+        _lib.check(self._L, self._h, self._L.tsidb_set_xfrc(self._h, _ptr(t)), "tsidb_set_xfrc")
+        self.xfrc = t
+
+    def _xfrc_rows(self, env_ids):
+        if self.xfrc is None:
+            self.set_xfrc(torch.zeros(self.num_envs, self.NB, 6, dtype=self.dtype, device=self.device))
+        if env_ids is None:
+            return slice(None)
+        if isinstance(env_ids, torch.Tensor):
+            return env_ids.to(self.device).long().reshape(-1)
+        return torch.as_tensor(np.asarray(env_ids, dtype=np.int64), device=self.device).reshape(-1)
+
+    def apply_push(self, force, torque=None, body=0, env_ids=None):
+        """Set the external wrench on sim body `body` (0 = torso; body_masses() lists the others) of the envs env_ids
+        (None = all): force [3] or [n, 3], torque likewise (None = 0), world frame, at the body's centre of mass.  It acts on
+        every sim step until changed (clear_pushes()) or the env is reset.  Registers a zero buffer on first use."""
+        self.sync_sim()
+        rows = self._xfrc_rows(env_ids)
+        w = torch.zeros(6, dtype=self.dtype, device=self.device)
+        f = torch.as_tensor(force, dtype=self.dtype, device=self.device)
+        tq = torch.zeros(3, dtype=self.dtype, device=self.device) if torque is None else \
+            torch.as_tensor(torque, dtype=self.dtype, device=self.device)
+        if f.dim() == 1 and tq.dim() == 1:
+            w[:3], w[3:] = f, tq
+        else:
+            w = torch.cat(torch.broadcast_tensors(f.reshape(-1, 3), tq.reshape(-1, 3)), dim=1)
+        self.xfrc[rows, int(body)] = w
+
+    def clear_pushes(self, env_ids=None):
+        """Zero every external wrench of the envs env_ids (None = all)."""
+        self.sync_sim()
+        if self.xfrc is None:
+            return
+        self.xfrc[self._xfrc_rows(env_ids)] = 0
+
+    def body_masses(self):
+        """[N, NB] mass of every sim body (the blob's mj_inertia[:, 0] times the env's mass scale, set_env_params): what a
+        uniform acceleration field a needs as forces, F_b = m_b a.  v1 robot (robot.xml document order): torso 0, left
+        foot 6, right foot 12, camera enclosure 20."""
+        m = torch.as_tensor(self.model["mj_inertia"].reshape(self.NB, 10)[:, 0].copy(), dtype=self.dtype, device=self.device)
+        scale = self.env_params[:, 0:1] if self.env_params is not None else torch.ones(self.num_envs, 1, dtype=self.dtype, device=self.device)
+        return scale * m
+
     def randomize(self, seed=2, mass=(0.8, 1.2), friction=(0.4, 1.0), tilt_deg=5.0, step_height=0.01, step_length=(0.04, 0.12)):
         """BASELINE config 5 workload: body-mass scale U(mass), contact friction
         U(friction), floor = random plane through the origin tilted by at most tilt_deg, with terrain steps of
@@ -292,7 +351,8 @@ class WalkController:
         (the default for up to 1024 envs is 8) the last few sim stages are not even launched until the batch is full, so a
         device / stream synchronize does not make the sim state current - sync_sim() launches them and makes the current
         stream wait.  Every entry point of this class that reads or rewrites sim-side data (step, sim_step, reset,
-        reset_done, set_params, set_env_params, capture_steps, WalkSchedule.apply with touch-down feedback) calls it.
+        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, capture_steps, WalkSchedule.apply with
+        touch-down feedback) calls it.
         `events` = four torch.cuda.Event recorded around the tick (current stream) and around the sim (sim stream), for
         timing."""
         if getattr(self.conf, "closed_loop", False) or not getattr(self.conf, "sim_enabled", True):
@@ -498,7 +558,7 @@ class WalkController:
 
         class _Graph:
             steps = n_steps
-            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"])   # what the captured kernels point at
+            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc)   # what the captured kernels point at
 
             def replay(self_inner):
                 g.replay()
