@@ -1,8 +1,8 @@
 """External body wrenches of the sim stage (tsidb_set_xfrc; MuJoCo's mj_data.xfrc_applied, the field a caller of mj_step
 writes to push the robot, main.py:192-195): no behaviour change without them, the spatial-force conversion against an
 independent computation (a uniform acceleration field, generalized forces J_b^T w_b from a numpy forward kinematics of the
-blob, a couple against motor torques in the oracle), push recovery, reset, the pipelined / captured / packed paths and the
-input guard."""
+blob, a couple against motor torques in the oracle), push recovery, reset, the pipelined and captured paths and the input
+guard."""
 import ctypes as C
 
 import numpy as np
@@ -334,21 +334,7 @@ def test_limb_push_in_a_captured_graph_equals_eager():
     assert not torch.equal(c.qpos, b.qpos)                 # (the rewrite did act)
 
 
-# ---------------------------------------------------------------------------- (h) packed sim kernel
-def test_packed_sim_with_pushes_is_bit_identical():
-    n = 33
-    a, b = closed_standing(n, sim_waves=1, sim_pack=0), closed_standing(n, sim_waves=1, sim_pack=1)
-    w = torch.randn(n, a.NB, 6, dtype=torch.float64, generator=torch.Generator().manual_seed(4)) * 0.5
-    w[:, :, 3:] *= 0.05
-    for x in (a, b):
-        x.set_xfrc(w.to(x.device).contiguous())
-    for _ in range(30):
-        a.step(); b.step()
-    torch.cuda.synchronize()
-    same(a, b)
-
-
-# ---------------------------------------------------------------------------- (i) errors and non-finite input
+# ---------------------------------------------------------------------------- (h) errors and non-finite input
 def test_set_xfrc_errors_and_non_finite_wrench():
     from tsid_control_amd._lib import TsidbError
     n = 8

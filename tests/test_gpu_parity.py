@@ -635,6 +635,10 @@ def test_api_error_behaviour():
     L.tsidb_destroy(h)
     rc = L.tsidb_create(wc.model.raw, len(wc.model.raw), wc.params.ctypes.data_as(C.c_void_p), P_COUNT, 4, 0, 0, C.byref(h))
     assert rc == 0
+    for val in (0, 1):   # option 4 is retired (it selected the removed packed sim kernel): unknown, like any other
+        assert L.tsidb_set_option(h, 4, val) != 0 and b"unknown option" in L.tsidb_last_error(h)
+    v = C.c_int(-7)
+    assert L.tsidb_get_option(h, 4, C.byref(v)) != 0 and b"unknown option" in L.tsidb_last_error(h) and v.value == -7
     rc = L.tsidb_tick(h, None, None, None, None, None, None, None, 65, None, None, None)
     assert rc != 0 and b"tsidb_set_refs" in L.tsidb_last_error(h)   # references never registered
     L.tsidb_destroy(h)
@@ -1695,31 +1699,6 @@ def test_two_wavefront_sim_is_bit_identical():
     for k in ("q", "v", "tau", "qpos", "qvel", "qacc_warmstart", "ncon", "con_pairs", "info", "rows"):
         assert torch.equal(getattr(a, k), getattr(b, k)), k
     assert int(a.ncon.max()) > 4 and int((a.con_pairs & 0x8000).bool().sum()) > 0     # floor and robot<->robot contacts were there
-
-
-@pytest.mark.parametrize("dtype,n", [("f64", 96), ("f64", 33), ("f32", 64)])
-def test_packed_sim_is_bit_identical(dtype, n):
-    """conf.sim_pack: the sim kernel with TWO envs per wavefront (tsidb_sim2.hpp: 32 lanes per env, DPP broadcasts instead of
-    v_readlane, per-env divergent control flow) against one env per wavefront - same operations on the same data in the same
-    order, bit for bit: perturbed standing, randomised floors with terrain steps, self-colliding poses (MPR, dense Newton
-    factor), an odd number of envs (the last wavefront holds one env), envs paired with a diverged neighbour"""
-    a, b = make(n, dtype, sim_waves=1, sim_pack=0), make(n, dtype, sim_waves=1, sim_pack=1)
-    for w in (a, b):
-        perturb(w, 41, dq=0.04, dv=0.05)
-        w.randomize(seed=3)
-        w.qpos[: n // 3, 7:] = _self_collision_poses(n // 3, 5).to(w.device, w.dtype)
-        w.qvel[n - 2, :] = 1e9     # a diverged env (its step is skipped, failure bit 4) beside a healthy one
-    for i in range(30):
-        a.step()
-        b.step()
-    for i in range(20):
-        a.sim_step(teleport=False)
-        b.sim_step(teleport=False)
-    torch.cuda.synchronize()
-    for k in ("q", "v", "tau", "qpos", "qvel", "qacc_warmstart", "ncon", "con_pairs", "info", "rows"):
-        assert torch.equal(getattr(a, k), getattr(b, k)), (k, (getattr(a, k) != getattr(b, k)).nonzero()[:8].tolist())
-    assert int(a.ncon.max()) > 4 and int((a.con_pairs & 0x8000).bool().sum()) > 0     # floor and robot<->robot contacts were there
-    assert int(a.info[n - 2, 3]) == 4 and int(a.info[n - 1, 3]) != 4
 
 
 def test_fused_walk_tick_and_device_episodes_in_the_pipelined_loop():

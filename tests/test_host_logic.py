@@ -100,10 +100,11 @@ def test_truncated_model_blob_is_rejected_on_the_host(blob):
         L.tsidb_destroy(h)
 
 
-def test_bench_contract_and_execution_options():
+def test_bench_contract_and_execution_option_numbers():
     """bench.py's command line (the driver's contract: --gpus / --steps / --warmup, defaults that finish in minutes) and the
-    execution options that must not change results: every secondary run names every attribute run_workload reads, the
-    option numbers of include/tsidb.h are the ones the facade passes, RobotConfig carries their switches."""
+    execution options: every secondary run names every attribute run_workload reads, the option numbers of include/tsidb.h
+    are the ones the facade passes, RobotConfig carries their switches, and the retired option 4 (the removed packed sim
+    kernel) is neither declared nor set."""
     import sys
     import importlib
     sys.path.insert(0, str(ROOT))
@@ -124,12 +125,15 @@ def test_bench_contract_and_execution_options():
         sys.argv = argv
     assert bench.TICK_WORDS == 347 and bench.SIM_WORDS == 185 and bench.HBM_PEAK_GBS == 8000.0
     hdr = (ROOT / "include" / "tsidb.h").read_text()
-    m = re.search(r"enum \{ TSIDB_OPT_SIM_WAVES = (\d+), TSIDB_OPT_LDS_PAD = (\d+), TSIDB_OPT_CU_SPLIT = (\d+), TSIDB_OPT_SIM_PACK = (\d+), TSIDB_OPT_QP_FAST_EQ = (\d+) \}", hdr)
-    assert m and [int(g) for g in m.groups()] == [1, 2, 3, 4, 5]
+    m = re.search(r"enum \{ TSIDB_OPT_SIM_WAVES = (\d+), TSIDB_OPT_LDS_PAD = (\d+), TSIDB_OPT_CU_SPLIT = (\d+), TSIDB_OPT_QP_FAST_EQ = (\d+) \}", hdr)
+    assert m and [int(g) for g in m.groups()] == [1, 2, 3, 5]
+    assert "TSIDB_OPT_SIM_PACK" not in hdr   # option 4 is retired with the packed sim kernel
     wc_src = (ROOT / "tsid_control_amd" / "walk_controller.py").read_text()
-    assert "tsidb_set_option(self._h, 1, sw)" in wc_src and "tsidb_set_option(self._h, 4, sp)" in wc_src and "tsidb_set_option(self._h, 5, fe)" in wc_src
+    assert "tsidb_set_option(self._h, 1, sw)" in wc_src and "tsidb_set_option(self._h, 5, fe)" in wc_src
+    assert not re.search(r"tsidb_set_option\(\s*self\._h\s*,\s*4\s*,", wc_src)
     from tsid_control_amd import RobotConfig
-    assert RobotConfig.sim_pack == -1 and RobotConfig.qp_fast_equalities == -1 and RobotConfig.sim_waves == 0 and RobotConfig.pipeline_sim_batch == 0
+    assert not hasattr(RobotConfig, "sim_pack")
+    assert RobotConfig.qp_fast_equalities == -1 and RobotConfig.sim_waves == 0 and RobotConfig.pipeline_sim_batch == 0
     # the flat compute-roofline scalars come from the committed counter passes
     import json
     t = json.loads((ROOT / "profiles" / "pmc_traffic.json").read_text())

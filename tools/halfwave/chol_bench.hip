@@ -1,7 +1,7 @@
 // Micro-benchmark (diagnostic, not part of the product): k_sim's tree-sparse 26 x 26 factorisation + the two substitutions
 //   mode 0  the product's one-env-per-wavefront code (tsidb_sim.hpp: chol26_factor / chol26_subst; v_readlane broadcasts),
 //           20 KB of LDS per workgroup = 8 workgroups per CU, two wavefronts per SIMD - the residency k_sim runs at
-//   mode 1  two envs per wavefront (tsidb_pack.hpp: DPP row_newbcast broadcasts), 40 KB per workgroup = 4 per CU, one
+//   mode 1  two envs per wavefront (tsidb_pack.hpp next to this file: DPP row_newbcast broadcasts), 40 KB per workgroup = 4 per CU, one
 //           wavefront per SIMD - the same 8 envs per CU
 // Both produce the same bits (checked).  Time = one launch of NENV envs x REPS repetitions.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I tsid_control_amd/csrc -o tools/halfwave/chol_bench tools/halfwave/chol_bench.hip

@@ -1,4 +1,6 @@
 // tsidb_pack.hpp - cross-lane primitives of the PACKED layout: two envs per wavefront, env h on lanes [32 h, 32 h + 32).
+// Used by chol_bench.hip.  The packed sim kernel built on them (round 4) measured slower than the one-env kernel and was
+// removed from the product; these primitives stay with the micro-benchmark that measured them.
 //
 // Why: the one-env-per-wavefront kernels use 26 (dofs) / 21 (bodies) / <= 32 (contacts) of the 64 lanes, so 59 % of every
 // vector instruction is idle lanes, and a float64 broadcast (lane k -> all) costs two v_readlane through the scalar
@@ -10,7 +12,7 @@
 //              instruction for both envs, no SGPR, no v_readlane -> VALU hazard.
 // Reductions are the 64-lane ones cut after the row step: quad_perm / row_half_mirror / row_mirror give every lane its row
 // total, then dup() + one add give R0 + R1 to both rows of the env.  Same operands in the same order as tsidb_common.hpp's
-// wave_sum on a vector that is zero on lanes >= 32 (there: (0 + 0) + (R1 + R0)), so the packed kernels reproduce the
+// wave_sum on a vector that is zero on lanes >= 32 (there: (0 + 0) + (R1 + R0)), so packed code reproduces the
 // one-env kernels' sums bit for bit.
 // Values that are wave-uniform in the one-env kernels (contact counts, iteration counters, Newton state) are uniform per
 // ENV here and live in VGPRs; control flow on them is ordinary divergent SIMT code, and every cross-lane operation in this

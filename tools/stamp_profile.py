@@ -68,8 +68,6 @@ for nm, k in (("  rbd: setup+sincos", 15), ("  rbd: depth loop", 23), ("  rbd: i
     print(f"{nm:26s} {np.median(b[:, k]):10.0f} cyc")
 names_s = ["kin+bias+M", "qacc_smooth chol", "collision", "rows+warmstart", "newton loop", "euler+write"]
 idx_s = [(16, 17), (17, 18), (18, 19), (19, 20), (20, 21), (21, 22)]
-if int(__import__("os").environ.get("TSIDB_SIM_PACK", "0")):   # packed sim kernel: one workgroup (= one stamp row) per PAIR of envs
-    b = b[: (n + 1) // 2]
 tot = np.median(b[:, 22] - b[:, 16])
 print(f"k_sim: ncon mean {wc.ncon.float().mean():.1f}; newton iters mean {wc.info[:,2].float().mean():.2f}")
 for nm, ix in zip(names_s, idx_s):
