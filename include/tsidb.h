@@ -60,7 +60,9 @@ int tsidb_create(const void *model_blob, size_t nbytes, const double *params, in
 int tsidb_destroy(tsidb_handle h);
 const char *tsidb_last_error(tsidb_handle h);
 
-/* RobotConfig edits after construction (the reference edits ctrl/conf.py and rebuilds) */
+/* RobotConfig edits after construction (the reference edits ctrl/conf.py and rebuilds).  First waits for the kernels in
+ * flight on the streams this handle has launched on (on the whole device once there have been more than 32 of them), so
+ * every stream a handle has launched on must outlive the handle or be released with tsidb_stream_destroy. */
 int tsidb_set_params(tsidb_handle h, const double *params, int n_params);
 
 /* task references: comTask.setReference (WalkController.py:152), postureTask.setReference (:165),

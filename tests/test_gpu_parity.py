@@ -885,6 +885,50 @@ def test_set_params_in_the_middle_of_a_sim_batch():
         assert torch.equal(getattr(a, k), getattr(b, k)), k
 
 
+def test_set_params_after_launches_on_more_than_32_streams():
+    """tsidb_set_params waits for the kernels in flight on every stream the handle has launched on before it replaces the
+    model constants - also once there have been more streams than the 32 it keeps track of (then it waits for the device).
+    A handle stepped on 40 streams in turn, the last ones possibly still running at set_params(), ends bit-identical to
+    one stepped on a single stream across a RobotConfig edit."""
+    import ctypes as C
+    from tsid_control_amd import _lib
+    a, b = make(64, reference_quirks=False), make(64, reference_quirks=False)
+    perturb(a, 9); perturb(b, 9)
+    L, h = b._L, b._h
+    # plain non-blocking streams: a CU-masked stream is a blocking one, ordered against the copy of the new constants anyway
+    _lib.check(L, h, L.tsidb_set_option(h, 3, 0), "tsidb_set_option(cu_split)")
+    handles = []
+    try:
+        for _ in range(40):
+            hs = C.c_void_p()
+            _lib.check(L, h, L.tsidb_stream_create(h, 0, C.byref(hs)), "tsidb_stream_create")
+            handles.append(hs)
+        cur = prev = torch.cuda.current_stream(b.device)
+        for hs in handles:
+            st = torch.cuda.ExternalStream(hs.value, device=b.device)
+            st.wait_stream(prev)
+            with torch.cuda.stream(st):
+                b.step()
+            a.step()
+            prev = st
+        assert len({hs.value for hs in handles}) == 40
+        for w in (a, b):
+            w.conf.dt = 0.003
+            w.conf.sim_frictionloss_scale = 0.5
+            w.set_params()
+        cur.wait_stream(prev)
+        for _ in range(3):
+            a.step()
+            b.step()
+        torch.cuda.synchronize()
+        for k in ("q", "v", "tau", "dv", "f", "status", "obs", "qpos", "qvel", "qacc_warmstart", "ncon", "con_pairs", "info"):
+            assert torch.equal(getattr(a, k), getattr(b, k)), k
+    finally:
+        torch.cuda.synchronize()
+        for hs in handles:
+            L.tsidb_stream_destroy(h, hs)
+
+
 @pytest.mark.parametrize("dephase", [False, True])
 def test_walk_update_kernel_matches_oracle_restatement(oracle, dephase):
     """f-2's independent check: tsidb_walk_update (k_walk) against oracle/or_walk.c - a C restatement of

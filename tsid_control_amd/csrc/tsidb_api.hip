@@ -651,17 +651,24 @@ static void chain_table(const int *parent, int n, int (*chain)[8]) {
 
 } // namespace
 
+// Batches up to this many envs default to two wavefronts per env in k_sim and to CU-split streams (tsidb_stream_create):
+// measured, DESIGN.md section 5 "Streams"
+constexpr int SMALL_BATCH_ENVS = 512;
+
 struct tsidb_ctx {
   int device = 0, dtype = 0, num_envs = 0;
   int sim_waves = 1; // wavefronts per env in k_sim (tsidb_set_option)
   std::vector<hipStream_t> used_streams; // streams this handle has launched model-reading kernels on (tsidb_set_params waits for them)
+  bool streams_overflow = false;         // more streams than the table holds: tsidb_set_params waits for the whole device
   void note_stream(hipStream_t s) {
     for (hipStream_t x : used_streams) if (x == s) return;
     if (used_streams.size() < 32) used_streams.push_back(s);
+    else streams_overflow = true;
   }
   int qp_fast_eq = 1; // the tick tries the equality-constrained optimum by a PP x PP Cholesky before the QR (TSIDB_OPT_QP_FAST_EQ)
   unsigned lds_pad = 0; // diagnostic: unused dynamic LDS per workgroup of k_tick / k_sim (occupancy experiments)
-  int cu_split = -1;    // tsidb_stream_create: tick and sim streams on disjoint halves of the CUs (-1 = up to 512 envs)
+  int cu_split = -1;    // tsidb_stream_create: tick and sim streams on disjoint halves of the CUs (-1 = up to SMALL_BATCH_ENVS)
+  bool cu_split_on() const { return cu_split == 1 || (cu_split < 0 && num_envs <= SMALL_BATCH_ENVS); }
   Blob blob;
   std::vector<double> params;
   void *d_model = nullptr, *d_hull = nullptr, *d_box = nullptr;
@@ -680,6 +687,13 @@ struct tsidb_ctx {
     hipError_t e_ = (call);                                                           \
     if (e_ != hipSuccess) throw std::string(#call " failed: ") + hipGetErrorString(e_); \
   } while (0)
+
+// The one branch on the arithmetic type: fn(T()) with T = double for TSIDB_F64, float otherwise
+template <typename F>
+static auto with_dtype(int dtype, F &&fn) {
+  if (dtype == TSIDB_F64) return fn(double());
+  return fn(float());
+}
 
 template <typename T>
 static void build_model(tsidb_ctx *h, DevModel<T> &m) {
@@ -938,72 +952,6 @@ static void need_refs(tsidb_ctx *h) {
   if (h->params[P_W_COP] != 0.0 && !h->cop_ref) throw std::string("w_cop != 0 needs a CoP reference (tsidb_set_cop_ref)");
 }
 
-template <typename T>
-static void launch_tick(tsidb_ctx *h, void *q, void *v, void *tau, void *dv, void *f, int32_t *status, void *obs, int obs_ld,
-                        void *frames, int32_t *info, hipStream_t s, const void *qpos_sim = nullptr,
-                        const void *qvel_sim = nullptr, const WalkArgs<T> *walk = nullptr, void *q_snap = nullptr, void *v_snap = nullptr) {
-  if (obs && obs_ld < NOBS) throw std::string("obs row stride must be at least TSIDB_NOBS");
-  h->note_stream(s);
-  WalkArgs<T> wa;
-  memset(&wa, 0, sizeof wa);
-  if (walk) wa = *walk;
-#define TSIDB_LAUNCH_TICK(COP)                                                                                             \
-  hipLaunchKernelGGL((k_tick<T, COP>), dim3(h->num_envs), dim3(WAVE), h->lds_pad, s, (const DevModel<T> *)h->d_model, h->num_envs,   \
-                     (T *)q, (T *)v, (const T *)h->com_ref, (const T *)h->posture_ref, (const T *)h->foot_ref,             \
-                     (const T *)h->contact_ref, h->contact_active, (const T *)h->cop_frames, (T *)tau, (T *)dv, (T *)f,    \
-                     status, (T *)obs, obs_ld, (T *)frames, info, (const T *)qpos_sim, (const T *)qvel_sim, (const T *)h->cop_ref, wa, \
-                     (T *)q_snap, (T *)v_snap, h->qp_fast_eq)
-  if (h->params[P_W_COP] != 0.0) TSIDB_LAUNCH_TICK(true);
-  else TSIDB_LAUNCH_TICK(false);
-#undef TSIDB_LAUNCH_TICK
-  HIP_OK(hipGetLastError());
-}
-template <typename T>
-static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ring, const int32_t *slots, void *qpos, void *qvel, void *qacc_ws, void *qacc,
-                       int32_t *ncon, int32_t *con, int32_t *info, hipStream_t s, const void *motor_tau = nullptr) {
-  if constexpr (!TOPO_HAS_SIM) throw std::string("this library was built without the sim stage");
-  else {
-    if (B < 1 || B > TSIDB_MAX_SIM_BATCH) throw std::string("sim batch must be 1 .. TSIDB_MAX_SIM_BATCH steps");
-    h->note_stream(s);
-    SimRing<T> ring;
-    ring.q = (const T *)q_ring; ring.v = (const T *)v_ring; ring.slots = 0;
-    for (int b = 0; b < B; b++) {
-      const int sl = slots ? slots[b] : 0;
-      if (sl < 0 || sl > 15) throw std::string("sim batch: slot numbers must be 0 .. 15");
-      ring.slots |= (unsigned long long)sl << (4 * b);
-    }
-    // Two wavefronts per env (collision beside the unconstrained dynamics, bit-identical) shorten the step only while every
-    // wavefront has a SIMD to itself: 2 N sim wavefronts + N of the tick running beside them on 1024 SIMDs, or 2 N on the
-    // 512 SIMDs of the sim stream's half when the streams are CU-split (<= 512 envs) - the library picks NW = 2 up to 512
-    // envs (tsidb_create; k_sim 5-9 % shorter; at 448 / 512 envs it pays since round 4's shorter tick made the sim the longer
-    // stream there: 7.8 -> 8.0 M env-steps/s).  Beyond that it loses, and the round-4 traces show how
-    // (profiles/r04_trace_pipeline_*.txt, DESIGN.md section 5 "Streams"): at 1024 envs the 2048 wavefronts of a sim batch
-    // take every wave slot of the GPU (2 per SIMD) for the whole batch, and the tick launched beside it "runs" 338-526 us
-    // instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
-    // neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
-    // (a registered xfrc buffer selects the XF = true instantiations; the float32 build for three wavefronts per SIMD has none:
-    //  the default build, bit-identical to it, runs instead)
-#define TSIDB_LAUNCH_SIM_XF(NW, MULTI, XF)                                                                                                    \
-    hipLaunchKernelGGL((k_sim<T, NW, MULTI, TSIDB_WPE, XF>), dim3(h->num_envs), dim3(WAVE * NW), h->lds_pad, s, (const DevModel<T> *)h->d_model, h->num_envs, B, ring, \
-                       (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau,     \
-                       (T *)qacc, ncon, con, info)
-#define TSIDB_LAUNCH_SIM(NW, MULTI) do { if (h->xfrc) TSIDB_LAUNCH_SIM_XF(NW, MULTI, true); else TSIDB_LAUNCH_SIM_XF(NW, MULTI, false); } while (0)
-    if (sizeof(T) == 4 && B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc)
-      hipLaunchKernelGGL((k_sim<T, 1, false, (sizeof(T) == 4 ? 3 : TSIDB_WPE)>), dim3(h->num_envs), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, B, ring,
-                         (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc, (const T *)motor_tau, (T *)qacc, ncon, con, info);
-    else if (B > 1) { if (h->sim_waves == 2) TSIDB_LAUNCH_SIM(2, true); else TSIDB_LAUNCH_SIM(1, true); }
-    else { if (h->sim_waves == 2) TSIDB_LAUNCH_SIM(2, false); else TSIDB_LAUNCH_SIM(1, false); }
-#undef TSIDB_LAUNCH_SIM
-#undef TSIDB_LAUNCH_SIM_XF
-  }
-  HIP_OK(hipGetLastError());
-}
-template <typename T>
-static void launch_sim(tsidb_ctx *h, const void *q_tsid, const void *v_tsid, void *qpos, void *qvel, void *qacc_ws, void *qacc,
-                       int32_t *ncon, int32_t *con, int32_t *info, hipStream_t s, const void *motor_tau = nullptr) {
-  launch_sim<T>(h, 1, q_tsid, v_tsid, nullptr, qpos, qvel, qacc_ws, qacc, ncon, con, info, s, motor_tau);
-}
-
 // tsidb_walk_args (include/tsidb.h) -> the kernel's argument block, with the registered reference buffers
 template <typename T>
 static WalkArgs<T> walk_args(tsidb_ctx *h, const tsidb_walk_args *a) {
@@ -1019,16 +967,89 @@ static WalkArgs<T> walk_args(tsidb_ctx *h, const tsidb_walk_args *a) {
   return w;
 }
 
+// k_tick instantiation: the CoP force task rows are compiled in only while w_cop != 0
 template <typename T>
+static auto tick_kernel(const tsidb_ctx *h) {
+  return h->params[P_W_COP] != 0.0 ? k_tick<T, true> : k_tick<T, false>;
+}
+
+// walk: the walking reference update runs in the tick's prologue (tsidb_tick_walk); q_snap / v_snap: copies of the state it ends on
+static void launch_tick(tsidb_ctx *h, void *q, void *v, void *tau, void *dv, void *f, int32_t *status, void *obs, int obs_ld,
+                        void *frames, int32_t *info, hipStream_t s, const void *qpos_sim = nullptr, const void *qvel_sim = nullptr,
+                        const tsidb_walk_args *walk = nullptr, void *q_snap = nullptr, void *v_snap = nullptr) {
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const WalkArgs<T> wa = walk ? walk_args<T>(h, walk) : WalkArgs<T>{}; // (coef == NULL: no walking update)
+    if (obs && obs_ld < NOBS) throw std::string("obs row stride must be at least TSIDB_NOBS");
+    h->note_stream(s);
+    hipLaunchKernelGGL(tick_kernel<T>(h), dim3(h->num_envs), dim3(WAVE), h->lds_pad, s, (const DevModel<T> *)h->d_model, h->num_envs,
+                       (T *)q, (T *)v, (const T *)h->com_ref, (const T *)h->posture_ref, (const T *)h->foot_ref,
+                       (const T *)h->contact_ref, h->contact_active, (const T *)h->cop_frames, (T *)tau, (T *)dv, (T *)f,
+                       status, (T *)obs, obs_ld, (T *)frames, info, (const T *)qpos_sim, (const T *)qvel_sim, (const T *)h->cop_ref, wa,
+                       (T *)q_snap, (T *)v_snap, h->qp_fast_eq);
+  });
+  HIP_OK(hipGetLastError());
+}
+
+// k_sim instantiation for a launch of B steps, with workgroups of WAVE * h->sim_waves lanes and lds_pad bytes of dynamic LDS.
+// Two wavefronts per env (collision beside the unconstrained dynamics, bit-identical) shorten the step only while every
+// wavefront has a SIMD to itself: 2 N sim wavefronts + N of the tick running beside them on 1024 SIMDs, or 2 N on the
+// 512 SIMDs of the sim stream's half when the streams are CU-split (<= 512 envs) - the library picks NW = 2 up to 512
+// envs (tsidb_create; k_sim 5-9 % shorter; at 448 / 512 envs it pays since round 4's shorter tick made the sim the longer
+// stream there: 7.8 -> 8.0 M env-steps/s).  Beyond that it loses, and the round-4 traces show how
+// (profiles/r04_trace_pipeline_*.txt, DESIGN.md section 5 "Streams"): at 1024 envs the 2048 wavefronts of a sim batch
+// take every wave slot of the GPU (2 per SIMD) for the whole batch, and the tick launched beside it "runs" 338-526 us
+// instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
+// neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
+// (a registered xfrc buffer selects the XF = true instantiations; the float32 build for three wavefronts per SIMD has none:
+//  the default build, bit-identical to it, runs instead; it is also never picked with lds_pad != 0)
+template <typename T>
+static auto sim_kernel(const tsidb_ctx *h, int B, bool motor_tau) {
+  if constexpr (sizeof(T) == 4)
+    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc) return k_sim<float, 1, false, 3, false>;
+  const decltype(&k_sim<T, 1, false>) pick[2][2][2] = { // [sim_waves == 2][B > 1][xfrc registered]
+      {{k_sim<T, 1, false, TSIDB_WPE, false>, k_sim<T, 1, false, TSIDB_WPE, true>},
+       {k_sim<T, 1, true, TSIDB_WPE, false>, k_sim<T, 1, true, TSIDB_WPE, true>}},
+      {{k_sim<T, 2, false, TSIDB_WPE, false>, k_sim<T, 2, false, TSIDB_WPE, true>},
+       {k_sim<T, 2, true, TSIDB_WPE, false>, k_sim<T, 2, true, TSIDB_WPE, true>}}};
+  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr];
+}
+
+// B sim steps in one launch, step b driven by slot slots[b] of the [K, N, NQ] / [K, N, NV] rings q_ring / v_ring (slot 0 if NULL)
+static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ring, const int32_t *slots, void *qpos, void *qvel, void *qacc_ws,
+                       void *qacc, int32_t *ncon, int32_t *con, int32_t *info, hipStream_t s, const void *motor_tau = nullptr) {
+  if (!TOPO_HAS_SIM) throw std::string("this library was built without the sim stage");
+  if (B < 1 || B > TSIDB_MAX_SIM_BATCH) throw std::string("sim batch must be 1 .. TSIDB_MAX_SIM_BATCH steps");
+  h->note_stream(s);
+  unsigned long long slot_bits = 0;
+  for (int b = 0; b < B; b++) {
+    const int sl = slots ? slots[b] : 0;
+    if (sl < 0 || sl > 15) throw std::string("sim batch: slot numbers must be 0 .. 15");
+    slot_bits |= (unsigned long long)sl << (4 * b);
+  }
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (TOPO_HAS_SIM) // (a TSID-only build instantiates no k_sim)
+      hipLaunchKernelGGL(sim_kernel<T>(h, B, motor_tau != nullptr), dim3(h->num_envs), dim3(WAVE * h->sim_waves), h->lds_pad, s,
+                         (const DevModel<T> *)h->d_model, h->num_envs, B, SimRing<T>{(const T *)q_ring, (const T *)v_ring, slot_bits},
+                         (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc,
+                         (const T *)motor_tau, (T *)qacc, ncon, con, info);
+  });
+  HIP_OK(hipGetLastError());
+}
+
 static void launch_reset(tsidb_ctx *h, const int32_t *env_ids, int n_ids, void *q, void *v, void *qpos, void *qvel, void *qacc_ws,
                          const void *done_rows, int rows_ld, void *frames, hipStream_t s) {
   const int grid = env_ids ? n_ids : h->num_envs;
   if (grid <= 0) return;
   h->note_stream(s);
-  hipLaunchKernelGGL(k_reset<T>, dim3(grid), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, env_ids, n_ids, (T *)q,
-                     (T *)v, (T *)qpos, (T *)qvel, (T *)qacc_ws, (T *)h->com_ref, (T *)h->posture_ref, (T *)h->foot_ref,
-                     (T *)h->contact_ref, (uint8_t *)h->contact_active, (T *)h->cop_frames, (T *)h->cop_ref, (const T *)done_rows,
-                     rows_ld, (const T *)h->posture_bias, (T *)frames, (T *)h->xfrc);
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_reset<T>, dim3(grid), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, env_ids, n_ids, (T *)q,
+                       (T *)v, (T *)qpos, (T *)qvel, (T *)qacc_ws, (T *)h->com_ref, (T *)h->posture_ref, (T *)h->foot_ref,
+                       (T *)h->contact_ref, (uint8_t *)h->contact_active, (T *)h->cop_frames, (T *)h->cop_ref, (const T *)done_rows,
+                       rows_ld, (const T *)h->posture_bias, (T *)frames, (T *)h->xfrc);
+  });
   HIP_OK(hipGetLastError());
 }
 
@@ -1046,7 +1067,7 @@ int tsidb_create(const void *model_blob, size_t nbytes, const double *params, in
     if (num_envs <= 0) throw std::string("num_envs must be positive");
     if (dtype != TSIDB_F64 && dtype != TSIDB_F32) throw std::string("dtype must be TSIDB_F64 or TSIDB_F32");
     h->device = device; h->dtype = dtype; h->num_envs = num_envs;
-    h->sim_waves = num_envs <= 512 ? 2 : 1; // (measured, DESIGN.md section 5 "Streams": up to the batch size the streams are CU-split for)
+    h->sim_waves = num_envs <= SMALL_BATCH_ENVS ? 2 : 1;
     h->blob.raw.assign((const uint8_t *)model_blob, (const uint8_t *)model_blob + nbytes);
     h->blob.validate();
     { // the blob must be for the robot this library was built for
@@ -1064,7 +1085,7 @@ int tsidb_create(const void *model_blob, size_t nbytes, const double *params, in
     if (device < 0 || device >= ndev) throw std::string("no such HIP device (this library has no CPU path)");
     HIP_OK(hipSetDevice(device));
     validate_geometry(h->blob);
-    if (dtype == TSIDB_F64) upload_model<double>(h); else upload_model<float>(h);
+    with_dtype(dtype, [&](auto t) { upload_model<decltype(t)>(h); });
     if (TOPO_HAS_SIM) { // sim body of each sole frame: frame -> TSID joint -> sim joint (mj_sim2tsid) -> body
       const int *fp = h->blob.i32("pin_frame_parent", 2), *s2t = h->blob.i32("mj_sim2tsid", NA);
       for (int f = 0; f < 2; f++)
@@ -1086,10 +1107,9 @@ int tsidb_create(const void *model_blob, size_t nbytes, const double *params, in
 
 int tsidb_destroy(tsidb_handle h) {
   if (!h) return -1;
-  if (h->d_model) {
-    (void)hipSetDevice(h->device);
-    (void)hipFree(h->d_model); (void)hipFree(h->d_hull); (void)hipFree(h->d_box); (void)hipFree(h->d_eadr); (void)hipFree(h->d_edge);
-  }
+  // (a tsidb_create that failed part-way may have allocated some of them: upload_model allocates d_model last)
+  for (void *p : {h->d_model, h->d_hull, h->d_box, (void *)h->d_eadr, (void *)h->d_edge})
+    if (p) { (void)hipSetDevice(h->device); (void)hipFree(p); }
   delete h;
   return 0;
 }
@@ -1103,9 +1123,12 @@ int tsidb_set_params(tsidb_handle h, const double *params, int n_params) {
   // kernels in flight (the pipelined sim stage runs on a side stream) read the model constants: wait for the streams THIS
   // handle has launched on before the constants are replaced - not for the whole device (other handles, the caller's own
   // work and collectives keep running).  A stream the caller has destroyed since has nothing in flight: its error is dropped.
-  for (hipStream_t st : h->used_streams)
-    if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-  if (h->dtype == TSIDB_F64) upload_model<double>(h); else upload_model<float>(h);
+  // A handle that has launched on more streams than it keeps track of waits for the whole device instead.
+  if (h->streams_overflow) HIP_OK(hipDeviceSynchronize());
+  else
+    for (hipStream_t st : h->used_streams)
+      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+  with_dtype(h->dtype, [&](auto t) { upload_model<decltype(t)>(h); });
   GUARD_END
 }
 
@@ -1137,7 +1160,7 @@ int tsidb_get_option(tsidb_handle h, int option, int *value) {
   if (option == TSIDB_OPT_SIM_WAVES) { *value = h->sim_waves; return 0; }
   if (option == TSIDB_OPT_LDS_PAD) { *value = (int)h->lds_pad; return 0; }
   if (option == TSIDB_OPT_QP_FAST_EQ) { *value = h->qp_fast_eq; return 0; }
-  if (option == TSIDB_OPT_CU_SPLIT) { *value = (h->cu_split == 1 || (h->cu_split < 0 && h->num_envs <= 512)) ? 1 : 0; return 0; }
+  if (option == TSIDB_OPT_CU_SPLIT) { *value = h->cu_split_on() ? 1 : 0; return 0; }
   h->err = "tsidb_get_option: unknown option";
   return 1;
 }
@@ -1146,8 +1169,7 @@ int tsidb_stream_create(tsidb_handle h, int role, void **stream) {
   GUARD_BEGIN
   if (!stream || (role != TSIDB_STREAM_TICK && role != TSIDB_STREAM_SIM)) throw std::string("tsidb_stream_create: role must be TSIDB_STREAM_TICK or TSIDB_STREAM_SIM");
   hipStream_t s = nullptr;
-  const bool split = h->cu_split == 1 || (h->cu_split < 0 && h->num_envs <= 512);
-  if (split) {
+  if (h->cu_split_on()) {
     hipDeviceProp_t prop;
     HIP_OK(hipGetDeviceProperties(&prop, h->device));
     const int ncu = prop.multiProcessorCount, half = ncu / 2;
@@ -1185,8 +1207,7 @@ int tsidb_reset(tsidb_handle h, const int32_t *env_ids, int n_ids, void *q, void
   GUARD_BEGIN
   need_refs(h);
   if (!q || !v || !qpos || !qvel || !qacc_ws) throw std::string("tsidb_reset: null state buffer");
-  if (h->dtype == TSIDB_F64) launch_reset<double>(h, env_ids, n_ids, q, v, qpos, qvel, qacc_ws, nullptr, 0, nullptr, (hipStream_t)stream);
-  else launch_reset<float>(h, env_ids, n_ids, q, v, qpos, qvel, qacc_ws, nullptr, 0, nullptr, (hipStream_t)stream);
+  launch_reset(h, env_ids, n_ids, q, v, qpos, qvel, qacc_ws, nullptr, 0, nullptr, (hipStream_t)stream);
   GUARD_END
 }
 
@@ -1196,8 +1217,7 @@ int tsidb_reset_done(tsidb_handle h, const void *rows, int rows_ld, void *q, voi
   need_refs(h);
   if (!rows || rows_ld < NROW) throw std::string("tsidb_reset_done: needs the [N, >= TSIDB_NROW] rows tsidb_tick writes (done flag in column TSIDB_NOBS + 1)");
   if (!q || !v || !qpos || !qvel || !qacc_ws) throw std::string("tsidb_reset_done: null state buffer");
-  if (h->dtype == TSIDB_F64) launch_reset<double>(h, nullptr, 0, q, v, qpos, qvel, qacc_ws, rows, rows_ld, frames, (hipStream_t)stream);
-  else launch_reset<float>(h, nullptr, 0, q, v, qpos, qvel, qacc_ws, rows, rows_ld, frames, (hipStream_t)stream);
+  launch_reset(h, nullptr, 0, q, v, qpos, qvel, qacc_ws, rows, rows_ld, frames, (hipStream_t)stream);
   GUARD_END
 }
 
@@ -1239,14 +1259,12 @@ int tsidb_walk_plan(tsidb_handle h, const int32_t *env_ids, int n_ids, const voi
   for (int i = 0; i < 16; i++) PP.v[i] = plan_params[i];
   hipStream_t s = (hipStream_t)stream;
   const int grid = (cnt + 63) / 64;
-  if (h->dtype == TSIDB_F64)
-    hipLaunchKernelGGL(k_plan<double>, dim3(grid), dim3(64), 0, s, h->num_envs, env_ids, n_ids, (const double *)done_rows, rows_ld, PP,
-                       (const double *)h->cop_frames, (const double *)h->com_ref, path, npts, P, scale, episode, bump_episode, K, steps,
-                       (double *)coef, side, nsteps, (double *)rest, (double *)com, flags, (double *)t_offset, td_latch, t, t_device);
-  else
-    hipLaunchKernelGGL(k_plan<float>, dim3(grid), dim3(64), 0, s, h->num_envs, env_ids, n_ids, (const float *)done_rows, rows_ld, PP,
-                       (const float *)h->cop_frames, (const float *)h->com_ref, path, npts, P, scale, episode, bump_episode, K, steps,
-                       (float *)coef, side, nsteps, (float *)rest, (float *)com, flags, (float *)t_offset, td_latch, t, t_device);
+  with_dtype(h->dtype, [&](auto t_) {
+    using T = decltype(t_);
+    hipLaunchKernelGGL(k_plan<T>, dim3(grid), dim3(64), 0, s, h->num_envs, env_ids, n_ids, (const T *)done_rows, rows_ld, PP,
+                       (const T *)h->cop_frames, (const T *)h->com_ref, path, npts, P, scale, episode, bump_episode, K, steps,
+                       (T *)coef, side, nsteps, (T *)rest, (T *)com, flags, (T *)t_offset, td_latch, t, t_device);
+  });
   HIP_OK(hipGetLastError());
   GUARD_END
 }
@@ -1256,8 +1274,7 @@ int tsidb_tick(tsidb_handle h, void *q, void *v, void *tau, void *dv, void *f, i
   GUARD_BEGIN
   need_refs(h);
   if (!q || !v || !tau || !dv || !f || !status) throw std::string("tsidb_tick: null buffer");
-  if (h->dtype == TSIDB_F64) launch_tick<double>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream);
-  else launch_tick<float>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream);
+  launch_tick(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream);
   GUARD_END
 }
 
@@ -1265,8 +1282,7 @@ int tsidb_sim(tsidb_handle h, const void *q_tsid, const void *v_tsid, void *qpos
               int32_t *ncon, int32_t *con_pairs, int32_t *info, void *stream) {
   GUARD_BEGIN
   if (!qpos || !qvel || !qacc_ws) throw std::string("tsidb_sim: null state buffer");
-  if (h->dtype == TSIDB_F64) launch_sim<double>(h, q_tsid, v_tsid, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
-  else launch_sim<float>(h, q_tsid, v_tsid, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
+  launch_sim(h, 1, q_tsid, v_tsid, nullptr, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
   GUARD_END
 }
 
@@ -1274,8 +1290,7 @@ int tsidb_sim_batch(tsidb_handle h, int n_steps, const void *q_ring, const void 
                     void *qacc_ws, void *qacc, int32_t *ncon, int32_t *con_pairs, int32_t *info, void *stream) {
   GUARD_BEGIN
   if (!qpos || !qvel || !qacc_ws || !q_ring || !slots) throw std::string("tsidb_sim_batch: null buffer");
-  if (h->dtype == TSIDB_F64) launch_sim<double>(h, n_steps, q_ring, v_ring, slots, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
-  else launch_sim<float>(h, n_steps, q_ring, v_ring, slots, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
+  launch_sim(h, n_steps, q_ring, v_ring, slots, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
   GUARD_END
 }
 
@@ -1290,13 +1305,8 @@ int tsidb_step(tsidb_handle h, void *q, void *v, void *qpos, void *qvel, void *q
   hipStream_t s = (hipStream_t)stream;
   for (int it = 0; it < n_substeps; it++) {
     // closed loop: the tick reads the sim state, the sim is driven by tau and keeps its own base pose
-    if (h->dtype == TSIDB_F64) {
-      launch_tick<double>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, s, closed ? qpos : nullptr, closed ? qvel : nullptr);
-      if (sim) launch_sim<double>(h, closed ? nullptr : q, closed ? nullptr : v, qpos, qvel, qacc_ws, nullptr, ncon, con_pairs, info, s, closed ? tau : nullptr);
-    } else {
-      launch_tick<float>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, s, closed ? qpos : nullptr, closed ? qvel : nullptr);
-      if (sim) launch_sim<float>(h, closed ? nullptr : q, closed ? nullptr : v, qpos, qvel, qacc_ws, nullptr, ncon, con_pairs, info, s, closed ? tau : nullptr);
-    }
+    launch_tick(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, s, closed ? qpos : nullptr, closed ? qvel : nullptr);
+    if (sim) launch_sim(h, 1, closed ? nullptr : q, closed ? nullptr : v, nullptr, qpos, qvel, qacc_ws, nullptr, ncon, con_pairs, info, s, closed ? tau : nullptr);
   }
   GUARD_END
 }
@@ -1311,8 +1321,7 @@ int tsidb_walk_update(tsidb_handle h, const void *coef, const int32_t *side, con
                              ncon, con_pairs, td_latch, td_fraction, (const double *)t_device};
   hipStream_t s = (hipStream_t)stream;
   const int grid = (h->num_envs * 16 + 255) / 256;
-  if (h->dtype == TSIDB_F64) hipLaunchKernelGGL(k_walk<double>, dim3(grid), dim3(256), 0, s, h->num_envs, walk_args<double>(h, &a));
-  else hipLaunchKernelGGL(k_walk<float>, dim3(grid), dim3(256), 0, s, h->num_envs, walk_args<float>(h, &a));
+  with_dtype(h->dtype, [&](auto t) { hipLaunchKernelGGL(k_walk<decltype(t)>, dim3(grid), dim3(256), 0, s, h->num_envs, walk_args<decltype(t)>(h, &a)); });
   HIP_OK(hipGetLastError());
   GUARD_END
 }
@@ -1322,17 +1331,7 @@ int tsidb_tick_walk(tsidb_handle h, const tsidb_walk_args *walk, void *q, void *
   GUARD_BEGIN
   need_refs(h);
   if (!q || !v || !tau || !dv || !f || !status) throw std::string("tsidb_tick_walk: null buffer");
-  if (h->dtype == TSIDB_F64) {
-    WalkArgs<double> wa;
-    if (walk) wa = walk_args<double>(h, walk);
-    launch_tick<double>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream, nullptr, nullptr, walk ? &wa : nullptr,
-                        q_snapshot, v_snapshot);
-  } else {
-    WalkArgs<float> wa;
-    if (walk) wa = walk_args<float>(h, walk);
-    launch_tick<float>(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream, nullptr, nullptr, walk ? &wa : nullptr,
-                       q_snapshot, v_snapshot);
-  }
+  launch_tick(h, q, v, tau, dv, f, status, obs, obs_ld, frames, info, (hipStream_t)stream, nullptr, nullptr, walk, q_snapshot, v_snapshot);
   GUARD_END
 }
 
@@ -1342,14 +1341,11 @@ int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void 
   if (!q || !v || !M || !hbias || !Jcom || !Jf || !oMf || !com) throw std::string("tsidb_rbd_terms: null buffer");
   hipStream_t s = (hipStream_t)stream;
   h->note_stream(s);
-  if (h->dtype == TSIDB_F64)
-    hipLaunchKernelGGL(k_rbd<double>, dim3(h->num_envs), dim3(WAVE), 0, s, (const DevModel<double> *)h->d_model, h->num_envs,
-                       (const double *)q, (const double *)v, (double *)M, (double *)hbias, (double *)Jcom, (double *)Jf,
-                       (double *)oMf, (double *)com);
-  else
-    hipLaunchKernelGGL(k_rbd<float>, dim3(h->num_envs), dim3(WAVE), 0, s, (const DevModel<float> *)h->d_model, h->num_envs,
-                       (const float *)q, (const float *)v, (float *)M, (float *)hbias, (float *)Jcom, (float *)Jf,
-                       (float *)oMf, (float *)com);
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_rbd<T>, dim3(h->num_envs), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, (const T *)q,
+                       (const T *)v, (T *)M, (T *)hbias, (T *)Jcom, (T *)Jf, (T *)oMf, (T *)com);
+  });
   HIP_OK(hipGetLastError());
   GUARD_END
 }
@@ -1370,8 +1366,7 @@ int tsidb_dims(int *out9) {
 }
 
 int tsidb_lds_bytes(int dtype, int which) {
-  if (dtype == TSIDB_F64) return which == 0 ? (int)sizeof(TickLds<double>) : (int)sizeof(SimLds<double>);
-  return which == 0 ? (int)sizeof(TickLds<float>) : (int)sizeof(SimLds<float>);
+  return with_dtype(dtype, [&](auto t) { return which == 0 ? (int)sizeof(TickLds<decltype(t)>) : (int)sizeof(SimLds<decltype(t)>); });
 }
 
 } // extern "C"
