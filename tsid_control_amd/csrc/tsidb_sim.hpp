@@ -18,11 +18,8 @@
 namespace tsidb {
 
 constexpr int LDM = 27;
-#ifndef TSIDB_NEWTON_INCR_MAX
-#define TSIDB_NEWTON_INCR_MAX 8
-#endif
-constexpr int NEWTON_INCR_MAX = TSIDB_NEWTON_INCR_MAX; // Newton: at most this many changed rows are applied to the factor as
-                                                       // rank-1 updates; more, and the Hessian is rebuilt (< 0: never incremental)
+constexpr int NEWTON_INCR_MAX = 8; // Newton: at most this many changed rows are applied to the factor as rank-1 updates;
+                                   // more, and the Hessian is rebuilt (< 0: never incremental)
 
 // floor plane n.x = d with its contact frame (mju_makeFrame: t1 from y unless |n_y| >= 0.5, t2 = n x t1)
 template <typename T>
@@ -76,12 +73,8 @@ static_assert(sizeof(SimLds<double>) <= 20480, "k_sim must fit 8 workgroups per 
 // is; in the two-wavefront variant the phases that run on different wavefronts at the same time must not meet at a
 // workgroup barrier, and need none: a wavefront's LDS instructions execute in order, only the compiler has to be told.
 template <int NW> __device__ __forceinline__ void wsync() {
-  if constexpr (NW == 1) TSIDB_SYNC1();
-  else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  if constexpr (NW == 1) __syncthreads();
+  else wave_sync();
 }
 
 __device__ __forceinline__ int sym_idx(int i, int j) { // packed upper index of a symmetric 6x6
@@ -1024,7 +1017,7 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   }
   const T myctrl = (lane < NA && q_tsid) ? q_tsid[m.mj_ctrl_qidx[lane]] : T(0); // joint target of actuator `lane`
   for (int i = lane; i < NV * LDM; i += WAVE) L.M[i] = 0;
-  wg_sync<NW>();
+  __syncthreads();
   const T Oz = L.qpos[2];
 
   // ---- kinematics, velocities, bias accelerations: parent-independent work up front, the depth
@@ -1079,8 +1072,8 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   int bchn[7];
 #pragma unroll
   for (int d = 0; d < 7; d++) bchn[d] = lane < NB ? m.mj_chain[lane][d] : -1;
-  tree_forward<T, NW>(lane, NB, up0, up1, up2, bchn, &L.R[0][0], &L.V[0][0], &L.f[0][0], 6, &L.Yc[0][0], 10, Rb, pb, qd, Sb,
-                  Vb, Ab);
+  tree_forward<T>(lane, NB, up0, up1, up2, bchn, &L.R[0][0], &L.V[0][0], &L.f[0][0], 6, &L.Yc[0][0], 10, Rb, pb, qd, Sb,
+                Vb, Ab);
   if (lane < NB) {
     const int b = lane;
     if (b > 0) {
@@ -1142,7 +1135,7 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
       for (int i = 0; i < 10; i++) L.Yc[lane][i] = Y[i];
     }
   }
-  wg_sync<NW>();
+  __syncthreads();
   const bool w_dyn = NW == 1 || wv == 0, w_col = NW == 1 || wv == NW - 1; // which phases this wavefront runs
   // ---- per dof: bias, mass-matrix column (+ armature), actuation
   T qfs = 0;
@@ -1194,11 +1187,7 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   const T margin = m.contact[10], tie_tol = m.opt[6];
   const T Ow[3] = {L.qpos[0], L.qpos[1], L.qpos[2]};
   const T nO = dot3(fl.n, Ow) - fl.d; // signed distance of the base origin O to the floor plane
-#ifdef TSIDB_NO_TERR
-  const bool has_terr = false;
-#else
   const bool has_terr = terr_g != nullptr;
-#endif
   T hmax_all = 0;
   if (has_terr) {
 #pragma unroll
@@ -1311,7 +1300,6 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   nfl = ncon; // contacts [0, nfl) are floor contacts (shared frame), [nfl, ncon) robot<->robot ones
   // ---- collision: robot<->robot convex-hull pairs (robot.xml:13-15 after the excludes of :18-52 and the
   //      parent-child filter): mid phase one lane per pair, narrow phase (MPR) one pair at a time on the wave
-#ifndef TSIDB_NO_HH
   if (m.params[P_SELF_COLLISION] != 0) {
     // bounding spheres of all bodies in the world (lane = body)
     if (lane < NG) {
@@ -1375,7 +1363,6 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     if (over) cfail |= 8;
     if (over64) cfail |= 32;
   }
-#endif
   } // (w_col)
   if constexpr (NW > 1) { // join: the collision wavefront hands over its counts and is done
     if (wv == NW - 1 && lane == 0) { L.xch[0] = ncon; L.xch[1] = nfl; L.xch[2] = hh_cross ? 1 : 0; L.xch[3] = cfail; }

@@ -198,7 +198,7 @@ __device__ __forceinline__ void rbd_terms(const DevModel<T> &m, TickLds<T> &L, i
       for (int i = 0; i < 10; i++) K.Yc[lane][i] = Y[i];
     }
   }
-  TSIDB_SYNC1();
+  __syncthreads();
   TSIDB_LAP(30);
   // ---- per dof: bias, F = Yc S, mass-matrix entries, CoM Jacobian column
   const T invm = T(1) / m.mass;
@@ -278,7 +278,7 @@ __device__ __forceinline__ void rbd_terms(const DevModel<T> &m, TickLds<T> &L, i
     L.dLam[1] = f0[4] - (cz * f0[0] - cx * f0[2]);
     L.dLam[2] = f0[5] - (cx * f0[1] - cy * f0[0]);
   }
-  TSIDB_SYNC1();
+  __syncthreads();
   // ---- frame Jacobian columns (LOCAL) and CoM velocity
   if (lane < NV) {
     const int k = lane, jk = k < 6 ? 0 : k - 5;
@@ -314,7 +314,7 @@ __device__ __forceinline__ void rbd_terms(const DevModel<T> &m, TickLds<T> &L, i
       }
     }
   }
-  TSIDB_SYNC1();
+  __syncthreads();
 }
 
 // --------------------------------------------------------------------------- task right-hand sides
@@ -497,7 +497,7 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
   T ul = 0; // lane k < na: multiplier of the k-th active inequality; lane na: the candidate's
   T R_norm = c.R_norm;
   for (int r = lane; r < c.nin; r += WAVE) S.cstate[r] = 0;
-  TSIDB_SYNC1();
+  __syncthreads();
 
   int iter = 0, status = -1;
   TSIDB_LAP_ZERO(10); TSIDB_LAP_ZERO(11); TSIDB_LAP_ZERO(12); TSIDB_LAP_ZERO(13); TSIDB_LAP_ZERO(14);
@@ -506,11 +506,11 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
     // ---------------- l1: new outer iteration
     iter++;
     if (iter >= max_iter) { status = 3; break; }
-    TSIDB_SYNC1();
+    __syncthreads();
     if (lane < n) L.x[lane] = xl;
-    TSIDB_SYNC1();
+    __syncthreads();
     act_partials(L, n, lane);
-    TSIDB_SYNC1();
+    __syncthreads();
     T psi = 0;
 #pragma unroll
     for (int rr = 0; rr < 3; rr++) {
@@ -526,7 +526,7 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
     if (fabs(psi) <= T(c.nin) * T(2.220446049250313e-16) * c1 * c2 * T(100)) { status = 0; break; }
     const T xold = xl, uold = ul;
     if (lane < na) S.Aold[lane] = S.A[lane];
-    TSIDB_SYNC1();
+    __syncthreads();
     TSIDB_LAP(10);
 
     bool outer_done = false;
@@ -652,14 +652,14 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
             if (na >= NAS - 2 || ad <= Eps<T>::v * R_norm) {
               // numerically dependent on the active set: exclude it for this outer iteration and
               // fall back to the state saved at l1 (eiquadprog's recovery path)
-              TSIDB_SYNC1();
+              __syncthreads();
               if (lane == 0) S.cstate[ip] |= 2;
               for (int r = lane; r < c.nin; r += WAVE) S.cstate[r] &= 2;
-              TSIDB_SYNC1();
+              __syncthreads();
               if (lane < na) { S.A[lane] = S.Aold[lane]; S.cstate[S.Aold[lane]] |= 1; }
               ul = lane < na ? uold : T(0);
               xl = xold;
-              TSIDB_SYNC1();
+              __syncthreads();
               break; // back to l2
             }
             if (ad > R_norm) R_norm = ad;
@@ -667,7 +667,7 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
             if (lane == 0) { S.Ra[rcol(na) + na] = dnew; S.Rinv[na] = T(1) / dnew; S.slot[na] = cstar; S.cstate[ip] |= 1; }
             freem &= ~(1ull << cstar);
             na++;
-            TSIDB_SYNC1();
+            __syncthreads();
             TSIDB_LAP(14);
             outer_done = true;
             break; // back to l1
@@ -676,7 +676,7 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
         }
         if (drop) {
           // ---------------- remove active constraint l, then recompute the direction for ip
-          TSIDB_SYNC1();
+          __syncthreads();
           if (lane == 0) S.cstate[l] &= ~1;
           const int qq = wave_min_int((lane < na && S.A[lane] == l) ? lane : 9999);
           for (int j = qq; j < na - 1; j++) { // Givens sweep restoring the triangular factor
@@ -688,7 +688,7 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
             T diag = h;
             if (cc < 0) { cc = -cc; ss = -ss; diag = -h; }
             const T xny = ss / (T(1) + cc);
-            TSIDB_SYNC1();
+            __syncthreads();
             for (int k = co + 1 + lane; k < na; k += WAVE) {
               const T a1 = S.Ra[rcol(k) + j], a2 = S.Ra[rcol(k) + j + 1];
               const T n1 = a1 * cc + a2 * ss;
@@ -701,19 +701,19 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
             const T n1 = ta * cc + tb * ss, n2 = xny * (n1 + ta) - tb;
 #pragma unroll
             for (int jj = PP; jj < NN; jj++) jr[jj] = (jj == sa) ? n1 : ((jj == sb) ? n2 : jr[jj]);
-            TSIDB_SYNC1();
+            __syncthreads();
           }
           for (int k = qq + 1; k < na; k++) { // shift the packed columns left
             const T val = lane < k ? S.Ra[rcol(k) + lane] : T(0);
-            TSIDB_SYNC1();
+            __syncthreads();
             if (lane < k) S.Ra[rcol(k - 1) + lane] = val;
-            TSIDB_SYNC1();
+            __syncthreads();
           }
           if (lane >= qq && lane < na - 1) S.Rinv[lane] = T(1) / S.Ra[rcol(lane) + lane];
           int Av = 0;
           if (lane >= qq && lane < na) Av = S.A[lane + 1];
           const T unext = __shfl_down(ul, 1, WAVE);
-          TSIDB_SYNC1();
+          __syncthreads();
           if (lane >= qq && lane < na) S.A[lane] = Av;
           if (lane >= qq && lane <= na) ul = unext;
           const int freed = S.slot[na - 1];
@@ -721,21 +721,21 @@ __device__ __forceinline__ int qp_active_regs(const DevModel<T> &m, TickLds<T> &
           na--;
           if (lane == na + 1) ul = 0;
           // refresh s[ip] at the new point
-          TSIDB_SYNC1();
+          __syncthreads();
           if (lane < n) L.x[lane] = xl;
-          TSIDB_SYNC1();
-          if (okind == 2) { act_partials(L, n, lane); TSIDB_SYNC1(); }
+          __syncthreads();
+          if (okind == 2) { act_partials(L, n, lane); __syncthreads(); }
 #pragma unroll
           for (int rr = 0; rr < 3; rr++)
             if (rr == oround && lane == owner) S.s[ip] = row_eval(rd[rr], L);
-          TSIDB_SYNC1();
+          __syncthreads();
         }
       }
     }
   }
-  TSIDB_SYNC1();
+  __syncthreads();
   if (lane < n) L.x[lane] = xl;
-  TSIDB_SYNC1();
+  __syncthreads();
   c.iq = p + na;
   iter_out = iter;
   return status;
@@ -871,7 +871,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
       // rows NV.. of B (non-zero for the base-dynamics columns only): fc[col][e] = sum_{b <= e} Jf0[b][e] Dyn[col][NV + b],
       // 6 x 12 NS dot products spread over the wavefront and handed over through LDS (the Jacobian scratch is dead now;
       // six lanes doing it alone read the 78 constants of Jf0 as wave-uniform scalars: 156 SGPRs at once)
-      TSIDB_SYNC1();
+      __syncthreads();
       for (int idx = lane; idx < 6 * 12 * NS; idx += WAVE) {
         const int cl = idx / (12 * NS), rem = idx % (12 * NS), s2 = rem / 12, e = rem % 12;
         T sacc = 0;
@@ -883,7 +883,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
         }
         fcl[idx] = sacc;
       }
-      TSIDB_SYNC1();
+      __syncthreads();
       if constexpr (COP) {
         const T w_cop = m.params[P_W_COP];
         if (w_cop != 0 && cop_ref) {
@@ -908,9 +908,9 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
             A0 = R[j] * x1[0] + R[3 + j] * x1[1] + R[6 + j] * x1[2]; // component j of R^T (t x d)
             A1 = R[j] * x2[0] + R[3 + j] * x2[1] + R[6 + j] * x2[2];
           }
-          TSIDB_SYNC1();
+          __syncthreads();
           if (isf) { L.x[fcol] = A0; L.x[24 + fcol] = A1; }
-          TSIDB_SYNC1();
+          __syncthreads();
           T t0 = 0, t1 = 0; // this lane's column of A J0 (J0 upper triangular within each foot's block)
           if (isf) {
             const int sl = fcol / 12, cb = fcol % 12;
@@ -925,9 +925,9 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
           const T bq = t1 - be1 * a12 * t0;
           const T al2 = wave_sum(bq * bq);
           const T be2 = al2 > tiny ? (1 - T(1) / sqrt(1 + w_cop * al2)) / al2 : T(0);
-          TSIDB_SYNC1();
+          __syncthreads();
           if (isf) { L.x[fcol] = t0; L.x[24 + fcol] = bq; }
-          TSIDB_SYNC1();
+          __syncthreads();
           if (isf) { // row of J: j0 (I - b1 a1 a1^T)(I - b2 b b^T)
             T s1 = 0, s2 = 0;
 #pragma unroll
@@ -956,7 +956,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
             for (int cc = 0; cc < 12 * NS; cc++) fcl[lane * 12 * NS + cc] = fc[cc];
           }
           c1 += w_cop * wave_sum(A0 * A0 + A1 * A1); // trace of the Hessian (tolerance scale only)
-          TSIDB_SYNC1();
+          __syncthreads();
         }
       }
       // rows of the force block go to their group's lane
@@ -967,14 +967,14 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
           if (row >= NV && row < NN) bs[j] = fcl[(col - NC) * 12 * NS + row - NV];
         }
       }
-      TSIDB_SYNC1(); // (the sweep below writes the row buffer)
+      __syncthreads(); // (the sweep below writes the row buffer)
     }
     TSIDB_STAMP(5);
     bool fast_done = false, swept = false; // swept: the fast attempt got as far as its sweep and found a violated inequality
     if constexpr (FASTEQ) {
       if (spd && fast_eq) {
         // S = B^T B, one pair (c <= d) per lane and round: 26 dv rows from LDS, the force rows for base-dynamics pairs
-        TSIDB_SYNC1();
+        __syncthreads();
         for (int pidx = lane; pidx < NPAIR; pidx += WAVE) {
           int d = (int)((sqrtf((float)(8 * pidx + 1)) - 1.0f) * 0.5f); // (pair index -> (c, d), d >= c; float is exact enough
           d += (d + 1) * (d + 2) / 2 <= pidx ? 1 : 0;                   //  for < 200 pairs, one correction step either way)
@@ -995,7 +995,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
           }
           Sl[pidx] = s0 + s1;
         }
-        TSIDB_SYNC1();
+        __syncthreads();
         TSIDB_STAMP(10);
         // lane r < PP: row r of S in registers; Cholesky S = Ls Ls^T; then forward substitutions that share Ls's broadcasts:
         // u = Ls^-1 c and column `lane` of Ls^-1 (as for J0 above), so that lambda = Ls^-T u needs no transposed access
@@ -1077,7 +1077,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
           TSIDB_STAMP(12);
           // z = -B lambda (lane r = row r of B), x = x0 + J0 z
           if (lane < PP) L.x[lane] = lam;
-          TSIDB_SYNC1();
+          __syncthreads();
           T z = 0;
           if (lane < NV) {
 #pragma unroll
@@ -1101,9 +1101,9 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
             }
             xf += xf1;
           }
-          TSIDB_SYNC1();
+          __syncthreads();
           if (lane < n) L.x[lane] = xf;
-          TSIDB_SYNC1();
+          __syncthreads();
           TSIDB_STAMP(6);
           // feasibility sweep at the equality-constrained optimum
           c.iq = p;
@@ -1111,7 +1111,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
 #pragma unroll
           for (int rr = 0; rr < 3; rr++) rdf[rr] = row_desc(m, L, c, lane + WAVE * rr);
           act_partials(L, n, lane);
-          TSIDB_SYNC1();
+          __syncthreads();
           T psi = 0;
 #pragma unroll
           for (int rr = 0; rr < 3; rr++)
@@ -1126,7 +1126,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
             qp_iters = 1;
           }
           swept = true;
-          TSIDB_SYNC1();
+          __syncthreads();
         }
       }
     }
@@ -1240,7 +1240,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
     // ---- first feasibility sweep straight from registers' result; J / R go to LDS only if the
     //      active-set iterations are actually needed
     if (lane < n) L.x[lane] = xeq;
-    TSIDB_SYNC1();
+    __syncthreads();
     c.iq = p;
     c.R_norm = R_norm;
     int iters = 1;
@@ -1252,7 +1252,7 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
     for (int rr = 0; rr < 3; rr++) rdesc[rr] = row_desc(m, L, c, lane + WAVE * rr);
     if (status < 0 && !swept) { // (after a failed fast attempt the answer is known: the active-set loop's own first sweep follows)
       act_partials(L, n, lane);
-      TSIDB_SYNC1();
+      __syncthreads();
       T psi = 0;
 #pragma unroll
       for (int rr = 0; rr < 3; rr++)
@@ -1304,11 +1304,11 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
     if (lane < NV) L.vs[lane] = v[lane];
   }
   if (lane >= 32 && lane < 34) L.act[lane - 32] = cact[lane - 32] != 0; // (the caller dispatched on act[0] + act[1] == NS)
-  TSIDB_SYNC1();
+  __syncthreads();
   rbd_terms(m, L, lane);
   if (m.params[P_TSID_ARMATURE] != 0) { // closed-loop knob: rotor inertia of the actuated joints in TSID's model
     if (lane >= 6 && lane < NV) L.Dyn[lane * LDD + lane] += m.params[P_TSID_ARMATURE];
-    TSIDB_SYNC1();
+    __syncthreads();
   }
   TSIDB_STAMP(1);
 
@@ -1343,7 +1343,7 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
     for (int i = 0; i < 6; i++) a += m.Tgen[i][e] * L.k.Jf[(6 * f + i) * LDF + r];
     L.Dyn[r * LDD + NV + cc] = -a;
   }
-  TSIDB_SYNC1(); // kinematics scratch is dead from here on
+  __syncthreads(); // kinematics scratch is dead from here on
   TSIDB_STAMP(2);
 
   // ---- Hessian block of dv in registers: lane i owns row i
@@ -1497,7 +1497,7 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
     status_out[0] = status;
     if (info) { info[0] = iters; info[1] = c.iq; }
   }
-  TSIDB_SYNC1();
+  __syncthreads();
   // ---- observations from this tick's data (main.py:132-142 reads data() before recomputing)
   if (obs) {
     // contact wrenches in the sole frames: component i of foot fo on lane 6 fo + i (twelve 12-term sums side by side
@@ -1540,7 +1540,7 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
       L.vs[lane] = vv + dt * dd;
       L.as.Ra[lane] = vm;
     }
-    TSIDB_SYNC1();
+    __syncthreads();
     if (lane >= 6 && lane < NV) L.qs[lane + 1] += vm;
     if (lane == 0) {
       const T *vl = &L.as.Ra[0], *w = &L.as.Ra[3];
@@ -1573,7 +1573,7 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
 #pragma unroll
       for (int i = 0; i < 4; i++) L.qs[3 + i] = r[i] * nn;
     }
-    TSIDB_SYNC1();
+    __syncthreads();
     if (lane < NQ) q[lane] = L.qs[lane];
     if (lane < NV) v[lane] = L.vs[lane];
   }

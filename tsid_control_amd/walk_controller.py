@@ -91,12 +91,8 @@ class WalkController:
         if sw:
             _lib.check(L, self._h, L.tsidb_set_option(self._h, 1, sw), "tsidb_set_option(sim_waves)")
         fe = int(getattr(conf, "qp_fast_equalities", -1))   # -1 = the library's default (on)
-        if os.environ.get("TSIDB_QP_FAST_EQ"):    # diagnostic override (A/B runs)
-            fe = int(os.environ["TSIDB_QP_FAST_EQ"])
         if fe >= 0:
             _lib.check(L, self._h, L.tsidb_set_option(self._h, 5, fe), "tsidb_set_option(qp_fast_eq)")
-        if os.environ.get("TSIDB_LDS_PAD"):       # diagnostic (occupancy measurements): unused LDS per workgroup
-            _lib.check(L, self._h, L.tsidb_set_option(self._h, 2, int(os.environ["TSIDB_LDS_PAD"])), "tsidb_set_option(lds_pad)")
         self.cop_ref = z(N, 3)   # reference of the CoP force task (legacy/biped.py:79-80; conf.w_cop)
         _lib.check(L, self._h, L.tsidb_set_cop_ref(self._h, _ptr(self.cop_ref)), "tsidb_set_cop_ref")
 
@@ -458,7 +454,7 @@ class WalkController:
     def _ensure_pipe(self):
         """the second stream and the ring of snapshot slots step_pipelined() hands the TSID state to the sim stages through;
         (re)built when missing or too small for the current sim batch"""
-        need = min(16, max(4, 2 * self.sim_batch, int(os.environ.get("TSIDB_RING_SLOTS", "0"))))
+        need = min(16, max(4, 2 * self.sim_batch))
         P = getattr(self, "_pipe", None)
         if P is not None and len(P["q"]) >= need:
             return
@@ -505,7 +501,7 @@ class WalkController:
         a different number of sim steps per launch agrees to rounding only, include/tsidb.h tsidb_sim_batch).  The sim state
         is valid after sync_sim().
         sim_batch = sim steps per launch INSIDE the graph (default: as in eager mode).  A graph ends with a join, so the
-        sim batch still to run after the last tick runs alone; measured (tools/r03_graph.sh, 512 envs): eager 6.64 M
+        sim batch still to run after the last tick runs alone; measured (512 envs): eager 6.64 M
         env-steps/s; 16 steps per graph 5.2 / 5.5 / 5.2 M with 1 / 2 / 8 sim steps per launch, 64 steps per graph 5.8 / 6.0 /
         6.4 M - replaying a graph never beats the eager pipeline here."""
         if getattr(self.conf, "closed_loop", False) or not getattr(self.conf, "sim_enabled", True):
