@@ -129,6 +129,24 @@ int tsidb_set_env_params(tsidb_handle h, const void *env_params, const void *ter
  * wrenches.  Rejected by a library built without the sim stage.  The pointer is remembered, not copied. */
 int tsidb_set_xfrc(tsidb_handle h, void *xfrc);
 
+/* sim-stage readouts of the last sim step (mj_data.contact, mj_contactForce, mj_data.actuator_force); each may be NULL.
+ * con_force [N,32,6], con_frame [N,32,9], con_pos [N,32,4] = world position (3) + dist,
+ * act_force [N,NA], foot_grf [N,2,6] = world force (3) + CoP (3).  Rows >= ncon are zero.
+ * Device buffers in the path's arithmetic type.  Contact c is row c of con_pairs, in the same order.  con_force is
+ * mj_contactForce: normal, tangent 1, tangent 2, torsional (contact dimension 4 only, else 0), 0, 0 in the contact frame, the
+ * force geom1 exerts on geom2, decoded from the pyramid rows at the solver's final acceleration.  The frame's rows are the
+ * normal, pointing from geom1 to geom2, and the two tangents (contact.frame; mju_makeFrame).  The floor is geom1 of every
+ * floor contact, so the normal points up out of the floor and the force is the floor's push on the robot.  con_pos is
+ * contact.pos and contact.dist, taken where the step's collision ran (its start).  act_force is actuator_force in the MJCF
+ * actuator order (the ctrl order): the clamped position-servo force, or the motor torque in the closed loop.  foot_grf holds
+ * per sole (LF, RF, TSID's contact order) the floor contacts on that sole's sim body summed in the world frame, then their
+ * centre of pressure (normal-force-weighted mean of the contact positions; all zero while the sole carries no normal force).
+ * Every sim step writes them (a tsidb_sim_batch launch or a tsidb_step with substeps leaves the last step's values); a
+ * skipped step (info flag bit 4) zeroes the env's rows.  tsidb_reset / tsidb_reset_done do not touch them, as they leave
+ * ncon and con_pairs alone.  The pointers are remembered, not copied; all NULL (the default) unregisters.  Rejected by a
+ * library built without the sim stage. */
+int tsidb_set_sim_readouts(tsidb_handle h, void *con_force, void *con_frame, void *con_pos, void *act_force, void *foot_grf);
+
 /* reset: WalkController.py:22-26,72-79 (standing state, soles onto z = 0), the references of
  * :81,122,151-152,164-165, and main.py:57-64 (mj_data.qpos = q).  env_ids (device, int32) selects
  * envs; NULL = all (a non-NULL list with n_ids = 0 resets nothing).  Writes state AND the reference buffers

@@ -226,10 +226,12 @@ template <typename T> struct SimRing { const T *q, *v; unsigned long long slots;
 // open-loop steps of 3072 envs and more (profiles/r04_f32_wpe3.txt, r04_f32_wpe3_sizes.txt).  Same arithmetic: bit-identical.
 // XF = the step reads the external wrenches xfrc (tsidb_set_xfrc); launch_sim selects it only while a buffer is registered,
 // so the kernels without it are unchanged (xfrc is then not read).
-template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false>
+// RO = the step writes the readouts ro (tsidb_set_sim_readouts; the last step of a batch leaves its values); likewise selected
+// only while a buffer is registered (ro, the last argument, is then not read).
+template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false, bool RO = false>
 __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))) void k_sim(const DevModel<T> *__restrict__ mp, int n, int B, SimRing<T> ring, T *qpos, T *qvel,
                                               T *qacc_ws, const T *env_params, const T *terrain, const T *xfrc, const T *motor_tau, T *qacc, int *ncon,
-                                              int *con, int *info) {
+                                              int *con, int *info, SimOut<T> ro) {
   __shared__ SimLds<T> L;
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   if ((int)blockIdx.x >= n) return;
@@ -244,6 +246,16 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       asm volatile("" : "+s"(mq), "+s"(qpos), "+s"(qvel), "+s"(qacc_ws), "+s"(env_params), "+s"(terrain), "+s"(motor_tau) : : "memory");
       asm volatile("" : "+s"(qacc), "+s"(ncon), "+s"(con), "+s"(info) : : "memory");
       if constexpr (XF) asm volatile("" : "+s"(xfrc) : : "memory");
+      if constexpr (RO) asm volatile("" : "+s"(ro.con_force), "+s"(ro.con_frame), "+s"(ro.con_pos), "+s"(ro.act_force), "+s"(ro.foot_grf) : : "memory");
+    }
+    SimOut<T> roe{}; // (the env's rows)
+    if constexpr (RO) {
+      roe.con_force = ro.con_force ? ro.con_force + E * MAXCON * 6 : nullptr;
+      roe.con_frame = ro.con_frame ? ro.con_frame + E * MAXCON * 9 : nullptr;
+      roe.con_pos = ro.con_pos ? ro.con_pos + E * MAXCON * 4 : nullptr;
+      roe.act_force = ro.act_force ? ro.act_force + E * NA : nullptr;
+      roe.foot_grf = ro.foot_grf ? ro.foot_grf + E * 12 : nullptr;
+      roe.foot_body[0] = ro.foot_body[0]; roe.foot_body[1] = ro.foot_body[1];
     }
     const size_t slot = (size_t)((ring.slots >> (4 * b)) & 15ull);
     const T *q_tsid = ring.q ? ring.q + slot * (size_t)n * NQ : nullptr, *v_tsid = ring.v ? ring.v + slot * (size_t)n * NV : nullptr;
@@ -265,13 +277,14 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
           if (ncon) ncon[e] = 0;
         }
         if (con && lane < MAXCON) con[E * MAXCON + lane] = -1;
+        if constexpr (RO) sim_readouts_zero(roe, lane);
       }
     }
     if (!skip)
-      sim_step_env<T, NW, XF>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+      sim_step_env<T, NW, XF, RO>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
                           env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
                           motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
-                          info ? info + E * 4 : nullptr);
+                          info ? info + E * 4 : nullptr, roe);
     if constexpr (MULTI) __syncthreads(); // both wavefronts; the step's state is written before the next step reads it
   }
 }
@@ -675,6 +688,9 @@ struct tsidb_ctx {
   const uint8_t *contact_active = nullptr;
   const void *env_params = nullptr, *terrain = nullptr, *cop_ref = nullptr, *posture_bias = nullptr;
   void *xfrc = nullptr; // [N, NB, 6] external body wrenches (tsidb_set_xfrc); k_reset zeroes the reset envs' rows
+  void *ro[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // sim readouts (tsidb_set_sim_readouts): con_force, con_frame, con_pos,
+                                                                // act_force, foot_grf
+  bool has_readouts() const { return ro[0] || ro[1] || ro[2] || ro[3] || ro[4]; }
   int foot_body[2] = {-1, -1}; // sim bodies that carry the left / right sole frame
   unsigned long long foot_geoms[2] = {0, 0}; // bit g: collision geom g is on that body
   std::string err;
@@ -945,6 +961,17 @@ extern "C" int tsidb_set_xfrc(tsidb_handle h, void *xfrc) {
   return 0;
 }
 
+extern "C" int tsidb_set_sim_readouts(tsidb_handle h, void *con_force, void *con_frame, void *con_pos, void *act_force, void *foot_grf) {
+  if (!h) return -1;
+  void *const p[5] = {con_force, con_frame, con_pos, act_force, foot_grf};
+  if (!TOPO_HAS_SIM && (con_force || con_frame || con_pos || act_force || foot_grf)) {
+    h->err = "tsidb_set_sim_readouts: this library was built without the sim stage";
+    return 1;
+  }
+  for (int i = 0; i < 5; i++) h->ro[i] = p[i]; // all NULL = no readouts
+  return 0;
+}
+
 static void need_refs(tsidb_ctx *h) {
   if (!h->com_ref) throw std::string("reference buffers not registered (call tsidb_set_refs first)");
   if (h->params[P_W_COP] != 0.0 && !h->cop_ref) throw std::string("w_cop != 0 needs a CoP reference (tsidb_set_cop_ref)");
@@ -999,18 +1026,20 @@ static void launch_tick(tsidb_ctx *h, void *q, void *v, void *tau, void *dv, voi
 // take every wave slot of the GPU (2 per SIMD) for the whole batch, and the tick launched beside it "runs" 338-526 us
 // instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
 // neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
-// (a registered xfrc buffer selects the XF = true instantiations; the float32 build for three wavefronts per SIMD has none:
-//  the default build, bit-identical to it, runs instead; it is also never picked with lds_pad != 0)
+// (a registered xfrc buffer selects the XF = true instantiations, registered readouts the RO = true ones; the float32 build for
+//  three wavefronts per SIMD has neither: the default build, bit-identical to it, runs instead; it is also never picked with
+//  lds_pad != 0)
 template <typename T>
 static auto sim_kernel(const tsidb_ctx *h, int B, bool motor_tau) {
   if constexpr (sizeof(T) == 4)
-    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc) return k_sim<float, 1, false, 3, false>;
-  const decltype(&k_sim<T, 1, false>) pick[2][2][2] = { // [sim_waves == 2][B > 1][xfrc registered]
-      {{k_sim<T, 1, false, TSIDB_WPE, false>, k_sim<T, 1, false, TSIDB_WPE, true>},
-       {k_sim<T, 1, true, TSIDB_WPE, false>, k_sim<T, 1, true, TSIDB_WPE, true>}},
-      {{k_sim<T, 2, false, TSIDB_WPE, false>, k_sim<T, 2, false, TSIDB_WPE, true>},
-       {k_sim<T, 2, true, TSIDB_WPE, false>, k_sim<T, 2, true, TSIDB_WPE, true>}}};
-  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr];
+    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc && !h->has_readouts())
+      return k_sim<float, 1, false, 3, false, false>;
+#define TSIDB_SIM_RO(NW, MULTI, XF) {k_sim<T, NW, MULTI, TSIDB_WPE, XF, false>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true>}
+  const decltype(&k_sim<T, 1, false>) pick[2][2][2][2] = { // [sim_waves == 2][B > 1][xfrc registered][readouts registered]
+      {{TSIDB_SIM_RO(1, false, false), TSIDB_SIM_RO(1, false, true)}, {TSIDB_SIM_RO(1, true, false), TSIDB_SIM_RO(1, true, true)}},
+      {{TSIDB_SIM_RO(2, false, false), TSIDB_SIM_RO(2, false, true)}, {TSIDB_SIM_RO(2, true, false), TSIDB_SIM_RO(2, true, true)}}};
+#undef TSIDB_SIM_RO
+  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr][h->has_readouts()];
 }
 
 // B sim steps in one launch, step b driven by slot slots[b] of the [K, N, NQ] / [K, N, NV] rings q_ring / v_ring (slot 0 if NULL)
@@ -1031,7 +1060,8 @@ static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ri
       hipLaunchKernelGGL(sim_kernel<T>(h, B, motor_tau != nullptr), dim3(h->num_envs), dim3(WAVE * h->sim_waves), h->lds_pad, s,
                          (const DevModel<T> *)h->d_model, h->num_envs, B, SimRing<T>{(const T *)q_ring, (const T *)v_ring, slot_bits},
                          (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc,
-                         (const T *)motor_tau, (T *)qacc, ncon, con, info);
+                         (const T *)motor_tau, (T *)qacc, ncon, con, info,
+                         SimOut<T>{(T *)h->ro[0], (T *)h->ro[1], (T *)h->ro[2], (T *)h->ro[3], (T *)h->ro[4], {h->foot_body[0], h->foot_body[1]}});
   });
   HIP_OK(hipGetLastError());
 }

@@ -959,12 +959,103 @@ template <typename T> __device__ __forceinline__ void sub_xfrc(const T *w, const
   for (int i = 0; i < 3; i++) { fb[i] -= F[i]; fb[3 + i] -= w[3 + i] + cxf[i]; }
 }
 
+// Sim-stage readouts (tsidb_set_sim_readouts): mj_data.contact, mj_contactForce and mj_data.actuator_force of the step.  The
+// env's rows of each buffer (NULL = not registered): con_force [MAXCON][6], con_frame [MAXCON][9], con_pos [MAXCON][4],
+// act_force [NA], foot_grf [2][6]; foot_body = the sim bodies of TSID's LF / RF soles.
+template <typename T> struct SimOut {
+  T *con_force, *con_frame, *con_pos, *act_force, *foot_grf;
+  int foot_body[2];
+};
+
+// Epilogue of a step with readouts, lane = contact, at the solver's final qacc (rs.cjar).  Per contact mj_contactForce: the
+// pyramid row forces f_i = D max(0, -jar_i) (rows_eval's active rows) decoded as mju_decodePyramid does - normal sum f_i,
+// tangent k mu (f_2k - f_2k+1), torsional mu_t (f_4 - f_5) - in the contact frame (rows normal, t1, t2 as contact.frame), the
+// force geom1 exerts on geom2 (the floor is geom1).  Position in the world (cr is relative to O) and distance.  Per foot: the
+// floor contacts on its body summed in the world frame, and their centre of pressure (normal-force weighted; 0 without load).
+template <typename T>
+__device__ __forceinline__ void sim_readouts(const DevModel<T> &m, const SimLds<T> &L, int lane, int nfl, int ncon, T mu, const RowState<T> &rs,
+                                             const SimOut<T> &ro) {
+  T fc[4] = {0, 0, 0, 0}, n[3] = {0, 0, 0}, t1[3] = {0, 0, 0}, t2[3] = {0, 0, 0}, pw[3] = {0, 0, 0}, dist = 0;
+  const bool live = lane < ncon;
+  if (live) {
+    T fr[NROWC];
+#pragma unroll
+    for (int i = 0; i < NROWC; i++) { fr[i] = rs.cjar[i] < 0 ? -rs.cD * rs.cjar[i] : T(0); fc[0] += fr[i]; }
+    fc[1] = mu * (fr[0] - fr[1]);
+    fc[2] = mu * (fr[2] - fr[3]);
+    if constexpr (CONDIM > 3) fc[3] = m.contact[9] * (fr[4] - fr[5]);
+    contact_frame(L, lane, nfl, n, t1, t2);
+#pragma unroll
+    for (int i = 0; i < 3; i++) pw[i] = L.cr[lane][i] + L.qpos[i];
+    dist = L.cdist[lane];
+  }
+  if (lane < MAXCON) { // rows >= ncon are zero
+    if (ro.con_force) {
+      T *o = ro.con_force + 6 * lane;
+#pragma unroll
+      for (int i = 0; i < 4; i++) o[i] = fc[i];
+      o[4] = 0; o[5] = 0;
+    }
+    if (ro.con_frame) {
+      T *o = ro.con_frame + 9 * lane;
+#pragma unroll
+      for (int i = 0; i < 3; i++) { o[i] = n[i]; o[3 + i] = t1[i]; o[6 + i] = t2[i]; }
+    }
+    if (ro.con_pos) {
+      T *o = ro.con_pos + 4 * lane;
+#pragma unroll
+      for (int i = 0; i < 3; i++) o[i] = pw[i];
+      o[3] = dist;
+    }
+  }
+  if (ro.foot_grf) {
+    const int b = live && lane < nfl ? L.cbody[lane] : -1;
+    T fw[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) fw[i] = fc[0] * n[i] + fc[1] * t1[i] + fc[2] * t2[i];
+    // per sole: force (3), normal-force-weighted position (3), normal force - fourteen wave sums, three at a time (wave_sum3:
+    // the DPP steps interleaved, no hazard wait per step)
+    T s[15];
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      const bool on = b >= 0 && b == ro.foot_body[f];
+#pragma unroll
+      for (int i = 0; i < 3; i++) { s[7 * f + i] = on ? fw[i] : T(0); s[7 * f + 3 + i] = on ? fc[0] * pw[i] : T(0); }
+      s[7 * f + 6] = on ? fc[0] : T(0);
+    }
+    s[14] = 0;
+#pragma unroll
+    for (int k = 0; k < 15; k += 3) wave_sum3(s[k], s[k + 1], s[k + 2]);
+    if (lane < 12) {
+      const int f = lane / 6, i = lane - 6 * f;
+      T v = s[0];
+#pragma unroll
+      for (int k = 1; k < 14; k++) v = 7 * f + i == k ? s[k] : v;
+      const T w = f == 0 ? s[6] : s[13];
+      if (i >= 3) v = w > 0 ? v / w : T(0);
+      ro.foot_grf[lane] = v;
+    }
+  }
+}
+
+// a skipped step (k_sim: non-finite input or diverged state) zeroes the env's readout rows, as it sets ncon = 0
+template <typename T> __device__ __forceinline__ void sim_readouts_zero(const SimOut<T> &ro, int lane) {
+  for (int i = lane; i < MAXCON * 9; i += WAVE) {
+    if (ro.con_force && i < MAXCON * 6) ro.con_force[i] = 0;
+    if (ro.con_frame) ro.con_frame[i] = 0;
+    if (ro.con_pos && i < MAXCON * 4) ro.con_pos[i] = 0;
+  }
+  if (ro.act_force && lane < NA) ro.act_force[lane] = 0;
+  if (ro.foot_grf && lane < 12) ro.foot_grf[lane] = 0;
+}
+
 // XF: the kernel reads external wrenches (xfrc, the env's [NB, 6] rows; tsidb_set_xfrc).  A template parameter rather than a
 // runtime NULL test: the test alone cost the multi-step and the three-wavefront float32 kernels VGPR spills.
-template <typename T, int NW, bool XF>
+// RO: the step writes the readouts of `ro` (tsidb_set_sim_readouts), likewise a template parameter.
+template <typename T, int NW, bool XF, bool RO>
 __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
-                             int *con_out, int *info) {
+                             int *con_out, int *info, const SimOut<T> &ro) {
   // per-env randomisation (BASELINE config 5), NULL = nominal: mass scale, contact friction, floor plane
   const T mscale = envp ? envp[0] : T(1);
   Floor<T> &fl = L.fl;
@@ -1173,7 +1264,13 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     const T cc = myctrl < m.act_range[lane][0] ? m.act_range[lane][0] : (myctrl > m.act_range[lane][1] ? m.act_range[lane][1] : myctrl);
     T servo = m.mj_act_kp[lane] * (cc - L.qpos[d + 1]) - m.mj_act_kv[lane] * L.qvel[d];
     servo = servo < m.act_range[lane][2] ? m.act_range[lane][2] : (servo > m.act_range[lane][3] ? m.act_range[lane][3] : servo);
-    L.xv[d] = motor_tau ? motor_tau[m.mj_ctrl_qidx[lane] - 7] : servo;
+    if constexpr (RO) { // (the readout is stored here, where it is made: nothing of it stays live across the step)
+      const T af = motor_tau ? motor_tau[m.mj_ctrl_qidx[lane] - 7] : servo;
+      L.xv[d] = af;
+      if (ro.act_force) ro.act_force[lane] = af;
+    } else {
+      L.xv[d] = motor_tau ? motor_tau[m.mj_ctrl_qidx[lane] - 7] : servo;
+    }
   } else if (lane >= 32 && lane < 38) L.xv[lane - 32] = 0;
   wsync<NW>();
   if (lane < NV) qfs += L.xv[lane];
@@ -1843,6 +1940,8 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     }
     solver_iter = iter;
   }
+  // readouts: here, before the damped-Euler solve, so that the row state is dead across it; L.qpos is still the step's start
+  if constexpr (RO) sim_readouts<T>(m, L, lane, nfl, ncon, mu, rs, ro);
   wsync<NW>();
   TSIDB_STAMP(21);
   // ---- semi-implicit Euler, write back

@@ -84,6 +84,8 @@ class WalkController:
         self.env_params = None
         self.terrain = None
         self.xfrc = None   # external body wrenches [N, NB, 6] (set_xfrc / apply_push); None = none registered
+        self._readouts = None   # sim-stage readout buffers (enable_sim_readouts); None = none registered
+        self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
         rc = L.tsidb_set_refs(self._h, _ptr(self.com_ref), _ptr(self.posture_ref), _ptr(self.foot_ref),
                               _ptr(self.contact_ref), _ptr(self.contact_active), _ptr(self.cop_frames))
         _lib.check(L, self._h, rc, "tsidb_set_refs")
@@ -232,6 +234,76 @@ class WalkController:
             return
         self.xfrc[self._xfrc_rows(env_ids)] = 0
 
+    # ------------------------------------------------------------------ sim-stage readouts (contacts, forces)
+    def enable_sim_readouts(self, con_force=None, con_frame=None, con_pos=None, actuator_force=None, foot_grf=None):
+        """Register the sim stage's readouts (include/tsidb.h tsidb_set_sim_readouts): what a MuJoCo caller reads after
+        mj_step as mj_data.contact, mj_contactForce and mj_data.actuator_force.  Every sim step of step(), sim_step(),
+        step_pipelined() and capture_steps() then writes them; a pipelined caller reads them after sync_sim(), like qpos.
+        Each argument is a tensor to use in place (self.dtype, on self.device, contiguous) or None to allocate one:
+        con_force [N, 32, 6], con_frame [N, 32, 9], con_pos [N, 32, 4], actuator_force [N, NA], foot_grf [N, 2, 6].
+        Exposed as self.con_force (normal, tangent 1, tangent 2, torsional, 0, 0 in the contact frame: the force geom1 - the
+        floor for floor contacts - exerts on geom2), self.con_frame [N, 32, 3, 3] (rows normal, t1, t2), self.con_pos
+        [N, 32, 3] (world), self.con_dist [N, 32], self.actuator_force [N, NA] (ctrl order), self.foot_force [N, 2, 3]
+        (world) and self.foot_cop [N, 2, 3] (LF, RF).  Contact rows follow con_pairs; rows >= ncon are zero.  reset() does
+        not touch them."""
+        self.sync_sim()   # sim stages step_pipelined() has not launched yet must write the buffers they were launched with
+        N = self.num_envs
+        want = dict(con_force=(N, MAXCON, 6), con_frame=(N, MAXCON, 9), con_pos=(N, MAXCON, 4), actuator_force=(N, self.NA),
+                    foot_grf=(N, 2, 6))
+        given = dict(con_force=con_force, con_frame=con_frame, con_pos=con_pos, actuator_force=actuator_force, foot_grf=foot_grf)
+        bufs = {}
+        for k, shape in want.items():
+            t = given[k]
+            if t is None:
+                t = torch.zeros(*shape, dtype=self.dtype, device=self.device)
+            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device \
+                    or not t.is_contiguous():
+                what = (tuple(t.shape), t.dtype, t.device, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)
+                raise _lib.TsidbError(f"enable_sim_readouts: {k} must be a contiguous {shape} {self.dtype} tensor on {self.device}, "
+                                      f"got {what}")
+            bufs[k] = t
+        rc = self._L.tsidb_set_sim_readouts(self._h, *(_ptr(bufs[k]) for k in want))
+        _lib.check(self._L, self._h, rc, "tsidb_set_sim_readouts")
+        self._readouts = bufs
+        self.con_force, self.actuator_force = bufs["con_force"], bufs["actuator_force"]
+        self.con_frame = bufs["con_frame"].view(N, MAXCON, 3, 3)
+        self.con_pos, self.con_dist = bufs["con_pos"][:, :, :3], bufs["con_pos"][:, :, 3]
+        self.foot_force, self.foot_cop = bufs["foot_grf"][:, :, :3], bufs["foot_grf"][:, :, 3:]
+
+    def disable_sim_readouts(self):
+        """Unregister the readouts: the sim stage runs its kernels without them again (bit-identical state)."""
+        self.sync_sim()
+        _lib.check(self._L, self._h, self._L.tsidb_set_sim_readouts(self._h, None, None, None, None, None), "tsidb_set_sim_readouts")
+        self._readouts = None
+        self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
+
+    def sim_cop(self):
+        """[N, 3] centre of pressure the sim realised on the floor: both soles' CoPs weighted by their normal force (the floor
+        normal of set_env_params, else +z) - the counterpart of get_cop().  NaN where neither sole carries a normal force."""
+        if getattr(self, "_readouts", None) is None:
+            raise _lib.TsidbError("sim_cop needs enable_sim_readouts()")
+        nrm = self.env_params[:, 2:5] if self.env_params is not None else \
+            torch.tensor([0.0, 0.0, 1.0], dtype=self.dtype, device=self.device).expand(self.num_envs, 3)
+        w = (self.foot_force * nrm[:, None, :]).sum(-1)          # [N, 2] normal force per sole
+        tot = w.sum(1, keepdim=True)
+        cop = (w[:, :, None] * self.foot_cop).sum(1) / tot
+        return torch.where(tot > 0, cop, torch.full_like(cop, float("nan")))
+
+    def contact_bodies(self):
+        """[N, 32, 2] int32 (body1, body2) of each row of con_pairs: sim bodies (the blob's order, 0 = torso) of geom1 and
+        geom2 (mj_data.contact.geom -> mj_geom_body); the floor is -1.  Rows >= ncon are (-1, -1)."""
+        gb = getattr(self, "_geom_body", None)
+        if gb is None:
+            gb = self._geom_body = torch.as_tensor(np.asarray(self.model["mj_geom_body"], dtype=np.int64), device=self.device)
+        cp = self.con_pairs.long()
+        live = cp >= 0
+        g2 = torch.where(live, cp >> 16, torch.zeros_like(cp))
+        hh = live & ((cp & 0x8000) != 0)                          # robot<->robot: the low bits carry geom1
+        g1 = torch.where(hh, cp & 0x7fff, torch.zeros_like(cp))
+        b2 = torch.where(live, gb[g2], torch.full_like(cp, -1))
+        b1 = torch.where(hh, gb[g1], torch.full_like(cp, -1))
+        return torch.stack([b1, b2], dim=-1).to(torch.int32)
+
     def body_masses(self):
         """[N, NB] mass of every sim body (the blob's mj_inertia[:, 0] times the env's mass scale, set_env_params): what a
         uniform acceleration field a needs as forces, F_b = m_b a.  v1 robot (robot.xml document order): torso 0, left
@@ -338,12 +410,12 @@ class WalkController:
         tick(t+1) are independent; the TSID state is handed to the sim through a ring of snapshot slots the tick writes.
         walk = (schedule, t) runs that tick's WalkSchedule.apply inside the tick's launch (tsidb_tick_walk).
         tau, q, v, status, obs are valid on the current stream as after step(); the sim state (qpos, qvel,
-        qacc_warmstart, ncon, con_pairs, info[:, 2:4]) is valid after sync_sim() ONLY: with conf.pipeline_sim_batch > 1
+        qacc_warmstart, ncon, con_pairs, info[:, 2:4], and the readouts of enable_sim_readouts()) is valid after sync_sim() ONLY: with conf.pipeline_sim_batch > 1
         (the default for up to 1024 envs is 8) the last few sim stages are not even launched until the batch is full, so a
         device / stream synchronize does not make the sim state current - sync_sim() launches them and makes the current
         stream wait.  Every entry point of this class that reads or rewrites sim-side data (step, sim_step, reset,
-        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, capture_steps, WalkSchedule.apply with
-        touch-down feedback) calls it.
+        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, enable_sim_readouts, disable_sim_readouts,
+        capture_steps, WalkSchedule.apply with touch-down feedback) calls it.
         `events` = four torch.cuda.Event recorded around the tick (current stream) and around the sim (sim stream), for
         timing."""
         if getattr(self.conf, "closed_loop", False) or not getattr(self.conf, "sim_enabled", True):
@@ -517,6 +589,7 @@ class WalkController:
         keep = {k: getattr(self, k).clone() for k in ("q", "v", "qpos", "qvel", "qacc_warmstart", "com_ref", "posture_ref",
                                                       "foot_ref", "contact_ref", "contact_active", "frames", "rows", "tau", "dv", "f",
                                                       "status", "ncon", "con_pairs", "info", "cop_ref")}
+        ro_keep = {k: t.clone() for k, t in self._readouts.items()} if self._readouts is not None else {}
         latch_keep = sched.td_latch.clone() if sched is not None and sched.td_latch is not None else None
         t_keep = self.t
         if sched is not None:
@@ -527,6 +600,8 @@ class WalkController:
         torch.cuda.synchronize(self.device)
         for k, v in keep.items():
             getattr(self, k).copy_(v)
+        for k, v in ro_keep.items():
+            self._readouts[k].copy_(v)
         if latch_keep is not None:
             sched.td_latch.copy_(latch_keep)
         self.t = t_keep
@@ -549,7 +624,7 @@ class WalkController:
 
         class _Graph:
             steps = n_steps
-            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc)   # what the captured kernels point at
+            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc, self._readouts)   # what the captured kernels point at
 
             def replay(self_inner):
                 g.replay()
