@@ -147,6 +147,35 @@ int tsidb_set_xfrc(tsidb_handle h, void *xfrc);
  * library built without the sim stage. */
 int tsidb_set_sim_readouts(tsidb_handle h, void *con_force, void *con_frame, void *con_pos, void *act_force, void *foot_grf);
 
+/* site sensors of the sim stage: mj_data.sensordata, which mj_step fills through mj_sensorPos / mj_sensorVel / mj_sensorAcc
+ * (robot/v0/robot.xml:214-219 declares framepos, framequat, framelinvel and frameangvel on root_site).  n_sites sites
+ * (1 .. TSIDB_MAXSITE): site_body [S] (the blob's sim body order, as for tsidb_set_xfrc), site_pos [S,3] and site_quat [S,4]
+ * (wxyz, normalised on the way in) in the body's own frame - host arrays, copied into the model constants.  sensordata
+ * [N,S,TSIDB_NSENS] is a device buffer in the path's arithmetic type; the pointer is remembered, not copied.  Row per site:
+ *   0-2   framepos      world position of the site (mj_sensorPos: site_xpos)
+ *   3-6   framequat     world orientation, wxyz, unit; w >= 0 is not enforced, as in MuJoCo (mj_sensorPos)
+ *   7-9   framelinvel   world-frame linear velocity of the site point (mj_sensorVel: mj_objectVelocity, flg_local = 0)
+ *   10-12 frameangvel   world-frame angular velocity (the same call)
+ *   13-15 velocimeter   linear velocity in the site frame (mj_sensorVel: mj_objectVelocity, flg_local = 1)
+ *   16-18 gyro          angular velocity in the site frame (the same call)
+ *   19-21 accelerometer site-frame linear acceleration of the site point minus gravity (mj_sensorAcc: mj_objectAcceleration on
+ *                       the cacc of mj_rnePostConstraint, whose world body accelerates at -gravity; it includes the omega x v
+ *                       term that turns the spatial into the classical acceleration): R_site^T (0,0,+g) at rest on the floor,
+ *                       0 in free fall.  The acceleration is the constraint solver's qacc (mj_data.qacc, what the step leaves
+ *                       in qacc_ws) - with joint damping (the v0 robot) not the damped-Euler effective one.
+ *   22-23 spare         zero
+ * Timing is mj_step's: sensors are evaluated inside mj_forward, before the integrator, so after a step the rows describe the
+ * positions and velocities the step STARTED from (in the teleport mode: after the teleport) and the acceleration it solved for.
+ * Every sim step writes the rows (a tsidb_sim_batch launch or a tsidb_step with substeps leaves the last step's values); a
+ * skipped step (info flag bit 4) zeroes the env's rows; tsidb_reset / tsidb_reset_done do not touch them.  n_sites = 0 with
+ * sensordata = NULL (the default) unregisters.  Changing the site table first waits for the handle's kernels in flight, as
+ * tsidb_set_params does.  Fails (message via tsidb_last_error) in a library built without the sim stage, for a body index out
+ * of range, a non-finite value, a zero quaternion, more than TSIDB_MAXSITE sites, and when exactly one of n_sites and
+ * sensordata is empty. */
+enum { TSIDB_MAXSITE = 16, TSIDB_NSENS = 24 };
+int tsidb_set_sensors(tsidb_handle h, int n_sites, const int32_t *site_body, const double *site_pos, const double *site_quat,
+                      void *sensordata);
+
 /* reset: WalkController.py:22-26,72-79 (standing state, soles onto z = 0), the references of
  * :81,122,151-152,164-165, and main.py:57-64 (mj_data.qpos = q).  env_ids (device, int32) selects
  * envs; NULL = all (a non-NULL list with n_ids = 0 resets nothing).  Writes state AND the reference buffers

@@ -228,7 +228,9 @@ template <typename T> struct SimRing { const T *q, *v; unsigned long long slots;
 // so the kernels without it are unchanged (xfrc is then not read).
 // RO = the step writes the readouts ro (tsidb_set_sim_readouts; the last step of a batch leaves its values); likewise selected
 // only while a buffer is registered (ro, the last argument, is then not read).
-template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false, bool RO = false>
+// SE = the step writes the site sensors to ro.sens (tsidb_set_sensors), [N, nsite, NSENS]; likewise selected only while a buffer
+// is registered, and built together with RO = true only (unregistered readouts are NULL pointers there and store nothing).
+template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false, bool RO = false, bool SE = false>
 __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))) void k_sim(const DevModel<T> *__restrict__ mp, int n, int B, SimRing<T> ring, T *qpos, T *qvel,
                                               T *qacc_ws, const T *env_params, const T *terrain, const T *xfrc, const T *motor_tau, T *qacc, int *ncon,
                                               int *con, int *info, SimOut<T> ro) {
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       asm volatile("" : "+s"(qacc), "+s"(ncon), "+s"(con), "+s"(info) : : "memory");
       if constexpr (XF) asm volatile("" : "+s"(xfrc) : : "memory");
       if constexpr (RO) asm volatile("" : "+s"(ro.con_force), "+s"(ro.con_frame), "+s"(ro.con_pos), "+s"(ro.act_force), "+s"(ro.foot_grf) : : "memory");
+      if constexpr (SE) asm volatile("" : "+s"(ro.sens) : : "memory");
     }
     SimOut<T> roe{}; // (the env's rows)
     if constexpr (RO) {
@@ -257,6 +260,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       roe.foot_grf = ro.foot_grf ? ro.foot_grf + E * 12 : nullptr;
       roe.foot_body[0] = ro.foot_body[0]; roe.foot_body[1] = ro.foot_body[1];
     }
+    if constexpr (SE) roe.sens = ro.sens + E * NSENS * mq->nsite;
     const size_t slot = (size_t)((ring.slots >> (4 * b)) & 15ull);
     const T *q_tsid = ring.q ? ring.q + slot * (size_t)n * NQ : nullptr, *v_tsid = ring.v ? ring.v + slot * (size_t)n * NV : nullptr;
     bool skip;
@@ -278,10 +282,11 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
         }
         if (con && lane < MAXCON) con[E * MAXCON + lane] = -1;
         if constexpr (RO) sim_readouts_zero(roe, lane);
+        if constexpr (SE) sim_sensors_zero(*mq, roe.sens, lane);
       }
     }
     if (!skip)
-      sim_step_env<T, NW, XF, RO>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+      sim_step_env<T, NW, XF, RO, SE>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
                           env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
                           motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
                           info ? info + E * 4 : nullptr, roe);
@@ -662,6 +667,8 @@ static void chain_table(const int *parent, int n, int (*chain)[8]) {
 
 } // namespace
 
+static_assert(MAXSITE == TSIDB_MAXSITE && NSENS == TSIDB_NSENS, "include/tsidb.h and the kernels agree on the sensor rows");
+
 // Batches up to this many envs default to two wavefronts per env in k_sim and to CU-split streams (tsidb_stream_create):
 // measured, DESIGN.md section 5 "Streams"
 constexpr int SMALL_BATCH_ENVS = 512;
@@ -692,6 +699,10 @@ struct tsidb_ctx {
                                                                 // act_force, foot_grf
   bool has_readouts() const { return ro[0] || ro[1] || ro[2] || ro[3] || ro[4]; }
   int foot_body[2] = {-1, -1}; // sim bodies that carry the left / right sole frame
+  // site sensors (tsidb_set_sensors): the site table as given (orientation as a row-major rotation) and the output buffer
+  int n_sites = 0, site_body[TSIDB_MAXSITE] = {};
+  double site_pos[TSIDB_MAXSITE][3] = {}, site_R[TSIDB_MAXSITE][9] = {};
+  void *sens = nullptr; // [N, n_sites, TSIDB_NSENS]
   unsigned long long foot_geoms[2] = {0, 0}; // bit g: collision geom g is on that body
   std::string err;
 };
@@ -874,6 +885,12 @@ static void build_model(tsidb_ctx *h, DevModel<T> &m) {
   m.chunk_box = (const T *)h->d_box;
   m.hull_eadr = h->d_eadr;
   m.hull_edge = h->d_edge;
+  m.nsite = h->n_sites;
+  for (int s = 0; s < h->n_sites; s++) {
+    m.site_body[s] = h->site_body[s];
+    for (int i = 0; i < 3; i++) m.site_pos[s][i] = (T)h->site_pos[s][i];
+    for (int i = 0; i < 9; i++) m.site_R[s][i] = (T)h->site_R[s][i];
+  }
 }
 
 // The kernels index the hull arrays with addresses taken from the blob and pack (geom << 16 | vertex) with bit 15 as
@@ -1027,19 +1044,20 @@ static void launch_tick(tsidb_ctx *h, void *q, void *v, void *tau, void *dv, voi
 // instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
 // neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
 // (a registered xfrc buffer selects the XF = true instantiations, registered readouts the RO = true ones; the float32 build for
-//  three wavefronts per SIMD has neither: the default build, bit-identical to it, runs instead; it is also never picked with
+//  three wavefronts per SIMD has neither, nor sensors: the default build, bit-identical to it, runs instead; it is also never picked with
 //  lds_pad != 0)
 template <typename T>
 static auto sim_kernel(const tsidb_ctx *h, int B, bool motor_tau) {
   if constexpr (sizeof(T) == 4)
-    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc && !h->has_readouts())
+    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc && !h->has_readouts() && !h->sens)
       return k_sim<float, 1, false, 3, false, false>;
-#define TSIDB_SIM_RO(NW, MULTI, XF) {k_sim<T, NW, MULTI, TSIDB_WPE, XF, false>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true>}
-  const decltype(&k_sim<T, 1, false>) pick[2][2][2][2] = { // [sim_waves == 2][B > 1][xfrc registered][readouts registered]
+  // (registered sensors select the SE = true instantiations, which exist with RO = true only: the nearest superset)
+#define TSIDB_SIM_RO(NW, MULTI, XF) {k_sim<T, NW, MULTI, TSIDB_WPE, XF, false>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true, true>}
+  const decltype(&k_sim<T, 1, false>) pick[2][2][2][3] = { // [sim_waves == 2][B > 1][xfrc registered][readouts / sensors registered]
       {{TSIDB_SIM_RO(1, false, false), TSIDB_SIM_RO(1, false, true)}, {TSIDB_SIM_RO(1, true, false), TSIDB_SIM_RO(1, true, true)}},
       {{TSIDB_SIM_RO(2, false, false), TSIDB_SIM_RO(2, false, true)}, {TSIDB_SIM_RO(2, true, false), TSIDB_SIM_RO(2, true, true)}}};
 #undef TSIDB_SIM_RO
-  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr][h->has_readouts()];
+  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr][h->sens ? 2 : h->has_readouts()];
 }
 
 // B sim steps in one launch, step b driven by slot slots[b] of the [K, N, NQ] / [K, N, NV] rings q_ring / v_ring (slot 0 if NULL)
@@ -1061,7 +1079,7 @@ static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ri
                          (const DevModel<T> *)h->d_model, h->num_envs, B, SimRing<T>{(const T *)q_ring, (const T *)v_ring, slot_bits},
                          (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc,
                          (const T *)motor_tau, (T *)qacc, ncon, con, info,
-                         SimOut<T>{(T *)h->ro[0], (T *)h->ro[1], (T *)h->ro[2], (T *)h->ro[3], (T *)h->ro[4], {h->foot_body[0], h->foot_body[1]}});
+                         SimOut<T>{(T *)h->ro[0], (T *)h->ro[1], (T *)h->ro[2], (T *)h->ro[3], (T *)h->ro[4], {h->foot_body[0], h->foot_body[1]}, (T *)h->sens});
   });
   HIP_OK(hipGetLastError());
 }
@@ -1156,6 +1174,45 @@ int tsidb_set_params(tsidb_handle h, const double *params, int n_params) {
   else
     for (hipStream_t st : h->used_streams)
       if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+  with_dtype(h->dtype, [&](auto t) { upload_model<decltype(t)>(h); });
+  GUARD_END
+}
+
+int tsidb_set_sensors(tsidb_handle h, int n_sites, const int32_t *site_body, const double *site_pos, const double *site_quat,
+                      void *sensordata) {
+  GUARD_BEGIN
+  if (!TOPO_HAS_SIM && (n_sites || sensordata)) throw std::string("tsidb_set_sensors: this library was built without the sim stage");
+  if (n_sites < 0 || n_sites > TSIDB_MAXSITE) throw std::string("tsidb_set_sensors: n_sites must be 0 .. TSIDB_MAXSITE");
+  if ((n_sites == 0) != (sensordata == nullptr)) throw std::string("tsidb_set_sensors: sites without a buffer, or a buffer without sites");
+  if (n_sites && (!site_body || !site_pos || !site_quat)) throw std::string("tsidb_set_sensors: null site table");
+  double R[TSIDB_MAXSITE][9];
+  for (int s = 0; s < n_sites; s++) {
+    if (site_body[s] < 0 || site_body[s] >= NB) throw std::string("tsidb_set_sensors: site body out of range");
+    double nn = 0;
+    for (int i = 0; i < 3; i++) if (!std::isfinite(site_pos[3 * s + i])) throw std::string("tsidb_set_sensors: non-finite site position");
+    for (int i = 0; i < 4; i++) {
+      if (!std::isfinite(site_quat[4 * s + i])) throw std::string("tsidb_set_sensors: non-finite site quaternion");
+      nn += site_quat[4 * s + i] * site_quat[4 * s + i];
+    }
+    nn = std::sqrt(nn);
+    if (!(nn > 0) || !std::isfinite(nn)) throw std::string("tsidb_set_sensors: zero site quaternion");
+    const double w = site_quat[4 * s] / nn, x = site_quat[4 * s + 1] / nn, y = site_quat[4 * s + 2] / nn, z = site_quat[4 * s + 3] / nn;
+    const double Rs[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                          2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+    memcpy(R[s], Rs, sizeof Rs);
+  }
+  // the site table is part of the model constants: wait for the kernels in flight, as tsidb_set_params does
+  if (h->streams_overflow) HIP_OK(hipDeviceSynchronize());
+  else
+    for (hipStream_t st : h->used_streams)
+      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+  h->n_sites = n_sites;
+  for (int s = 0; s < n_sites; s++) {
+    h->site_body[s] = site_body[s];
+    memcpy(h->site_pos[s], site_pos + 3 * s, sizeof h->site_pos[s]);
+    memcpy(h->site_R[s], R[s], sizeof R[s]);
+  }
+  h->sens = sensordata;
   with_dtype(h->dtype, [&](auto t) { upload_model<decltype(t)>(h); });
   GUARD_END
 }

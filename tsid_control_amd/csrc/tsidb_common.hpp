@@ -47,6 +47,7 @@ constexpr int CONDIM = TOPO_CONDIM;   // contact dimension: 3 (robot/v1) or 4 (+
 constexpr int NROWC = 2 * (CONDIM - 1); // pyramidal rows per contact
 constexpr bool EULERDAMP = TOPO_EULERDAMP != 0; // joint damping, integrated implicitly as MuJoCo's Euler does
 static_assert(NG <= 64 && NG >= NB && (CONDIM == 3 || CONDIM == 4) && MAXPAIR % 64 == 0, "sim stage limits");
+constexpr int MAXSITE = 16;  // sensor sites per env (TSIDB_MAXSITE)
 constexpr int MAXCHILD = 6;
 constexpr int WAVE = 64;
 
@@ -115,6 +116,10 @@ struct DevModel {
   // centres of mass and body-frame bounding boxes (centre, half extents)
   int npair, pair_a[MAXPAIR], pair_b[MAXPAIR]; // geom pairs
   T hcen[NG][3], hbox[NG][6];
+  // site sensors (tsidb_set_sensors): body, position and orientation (row-major) of each site in its body's frame.  Last in the
+  // block: the offsets of everything above are those of a library without them
+  int nsite, site_body[MAXSITE];
+  T site_pos[MAXSITE][3], site_R[MAXSITE][9];
 };
 
 // ------------------------------------------------------------------ small vector helpers

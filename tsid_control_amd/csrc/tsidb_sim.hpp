@@ -965,6 +965,7 @@ template <typename T> __device__ __forceinline__ void sub_xfrc(const T *w, const
 template <typename T> struct SimOut {
   T *con_force, *con_frame, *con_pos, *act_force, *foot_grf;
   int foot_body[2];
+  T *sens; // site sensors (tsidb_set_sensors): the env's [nsite][NSENS] rows; read by the SE instantiations only
 };
 
 // Epilogue of a step with readouts, lane = contact, at the solver's final qacc (rs.cjar).  Per contact mj_contactForce: the
@@ -1049,10 +1050,128 @@ template <typename T> __device__ __forceinline__ void sim_readouts_zero(const Si
   if (ro.foot_grf && lane < 12) ro.foot_grf[lane] = 0;
 }
 
+// Site sensors (tsidb_set_sensors): mj_data.sensordata of the step, lane = site.  A site s sits on body b = m.site_body[s] at
+// m.site_pos[s] with orientation m.site_R[s], both in the body's frame.  Row layout (NSENS = 24 columns, include/tsidb.h):
+// framepos 0-2, framequat 3-6 (wxyz), framelinvel 7-9, frameangvel 10-12, velocimeter 13-15, gyro 16-18, accelerometer 19-21,
+// spare 22-23.  Two parts, because no LDS survives from the tree pass to the end of the Newton loop but S, qpos, qvel and anc
+// (and SimLds<double> has 24 bytes to spare): part 1 runs where the body frames, velocities and bias accelerations are in LDS,
+// part 2 where qacc is final.  What part 2 needs of part 1 is parked in the env's own row - columns 19-21 hold the
+// velocity-dependent part of the point's classical acceleration in the world frame until part 2 replaces them - and the offset
+// r and the rotation are rebuilt from framepos and framequat: nothing stays live in registers across the Newton loop, whose
+// kernels have none to spare.  Same lane, same wavefront, same addresses: the accesses stay ordered.
+constexpr int NSENS = 24; // TSIDB_NSENS
+
+// mju_mat2Quat's four cases (the largest of the trace and the three diagonal entries picks the component that is computed by
+// the square root: stable at every angle, 180 degrees included), then normalised.  wxyz, w >= 0 not enforced.
+template <typename T> __device__ __forceinline__ void mat_to_quat(const T *R, T *q) {
+  const T tr = R[0] + R[4] + R[8];
+  if (tr > 0) {
+    const T s = 2 * sqrt(tr + 1);
+    q[0] = T(0.25) * s; q[1] = (R[7] - R[5]) / s; q[2] = (R[2] - R[6]) / s; q[3] = (R[3] - R[1]) / s;
+  } else if (R[0] > R[4] && R[0] > R[8]) {
+    const T s = 2 * sqrt(1 + R[0] - R[4] - R[8]);
+    q[0] = (R[7] - R[5]) / s; q[1] = T(0.25) * s; q[2] = (R[1] + R[3]) / s; q[3] = (R[2] + R[6]) / s;
+  } else if (R[4] > R[8]) {
+    const T s = 2 * sqrt(1 + R[4] - R[0] - R[8]);
+    q[0] = (R[2] - R[6]) / s; q[1] = (R[1] + R[3]) / s; q[2] = T(0.25) * s; q[3] = (R[5] + R[7]) / s;
+  } else {
+    const T s = 2 * sqrt(1 + R[8] - R[0] - R[4]);
+    q[0] = (R[3] - R[1]) / s; q[1] = (R[2] + R[6]) / s; q[2] = (R[5] + R[7]) / s; q[3] = T(0.25) * s;
+  }
+  const T nn = T(1) / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] *= nn;
+}
+
+// Part 1 (mj_sensorPos, mj_sensorVel): right after the tree pass.  L.R / L.p / L.V / L.A hold every body's frame (p relative to
+// the spatial origin O = the base position), spatial velocity and bias acceleration [lin; ang] about O.  With r = p_b + R_b pos_s:
+// position O + r, orientation R_b R_s, point velocity v + w x r (mj_objectVelocity), and the part of the point's classical
+// acceleration that does not depend on qacc, A_lin + A_ang x r + w x (v + w x r) - g (mj_objectAcceleration on cacc with the
+// world body accelerating at -gravity; w x v is the spatial -> classical correction).
+template <typename T>
+__device__ __forceinline__ void sim_sensors_kin(const DevModel<T> &m, const SimLds<T> &L, int lane, T gz, T *sens) {
+  if (lane < m.nsite) {
+    const int b = m.site_body[lane];
+    T Rb[9], r[3], Rw[9], q[4], V[6], A[6], vp[3], t[3], vl[3], wl[3], acc[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) Rb[i] = L.R[b][i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { V[i] = L.V[b][i]; A[i] = L.A[b][i]; }
+    mat3vec(Rb, m.site_pos[lane], r);
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] += L.p[b][i];
+    mat3mul(Rb, m.site_R[lane], Rw);
+    mat_to_quat(Rw, q);
+    cross3(V + 3, r, t);
+#pragma unroll
+    for (int i = 0; i < 3; i++) vp[i] = V[i] + t[i];
+    mat3Tvec(Rw, vp, vl);
+    mat3Tvec(Rw, V + 3, wl);
+    cross3(A + 3, r, t);
+    cross3(V + 3, vp, acc);
+#pragma unroll
+    for (int i = 0; i < 3; i++) acc[i] += A[i] + t[i];
+    acc[2] -= gz;
+    T *o = sens + NSENS * lane;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      o[i] = L.qpos[i] + r[i];
+      o[7 + i] = vp[i]; o[10 + i] = V[3 + i]; o[13 + i] = vl[i]; o[16 + i] = wl[i];
+      o[19 + i] = acc[i]; // (parked for part 2)
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[3 + i] = q[i];
+    o[22] = 0; o[23] = 0;
+  }
+}
+
+// Part 2 (mj_sensorAcc): after the Newton loop, qacc staged in L.xv.  The qacc part of the body's spatial acceleration is the sum
+// of S_k qacc_k over the dofs on the body's root path - the root's six, then the static chain table - evaluated at the site,
+// lin + ang x r; the sum with the parked part is rotated into the site frame.  L.qpos is still the step's start.
+template <typename T>
+__device__ __forceinline__ void sim_sensors_acc(const DevModel<T> &m, const SimLds<T> &L, int lane, T *sens) {
+  if (lane < m.nsite) {
+    const int b = m.site_body[lane];
+    T a[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const T qa = L.xv[k];
+#pragma unroll
+      for (int i = 0; i < 6; i++) a[i] += L.S[k][i] * qa;
+    }
+#pragma unroll
+    for (int d = 6; d >= 0; d--) {
+      const int c = m.mj_chain[b][d];
+      if (c > 0) {
+        const T qa = L.xv[5 + c];
+#pragma unroll
+        for (int i = 0; i < 6; i++) a[i] += L.S[5 + c][i] * qa;
+      }
+    }
+    T *o = sens + NSENS * lane;
+    T r[3], t[3], acc[3], al[3], Rw[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++) r[i] = o[i] - L.qpos[i];
+    quat_to_R(o[4], o[5], o[6], o[3], Rw); // wxyz storage
+    cross3(a + 3, r, t);
+#pragma unroll
+    for (int i = 0; i < 3; i++) acc[i] = o[19 + i] + (a[i] + t[i]);
+    mat3Tvec(Rw, acc, al);
+#pragma unroll
+    for (int i = 0; i < 3; i++) o[19 + i] = al[i];
+  }
+}
+
+// a skipped step zeroes the env's sensor rows
+template <typename T> __device__ __forceinline__ void sim_sensors_zero(const DevModel<T> &m, T *sens, int lane) {
+  for (int i = lane; i < NSENS * m.nsite; i += WAVE) sens[i] = 0;
+}
+
 // XF: the kernel reads external wrenches (xfrc, the env's [NB, 6] rows; tsidb_set_xfrc).  A template parameter rather than a
 // runtime NULL test: the test alone cost the multi-step and the three-wavefront float32 kernels VGPR spills.
 // RO: the step writes the readouts of `ro` (tsidb_set_sim_readouts), likewise a template parameter.
-template <typename T, int NW, bool XF, bool RO>
+// SE: the step writes the site sensors to ro.sens (tsidb_set_sensors), likewise; built together with RO = true only.
+template <typename T, int NW, bool XF, bool RO, bool SE = false>
 __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
                              int *con_out, int *info, const SimOut<T> &ro) {
@@ -1228,6 +1347,9 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   }
   __syncthreads();
   const bool w_dyn = NW == 1 || wv == 0, w_col = NW == 1 || wv == NW - 1; // which phases this wavefront runs
+  if constexpr (SE) { // site sensors, part 1: the body frames, V and A are visible, and none of them is overwritten yet
+    if (w_dyn) sim_sensors_kin<T>(m, L, lane, gz, ro.sens);
+  }
   // ---- per dof: bias, mass-matrix column (+ armature), actuation
   T qfs = 0;
   if (w_dyn) {
@@ -1942,6 +2064,12 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
   }
   // readouts: here, before the damped-Euler solve, so that the row state is dead across it; L.qpos is still the step's start
   if constexpr (RO) sim_readouts<T>(m, L, lane, nfl, ncon, mu, rs, ro);
+  if constexpr (SE) { // site sensors, part 2: the solver's qacc goes through L.xv (free from here on)
+    wsync<NW>();
+    if (lane < NV) L.xv[lane] = qacc;
+    wsync<NW>();
+    sim_sensors_acc<T>(m, L, lane, ro.sens);
+  }
   wsync<NW>();
   TSIDB_STAMP(21);
   // ---- semi-implicit Euler, write back

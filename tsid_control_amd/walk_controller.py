@@ -86,6 +86,8 @@ class WalkController:
         self.xfrc = None   # external body wrenches [N, NB, 6] (set_xfrc / apply_push); None = none registered
         self._readouts = None   # sim-stage readout buffers (enable_sim_readouts); None = none registered
         self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
+        self.sensordata = None   # site sensors [N, S, 24] (enable_sensors); None = none registered
+        self.framepos = self.framequat = self.framelinvel = self.frameangvel = self.velocimeter = self.gyro = self.accelerometer = None
         rc = L.tsidb_set_refs(self._h, _ptr(self.com_ref), _ptr(self.posture_ref), _ptr(self.foot_ref),
                               _ptr(self.contact_ref), _ptr(self.contact_active), _ptr(self.cop_frames))
         _lib.check(L, self._h, rc, "tsidb_set_refs")
@@ -277,6 +279,60 @@ class WalkController:
         self._readouts = None
         self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
 
+    # ------------------------------------------------------------------ site sensors (IMU, frame readouts)
+    SENSOR_COLUMNS = dict(framepos=(0, 3), framequat=(3, 7), framelinvel=(7, 10), frameangvel=(10, 13), velocimeter=(13, 16),
+                          gyro=(16, 19), accelerometer=(19, 22))
+
+    def _named_site(self, name):
+        if name == "imu":          # the free joint's frame: root_site of robot/v0/robot.xml:62
+            return 0, (0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0)
+        if name in ("lf_imu", "rf_imu"):   # the sole bodies: sole frame -> TSID joint -> sim joint -> body, as foot_grf finds them
+            fp, s2t = self.model["pin_frame_parent"], list(self.model["mj_sim2tsid"])
+            return 1 + s2t.index(int(fp[0 if name == "lf_imu" else 1]) - 1), (0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0)
+        raise _lib.TsidbError(f"enable_sensors: unknown site name {name!r} (known: 'imu', 'lf_imu', 'rf_imu')")
+
+    def enable_sensors(self, sites=None, out=None):
+        """Register site sensors of the sim stage (include/tsidb.h tsidb_set_sensors): what a MuJoCo caller reads after
+        mj_step as mj_data.sensordata.  sites = a list (1 .. 16 entries) of names or (body, pos [3], quat [4] wxyz) tuples in
+        the body's own frame (sim body order, 0 = torso): "imu" is body 0 at the origin with identity orientation (the free
+        joint's frame), "lf_imu" / "rf_imu" the two sole bodies' frames; default ["imu"].  out = a tensor to use in place
+        ([N, S, 24], self.dtype, on self.device, contiguous) or None to allocate one.  Every sim step of step(), sim_step(),
+        step_pipelined() and capture_steps() then writes the rows; a pipelined caller reads them after sync_sim(), like qpos.
+        Exposed as self.sensordata [N, S, 24] and as views under MuJoCo's names: framepos, framelinvel, frameangvel (world
+        frame), velocimeter, gyro, accelerometer (site frame) [N, S, 3] and framequat [N, S, 4] (wxyz).  As in mj_step the
+        rows describe the positions and velocities the step STARTED from and the acceleration it solved for; the
+        accelerometer reads R^T (0, 0, g) at rest and 0 in free fall.  reset() does not touch them."""
+        self.sync_sim()   # sim stages step_pipelined() has not launched yet must write the buffer they were launched with
+        sites = ["imu"] if sites is None else list(sites)
+        S, N = len(sites), self.num_envs
+        if not 1 <= S <= 16:
+            raise _lib.TsidbError(f"enable_sensors: need 1 .. 16 sites, got {S}")
+        body, pos, quat = np.zeros(S, np.int32), np.zeros((S, 3)), np.zeros((S, 4))
+        for i, st in enumerate(sites):
+            b, p, q = self._named_site(st) if isinstance(st, str) else st
+            body[i], pos[i], quat[i] = int(b), np.asarray(p, dtype=np.float64).reshape(3), np.asarray(q, dtype=np.float64).reshape(4)
+        shape = (N, S, 24)
+        if out is None:
+            out = torch.zeros(*shape, dtype=self.dtype, device=self.device)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != self.dtype or out.device != self.device \
+                or not out.is_contiguous():
+            what = (tuple(out.shape), out.dtype, out.device, out.is_contiguous()) if isinstance(out, torch.Tensor) else type(out)
+            raise _lib.TsidbError(f"enable_sensors: out must be a contiguous {shape} {self.dtype} tensor on {self.device}, got {what}")
+        vp = C.c_void_p
+        rc = self._L.tsidb_set_sensors(self._h, S, body.ctypes.data_as(vp), pos.ctypes.data_as(vp), quat.ctypes.data_as(vp), _ptr(out))
+        _lib.check(self._L, self._h, rc, "tsidb_set_sensors")
+        self.sensordata = out
+        for k, (a, b) in self.SENSOR_COLUMNS.items():
+            setattr(self, k, out[:, :, a:b])
+
+    def disable_sensors(self):
+        """Unregister the site sensors: the sim stage runs its kernels without them again (bit-identical state)."""
+        self.sync_sim()
+        _lib.check(self._L, self._h, self._L.tsidb_set_sensors(self._h, 0, None, None, None, None), "tsidb_set_sensors")
+        self.sensordata = None
+        for k in self.SENSOR_COLUMNS:
+            setattr(self, k, None)
+
     def sim_cop(self):
         """[N, 3] centre of pressure the sim realised on the floor: both soles' CoPs weighted by their normal force (the floor
         normal of set_env_params, else +z) - the counterpart of get_cop().  NaN where neither sole carries a normal force."""
@@ -414,7 +470,7 @@ class WalkController:
         (the default for up to 1024 envs is 8) the last few sim stages are not even launched until the batch is full, so a
         device / stream synchronize does not make the sim state current - sync_sim() launches them and makes the current
         stream wait.  Every entry point of this class that reads or rewrites sim-side data (step, sim_step, reset,
-        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, enable_sim_readouts, disable_sim_readouts,
+        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, enable_sim_readouts, disable_sim_readouts, enable_sensors, disable_sensors,
         capture_steps, WalkSchedule.apply with touch-down feedback) calls it.
         `events` = four torch.cuda.Event recorded around the tick (current stream) and around the sim (sim stream), for
         timing."""
@@ -590,6 +646,7 @@ class WalkController:
                                                       "foot_ref", "contact_ref", "contact_active", "frames", "rows", "tau", "dv", "f",
                                                       "status", "ncon", "con_pairs", "info", "cop_ref")}
         ro_keep = {k: t.clone() for k, t in self._readouts.items()} if self._readouts is not None else {}
+        sens_keep = self.sensordata.clone() if self.sensordata is not None else None
         latch_keep = sched.td_latch.clone() if sched is not None and sched.td_latch is not None else None
         t_keep = self.t
         if sched is not None:
@@ -602,6 +659,8 @@ class WalkController:
             getattr(self, k).copy_(v)
         for k, v in ro_keep.items():
             self._readouts[k].copy_(v)
+        if sens_keep is not None:
+            self.sensordata.copy_(sens_keep)
         if latch_keep is not None:
             sched.td_latch.copy_(latch_keep)
         self.t = t_keep
@@ -624,7 +683,7 @@ class WalkController:
 
         class _Graph:
             steps = n_steps
-            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc, self._readouts)   # what the captured kernels point at
+            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc, self._readouts, self.sensordata)   # what the captured kernels point at
 
             def replay(self_inner):
                 g.replay()
