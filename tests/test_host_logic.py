@@ -128,9 +128,14 @@ def test_bench_contract_and_execution_option_numbers():
     m = re.search(r"enum \{ TSIDB_OPT_SIM_WAVES = (\d+), TSIDB_OPT_LDS_PAD = (\d+), TSIDB_OPT_CU_SPLIT = (\d+), TSIDB_OPT_QP_FAST_EQ = (\d+) \}", hdr)
     assert m and [int(g) for g in m.groups()] == [1, 2, 3, 5]
     assert "TSIDB_OPT_SIM_PACK" not in hdr   # option 4 is retired with the packed sim kernel
-    wc_src = (ROOT / "tsid_control_amd" / "walk_controller.py").read_text()
-    assert "tsidb_set_option(self._h, 1, sw)" in wc_src and "tsidb_set_option(self._h, 5, fe)" in wc_src
-    assert not re.search(r"tsidb_set_option\(\s*self\._h\s*,\s*4\s*,", wc_src)
+    from tsid_control_amd import _lib
+    assert [_lib.OPT_SIM_WAVES, _lib.OPT_LDS_PAD, _lib.OPT_CU_SPLIT, _lib.OPT_QP_FAST_EQ] == [int(g) for g in m.groups()]
+    assert 4 not in [v for k, v in vars(_lib).items() if k.startswith("OPT_")]
+    # the facade passes options by those names only: never a literal number (so never the retired 4), in either spelling
+    passed = []
+    for f in ("walk_controller.py", "sim_pipeline.py"):
+        passed += re.findall(r"tsidb_[sg]et_option\W+(?:self\._h\s*,\s*)?([\w.]+)", (ROOT / "tsid_control_amd" / f).read_text())
+    assert set(passed) == {"_lib.OPT_SIM_WAVES", "_lib.OPT_QP_FAST_EQ", "_lib.OPT_CU_SPLIT"}, passed
     from tsid_control_amd import RobotConfig
     assert not hasattr(RobotConfig, "sim_pack")
     assert RobotConfig.qp_fast_equalities == -1 and RobotConfig.sim_waves == 0 and RobotConfig.pipeline_sim_batch == 0
@@ -141,6 +146,22 @@ def test_bench_contract_and_execution_option_numbers():
         v = t["valu"][k]
         assert 0.3 < 2.0 * v["issue_floor_cycles_per_env"] / (4.0 * v["wave_cycles_per_env"]) < 0.7
         assert 100.0 < v["launch_us_back_to_back"] < 200.0 and 0.8 < t[k]["bytes_per_launch"] / (4096 * 8 * (347 if k == "k_tick" else 185)) < 1.4
+
+
+def test_stream_table_close_spares_a_library_stream_somebody_still_holds():
+    """StreamTable.close() (WalkController.__del__): the HIP stream behind a wrapper that a caller or a captured graph
+    still holds is left alive, every other library stream is destroyed - the reference count it compares against is right
+    for where the table keeps its wrappers."""
+    from tsid_control_amd.sim_pipeline import StreamTable
+
+    class Wrapper:
+        pass
+    t = StreamTable("cuda:0")
+    t.streams, t.raw = [Wrapper(), Wrapper()], ["tick handle", "sim handle"]
+    held = t.streams[1]
+    destroyed = []
+    t.close(lambda name, hs: destroyed.append((name, hs)))
+    assert destroyed == [("tsidb_stream_destroy", "tick handle")] and t.streams == [] and t.raw == [] and held is not None
 
 
 def test_bench_dump_outputs(tmp_path):

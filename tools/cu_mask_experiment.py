@@ -58,7 +58,7 @@ sched = WalkSchedule.from_demo_paths(n, wc.conf, wc.device, wc.dtype, seed=1, q0
 with torch.cuda.stream(s_tick):
     wc._ensure_pipe()
     if s_sim is not None:
-        wc._pipe["stream"] = s_sim
+        wc._pipe.stream = s_sim
     for i in range(620):
         wc.step_pipelined(walk=(sched, wc.t))
     wc.sync_sim(); torch.cuda.synchronize()

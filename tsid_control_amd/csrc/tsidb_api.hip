@@ -961,6 +961,25 @@ static void upload_model(tsidb_ctx *h) {
   }                                      \
   return 0;
 
+// A library built without the sim stage refuses what needs it: true, with the message in h->err for the caller to return or
+// throw, if `wanted`.  `who` names the entry point ("tsidb_x: ").
+static bool lacks_sim(tsidb_ctx *h, bool wanted, const char *who, const char *advice = "") {
+  if (TOPO_HAS_SIM || !wanted) return false;
+  h->err = std::string(who) + "this library was built without the sim stage" + advice;
+  return true;
+}
+
+// Kernels in flight (the pipelined sim stage runs on a side stream) read the model constants: wait for the streams THIS handle
+// has launched on before the constants are replaced - not for the whole device (other handles, the caller's own work and
+// collectives keep running).  A stream the caller has destroyed since has nothing in flight: its error is dropped.  A handle
+// that has launched on more streams than it keeps track of waits for the whole device instead.
+static void wait_for_own_streams(tsidb_ctx *h) {
+  if (h->streams_overflow) HIP_OK(hipDeviceSynchronize());
+  else
+    for (hipStream_t st : h->used_streams)
+      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+}
+
 extern "C" int tsidb_set_env_params(tsidb_handle h, const void *env_params, const void *terrain) {
   if (!h) return -1;
   h->env_params = env_params; // NULL restores the nominal model
@@ -970,10 +989,7 @@ extern "C" int tsidb_set_env_params(tsidb_handle h, const void *env_params, cons
 
 extern "C" int tsidb_set_xfrc(tsidb_handle h, void *xfrc) {
   if (!h) return -1;
-  if (!TOPO_HAS_SIM && xfrc) {
-    h->err = "tsidb_set_xfrc: this library was built without the sim stage";
-    return 1;
-  }
+  if (lacks_sim(h, xfrc != nullptr, "tsidb_set_xfrc: ")) return 1;
   h->xfrc = xfrc; // NULL = no external wrenches
   return 0;
 }
@@ -981,10 +997,7 @@ extern "C" int tsidb_set_xfrc(tsidb_handle h, void *xfrc) {
 extern "C" int tsidb_set_sim_readouts(tsidb_handle h, void *con_force, void *con_frame, void *con_pos, void *act_force, void *foot_grf) {
   if (!h) return -1;
   void *const p[5] = {con_force, con_frame, con_pos, act_force, foot_grf};
-  if (!TOPO_HAS_SIM && (con_force || con_frame || con_pos || act_force || foot_grf)) {
-    h->err = "tsidb_set_sim_readouts: this library was built without the sim stage";
-    return 1;
-  }
+  if (lacks_sim(h, con_force || con_frame || con_pos || act_force || foot_grf, "tsidb_set_sim_readouts: ")) return 1;
   for (int i = 0; i < 5; i++) h->ro[i] = p[i]; // all NULL = no readouts
   return 0;
 }
@@ -1063,7 +1076,7 @@ static auto sim_kernel(const tsidb_ctx *h, int B, bool motor_tau) {
 // B sim steps in one launch, step b driven by slot slots[b] of the [K, N, NQ] / [K, N, NV] rings q_ring / v_ring (slot 0 if NULL)
 static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ring, const int32_t *slots, void *qpos, void *qvel, void *qacc_ws,
                        void *qacc, int32_t *ncon, int32_t *con, int32_t *info, hipStream_t s, const void *motor_tau = nullptr) {
-  if (!TOPO_HAS_SIM) throw std::string("this library was built without the sim stage");
+  if (lacks_sim(h, true, "")) throw h->err;
   if (B < 1 || B > TSIDB_MAX_SIM_BATCH) throw std::string("sim batch must be 1 .. TSIDB_MAX_SIM_BATCH steps");
   h->note_stream(s);
   unsigned long long slot_bits = 0;
@@ -1125,7 +1138,7 @@ int tsidb_create(const void *model_blob, size_t nbytes, const double *params, in
                             "the blob's topology header, -DTSIDB_TOPOLOGY_HEADER)");
     }
     h->params.assign(params, params + n_params);
-    if (!TOPO_HAS_SIM && h->params[P_SIM_ENABLED] != 0.0) throw std::string("this library was built without the sim stage: set sim_enabled = False");
+    if (lacks_sim(h, h->params[P_SIM_ENABLED] != 0.0, "", ": set sim_enabled = False")) throw h->err;
     int ndev = 0;
     HIP_OK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) throw std::string("no such HIP device (this library has no CPU path)");
@@ -1166,14 +1179,7 @@ int tsidb_set_params(tsidb_handle h, const double *params, int n_params) {
   GUARD_BEGIN
   if (!params || n_params != P_COUNT) throw std::string("params must hold TSIDB_P_COUNT doubles");
   h->params.assign(params, params + n_params);
-  // kernels in flight (the pipelined sim stage runs on a side stream) read the model constants: wait for the streams THIS
-  // handle has launched on before the constants are replaced - not for the whole device (other handles, the caller's own
-  // work and collectives keep running).  A stream the caller has destroyed since has nothing in flight: its error is dropped.
-  // A handle that has launched on more streams than it keeps track of waits for the whole device instead.
-  if (h->streams_overflow) HIP_OK(hipDeviceSynchronize());
-  else
-    for (hipStream_t st : h->used_streams)
-      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+  wait_for_own_streams(h);
   with_dtype(h->dtype, [&](auto t) { upload_model<decltype(t)>(h); });
   GUARD_END
 }
@@ -1181,7 +1187,7 @@ int tsidb_set_params(tsidb_handle h, const double *params, int n_params) {
 int tsidb_set_sensors(tsidb_handle h, int n_sites, const int32_t *site_body, const double *site_pos, const double *site_quat,
                       void *sensordata) {
   GUARD_BEGIN
-  if (!TOPO_HAS_SIM && (n_sites || sensordata)) throw std::string("tsidb_set_sensors: this library was built without the sim stage");
+  if (lacks_sim(h, n_sites || sensordata, "tsidb_set_sensors: ")) throw h->err;
   if (n_sites < 0 || n_sites > TSIDB_MAXSITE) throw std::string("tsidb_set_sensors: n_sites must be 0 .. TSIDB_MAXSITE");
   if ((n_sites == 0) != (sensordata == nullptr)) throw std::string("tsidb_set_sensors: sites without a buffer, or a buffer without sites");
   if (n_sites && (!site_body || !site_pos || !site_quat)) throw std::string("tsidb_set_sensors: null site table");
@@ -1201,11 +1207,7 @@ int tsidb_set_sensors(tsidb_handle h, int n_sites, const int32_t *site_body, con
                           2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
     memcpy(R[s], Rs, sizeof Rs);
   }
-  // the site table is part of the model constants: wait for the kernels in flight, as tsidb_set_params does
-  if (h->streams_overflow) HIP_OK(hipDeviceSynchronize());
-  else
-    for (hipStream_t st : h->used_streams)
-      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+  wait_for_own_streams(h); // (the site table is part of the model constants)
   h->n_sites = n_sites;
   for (int s = 0; s < n_sites; s++) {
     h->site_body[s] = site_body[s];

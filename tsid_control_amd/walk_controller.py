@@ -12,7 +12,6 @@ TaskActuationBounds, TaskJointBounds, SolverHQuadProgFast.  The `formulation`, `
 objects of the reference have no counterpart - their work happens inside `step()`.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -21,8 +20,9 @@ from . import _lib
 from .conf import RobotConfig
 from .model import ModelBlob
 from .params import P_COUNT, pack_params
+from .sim_pipeline import SimPipeline, StreamTable, streams_overlap
 
-NQ, NV, NA, NOBS, NROW, MAXCON = 27, 26, 20, 65, 67, 32
+MAXCON = 32
 
 
 def _ptr(t):
@@ -58,10 +58,12 @@ class WalkController:
         NOBS, NROW = NQ + NV + 12, NQ + NV + 14
         self.NQ, self.NV, self.NA, self.NOBS, self.NROW = NQ, NV, NA, NOBS, NROW
         self._h = C.c_void_p()
+        self._pipe = None                        # the SimPipeline of step_pipelined(), made on first use
+        self._streams = StreamTable(self.device)   # tick_stream and its sim stream
+        self._geom_body = None
         raw = self.model.raw
-        rc = L.tsidb_create(raw, len(raw), self.params.ctypes.data_as(C.c_void_p), P_COUNT, N, self.device.index,
-                            0 if dt_name == "f64" else 1, C.byref(self._h))
-        _lib.check(L, self._h, rc, "tsidb_create")
+        self._check(L.tsidb_create(raw, len(raw), self.params.ctypes.data_as(C.c_void_p), P_COUNT, N, self.device.index,
+                                   0 if dt_name == "f64" else 1, C.byref(self._h)), "tsidb_create")
 
         z = lambda *s, dt=self.dtype: torch.zeros(*s, dtype=dt, device=self.device)
         # TSID state (WalkController.py:23-24) and sim state (main.py:51,64)
@@ -88,17 +90,16 @@ class WalkController:
         self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
         self.sensordata = None   # site sensors [N, S, 24] (enable_sensors); None = none registered
         self.framepos = self.framequat = self.framelinvel = self.frameangvel = self.velocimeter = self.gyro = self.accelerometer = None
-        rc = L.tsidb_set_refs(self._h, _ptr(self.com_ref), _ptr(self.posture_ref), _ptr(self.foot_ref),
-                              _ptr(self.contact_ref), _ptr(self.contact_active), _ptr(self.cop_frames))
-        _lib.check(L, self._h, rc, "tsidb_set_refs")
+        self._call("tsidb_set_refs", _ptr(self.com_ref), _ptr(self.posture_ref), _ptr(self.foot_ref), _ptr(self.contact_ref),
+                   _ptr(self.contact_active), _ptr(self.cop_frames))
         sw = int(getattr(conf, "sim_waves", 0))   # 0 = the library's choice (2 wavefronts per env up to 512 envs, else 1)
         if sw:
-            _lib.check(L, self._h, L.tsidb_set_option(self._h, 1, sw), "tsidb_set_option(sim_waves)")
+            self._call("tsidb_set_option", _lib.OPT_SIM_WAVES, sw)
         fe = int(getattr(conf, "qp_fast_equalities", -1))   # -1 = the library's default (on)
         if fe >= 0:
-            _lib.check(L, self._h, L.tsidb_set_option(self._h, 5, fe), "tsidb_set_option(qp_fast_eq)")
+            self._call("tsidb_set_option", _lib.OPT_QP_FAST_EQ, fe)
         self.cop_ref = z(N, 3)   # reference of the CoP force task (legacy/biped.py:79-80; conf.w_cop)
-        _lib.check(L, self._h, L.tsidb_set_cop_ref(self._h, _ptr(self.cop_ref)), "tsidb_set_cop_ref")
+        self._call("tsidb_set_cop_ref", _ptr(self.cop_ref))
 
         # WalkController.py:168-169,179-180
         self.tau_max = conf.tau_max_scaling * self.model.effort_limit
@@ -118,14 +119,8 @@ class WalkController:
     def __del__(self):
         try:
             if self._h:
-                import sys
                 self._pipe = None    # (its reference to the sim stream's wrapper is ours, not a caller's)
-                for ext, hs in getattr(self, "_streams", {}).values():
-                    # a caller (or a captured graph's keep list) may still hold the ExternalStream wrapper of a library
-                    # stream: then the HIP stream is left alive (a leaked stream is harmless, a dangling one is not)
-                    if hs is not None and sys.getrefcount(ext) <= 3:
-                        self._L.tsidb_stream_destroy(self._h, hs)
-                self._streams = {}
+                self._streams.close(self._call)
                 self._L.tsidb_destroy(self._h)
                 self._h = C.c_void_p()
         except Exception:
@@ -134,6 +129,41 @@ class WalkController:
     # ------------------------------------------------------------------ helpers
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check(self, rc, what):
+        _lib.check(self._L, self._h, rc, what)
+
+    def _call(self, name, *args):
+        """The one path into the library: self._L.<name>(self._h, *args) with self.device current; raises TsidbError with
+        the library's message when the call fails."""
+        with torch.cuda.device(self.device):
+            rc = getattr(self._L, name)(self._h, *args)
+        if rc:
+            self._check(rc, name)
+
+    def _buffer(self, method, arg, shape, t=None):
+        """A caller's tensor to use in place - it must be contiguous, of `shape` and self.dtype, on self.device - or a new
+        zero tensor if t is None."""
+        if t is None:
+            return torch.zeros(*shape, dtype=self.dtype, device=self.device)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device \
+                or not t.is_contiguous():
+            what = (tuple(t.shape), t.dtype, t.device, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)
+            raise _lib.TsidbError(f"{method}: {arg} must be a contiguous {shape} {self.dtype} tensor on {self.device}, got {what}")
+        return t
+
+    def _written(self, sched=None):
+        """Every tensor a tick or a sim step writes, for what is registered now (with a schedule: its touch-down latch too):
+        what capture_steps() rewinds after its warm-up and a captured graph keeps alive.  A new optional buffer goes HERE."""
+        yield from (self.q, self.v, self.qpos, self.qvel, self.qacc_warmstart, self.com_ref, self.posture_ref, self.foot_ref,
+                    self.contact_ref, self.contact_active, self.frames, self.rows, self.tau, self.dv, self.f, self.status, self.ncon,
+                    self.con_pairs, self.info, self.cop_ref)
+        if self._readouts is not None:
+            yield from self._readouts.values()
+        if self.sensordata is not None:
+            yield self.sensordata
+        if sched is not None and sched.td_latch is not None:
+            yield sched.td_latch
 
     @property
     def contactLF_active(self):
@@ -147,8 +177,7 @@ class WalkController:
         """Re-read self.conf (edited RobotConfig values) into the device-side constants."""
         self.sync_sim()  # sim stages step_pipelined() has not launched yet belong to the OLD constants: run them first
         self.params = pack_params(self.conf, self.model.effort_limit, self.model.velocity_limit)
-        rc = self._L.tsidb_set_params(self._h, self.params.ctypes.data_as(C.c_void_p), P_COUNT)
-        _lib.check(self._L, self._h, rc, "tsidb_set_params")
+        self._call("tsidb_set_params", self.params.ctypes.data_as(C.c_void_p), P_COUNT)
 
     def set_env_params(self, mass_scale=None, friction=None, floor_normal=None, floor_offset=None, terrain=None):
         """Per-env randomisation of the sim stage (BASELINE config 5; no reference counterpart): any
@@ -183,8 +212,7 @@ class WalkController:
             tr[:, 3] = 1.0 / torch.as_tensor(terrain["step_length"], dtype=torch.float64)
             tr[:, 4:] = torch.as_tensor(terrain["heights"], dtype=torch.float64).reshape(N, 16)
             self.terrain = tr.to(self.device, self.dtype).contiguous()
-        rc = self._L.tsidb_set_env_params(self._h, _ptr(self.env_params), _ptr(self.terrain))
-        _lib.check(self._L, self._h, rc, "tsidb_set_env_params")
+        self._call("tsidb_set_env_params", _ptr(self.env_params), _ptr(self.terrain))
 
     # ------------------------------------------------------------------ external wrenches (push recovery)
     def set_xfrc(self, t=None):
@@ -196,12 +224,8 @@ class WalkController:
         first, as the methods here do: a sim stage left unlaunched would otherwise read the new values."""
         self.sync_sim()   # sim stages step_pipelined() has not launched yet belong to the old wrenches
         if t is not None:
-            shape = (self.num_envs, self.NB, 6)
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device \
-                    or not t.is_contiguous():
-                what = (tuple(t.shape), t.dtype, t.device, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)
-                raise _lib.TsidbError(f"set_xfrc: need a contiguous {shape} {self.dtype} tensor on {self.device}, got {what}")
-        _lib.check(self._L, self._h, self._L.tsidb_set_xfrc(self._h, _ptr(t)), "tsidb_set_xfrc")
+            self._buffer("set_xfrc", "t", (self.num_envs, self.NB, 6), t)
+        self._call("tsidb_set_xfrc", _ptr(t))
         self.xfrc = t
 
     def _xfrc_rows(self, env_ids):
@@ -253,19 +277,8 @@ class WalkController:
         want = dict(con_force=(N, MAXCON, 6), con_frame=(N, MAXCON, 9), con_pos=(N, MAXCON, 4), actuator_force=(N, self.NA),
                     foot_grf=(N, 2, 6))
         given = dict(con_force=con_force, con_frame=con_frame, con_pos=con_pos, actuator_force=actuator_force, foot_grf=foot_grf)
-        bufs = {}
-        for k, shape in want.items():
-            t = given[k]
-            if t is None:
-                t = torch.zeros(*shape, dtype=self.dtype, device=self.device)
-            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device \
-                    or not t.is_contiguous():
-                what = (tuple(t.shape), t.dtype, t.device, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)
-                raise _lib.TsidbError(f"enable_sim_readouts: {k} must be a contiguous {shape} {self.dtype} tensor on {self.device}, "
-                                      f"got {what}")
-            bufs[k] = t
-        rc = self._L.tsidb_set_sim_readouts(self._h, *(_ptr(bufs[k]) for k in want))
-        _lib.check(self._L, self._h, rc, "tsidb_set_sim_readouts")
+        bufs = {k: self._buffer("enable_sim_readouts", k, shape, given[k]) for k, shape in want.items()}
+        self._call("tsidb_set_sim_readouts", *(_ptr(bufs[k]) for k in want))
         self._readouts = bufs
         self.con_force, self.actuator_force = bufs["con_force"], bufs["actuator_force"]
         self.con_frame = bufs["con_frame"].view(N, MAXCON, 3, 3)
@@ -275,7 +288,7 @@ class WalkController:
     def disable_sim_readouts(self):
         """Unregister the readouts: the sim stage runs its kernels without them again (bit-identical state)."""
         self.sync_sim()
-        _lib.check(self._L, self._h, self._L.tsidb_set_sim_readouts(self._h, None, None, None, None, None), "tsidb_set_sim_readouts")
+        self._call("tsidb_set_sim_readouts", None, None, None, None, None)
         self._readouts = None
         self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
 
@@ -311,16 +324,9 @@ class WalkController:
         for i, st in enumerate(sites):
             b, p, q = self._named_site(st) if isinstance(st, str) else st
             body[i], pos[i], quat[i] = int(b), np.asarray(p, dtype=np.float64).reshape(3), np.asarray(q, dtype=np.float64).reshape(4)
-        shape = (N, S, 24)
-        if out is None:
-            out = torch.zeros(*shape, dtype=self.dtype, device=self.device)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != self.dtype or out.device != self.device \
-                or not out.is_contiguous():
-            what = (tuple(out.shape), out.dtype, out.device, out.is_contiguous()) if isinstance(out, torch.Tensor) else type(out)
-            raise _lib.TsidbError(f"enable_sensors: out must be a contiguous {shape} {self.dtype} tensor on {self.device}, got {what}")
+        out = self._buffer("enable_sensors", "out", (N, S, 24), out)
         vp = C.c_void_p
-        rc = self._L.tsidb_set_sensors(self._h, S, body.ctypes.data_as(vp), pos.ctypes.data_as(vp), quat.ctypes.data_as(vp), _ptr(out))
-        _lib.check(self._L, self._h, rc, "tsidb_set_sensors")
+        self._call("tsidb_set_sensors", S, body.ctypes.data_as(vp), pos.ctypes.data_as(vp), quat.ctypes.data_as(vp), _ptr(out))
         self.sensordata = out
         for k, (a, b) in self.SENSOR_COLUMNS.items():
             setattr(self, k, out[:, :, a:b])
@@ -328,7 +334,7 @@ class WalkController:
     def disable_sensors(self):
         """Unregister the site sensors: the sim stage runs its kernels without them again (bit-identical state)."""
         self.sync_sim()
-        _lib.check(self._L, self._h, self._L.tsidb_set_sensors(self._h, 0, None, None, None, None), "tsidb_set_sensors")
+        self._call("tsidb_set_sensors", 0, None, None, None, None)
         self.sensordata = None
         for k in self.SENSOR_COLUMNS:
             setattr(self, k, None)
@@ -336,7 +342,7 @@ class WalkController:
     def sim_cop(self):
         """[N, 3] centre of pressure the sim realised on the floor: both soles' CoPs weighted by their normal force (the floor
         normal of set_env_params, else +z) - the counterpart of get_cop().  NaN where neither sole carries a normal force."""
-        if getattr(self, "_readouts", None) is None:
+        if self._readouts is None:
             raise _lib.TsidbError("sim_cop needs enable_sim_readouts()")
         nrm = self.env_params[:, 2:5] if self.env_params is not None else \
             torch.tensor([0.0, 0.0, 1.0], dtype=self.dtype, device=self.device).expand(self.num_envs, 3)
@@ -348,7 +354,7 @@ class WalkController:
     def contact_bodies(self):
         """[N, 32, 2] int32 (body1, body2) of each row of con_pairs: sim bodies (the blob's order, 0 = torso) of geom1 and
         geom2 (mj_data.contact.geom -> mj_geom_body); the floor is -1.  Rows >= ncon are (-1, -1)."""
-        gb = getattr(self, "_geom_body", None)
+        gb = self._geom_body
         if gb is None:
             gb = self._geom_body = torch.as_tensor(np.asarray(self.model["mj_geom_body"], dtype=np.int64), device=self.device)
         cp = self.con_pairs.long()
@@ -405,7 +411,7 @@ class WalkController:
         if new is not None:
             self.posture_ref += new
         self.posture_bias = new
-        _lib.check(self._L, self._h, self._L.tsidb_set_posture_bias(self._h, _ptr(new)), "tsidb_set_posture_bias")
+        self._call("tsidb_set_posture_bias", _ptr(new))
 
     def reset_done(self, sched=None, t=None, new_paths=True):
         """Episode lifecycle on the device: reset every env whose done flag (self.done, written by the last tick) is set -
@@ -413,10 +419,8 @@ class WalkController:
         when new_paths) and restart its clock at time t (default self.t, the time of the next tick).  Nothing comes back
         to the host; envs that are not done are untouched."""
         self.sync_sim()
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_reset_done(self._h, _ptr(self.rows), self.NROW, _ptr(self.q), _ptr(self.v), _ptr(self.qpos),
-                                          _ptr(self.qvel), _ptr(self.qacc_warmstart), _ptr(self.frames), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_reset_done")
+        self._call("tsidb_reset_done", _ptr(self.rows), self.NROW, _ptr(self.q), _ptr(self.v), _ptr(self.qpos), _ptr(self.qvel),
+                   _ptr(self.qacc_warmstart), _ptr(self.frames), self._stream())
         if sched is not None:
             sched.plan(self, t=self.t if t is None else t, done_only=True, new_paths=new_paths)
 
@@ -433,10 +437,8 @@ class WalkController:
             n_ids = ids.numel()
             if n_ids == 0:
                 return  # nothing to reset (the C entry point reads a NULL id list as "every env")
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_reset(self._h, _ptr(ids), n_ids, _ptr(self.q), _ptr(self.v), _ptr(self.qpos),
-                                     _ptr(self.qvel), _ptr(self.qacc_warmstart), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_reset")
+        self._call("tsidb_reset", _ptr(ids), n_ids, _ptr(self.q), _ptr(self.v), _ptr(self.qpos), _ptr(self.qvel),
+                   _ptr(self.qacc_warmstart), self._stream())
         if env_ids is None:
             self.frames.copy_(self.cop_frames)
             self.t = 0.0
@@ -450,12 +452,9 @@ class WalkController:
         teleport + joint targets + sim step (main.py:192-195).  Returns (tau, q, v, status, obs);
         all are views of the controller's tensors, updated in place."""
         self.sync_sim()
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_step(self._h, _ptr(self.q), _ptr(self.v), _ptr(self.qpos), _ptr(self.qvel),
-                                    _ptr(self.qacc_warmstart), _ptr(self.tau), _ptr(self.dv), _ptr(self.f),
-                                    _ptr(self.status), _ptr(self.rows), self.NROW, _ptr(self.frames), _ptr(self.ncon),
-                                    _ptr(self.con_pairs), _ptr(self.info), int(n_substeps), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_step")
+        self._call("tsidb_step", _ptr(self.q), _ptr(self.v), _ptr(self.qpos), _ptr(self.qvel), _ptr(self.qacc_warmstart),
+                   _ptr(self.tau), _ptr(self.dv), _ptr(self.f), _ptr(self.status), _ptr(self.rows), self.NROW, _ptr(self.frames),
+                   _ptr(self.ncon), _ptr(self.con_pairs), _ptr(self.info), int(n_substeps), self._stream())
         self.t += n_substeps * self.conf.dt
         return self.tau, self.q, self.v, self.status, self.obs
 
@@ -477,98 +476,27 @@ class WalkController:
         if getattr(self.conf, "closed_loop", False) or not getattr(self.conf, "sim_enabled", True):
             raise _lib.TsidbError("step_pipelined needs the open-loop sim stage (closed loop: the tick reads the sim state)")
         cur = torch.cuda.current_stream(self.device)
-        self._ensure_pipe()
-        P = self._pipe
-        par = P["par"]
-        P["par"] = (par + 1) % len(P["q"])
-        ev = P["done"][par]                    # the sim batch that read this slot 2 * sim_batch steps ago
-        lw = P.get("last_wait")
-        if ev is not None and not (lw is not None and lw[0] == cur.cuda_stream and lw[1] is ev):
-            # (once per batch: the slots of one batch share its event, and a cross-stream wait is a barrier packet that costs
-            #  the tick stream ~10 us each - at 512 envs a fifth of the step when it was issued before every tick)
-            if torch.cuda.is_current_stream_capturing() or not ev.query():   # (already complete: no packet)
-                cur.wait_event(ev)
-            P["last_wait"] = (cur.cuda_stream, ev)   # (the reference keeps the event alive: no id reuse)
+        P = self._ensure_pipe()
+        slot = P.next_slot(cur)                # (waits for the sim batch that read this slot 2 * sim_batch steps ago)
         if events:
             events[0].record(cur)
         # the tick writes the TSID state it ends on into the slot as well (two copy kernels less on this stream); walk =
         # (schedule, t): the walking reference update of this tick in the same launch
-        self.tick(walk=walk, _snap=(P["q"][par], P["v"][par]))
+        self.tick(walk=walk, _snap=(P.q[slot], P.v[slot]))
         if events:
             events[1].record(cur)
-        P["pending"].append(par)
+        P.pending.append(slot)
         # conf.pipeline_sim_batch > 1 enqueues the sim stages that many at a time, as one launch (one cross-stream wait and one
         # record per batch instead of per step, no launch gaps; the sim state then lags the tick by up to that many steps
         # until sync_sim()).  Measured (DESIGN.md section 5 "Streams"): no gain from 2048 envs on; 512 / 1024 walkers +25-30 %
         # together with the fused tick launch (8 at a time, the default for up to 1024 envs).
-        if len(P["pending"]) >= self.sim_batch or events:
-            self._flush_sims(events)
+        if len(P.pending) >= self.sim_batch or events:
+            P.flush(cur, self._sim_batch, events)
         self.t += self.conf.dt
         return self.tau, self.q, self.v, self.status, self.obs
 
-    def _streams_overlap(self, sa, sb):
-        """True if work on the two streams really runs concurrently.  HIP multiplexes its streams onto a few hardware queues
-        (GPU_MAX_HW_QUEUES, 4 by default) and two streams - even two created one after the other - can share one, in which
-        case tick and sim run one after the other and the pipelined step loses its overlap without any error
-        (tools/stream_overlap_probe.py).  Probe: a short device-side spin on each, timed together against one alone."""
-        if os.environ.get("TSIDB_NO_STREAM_PROBE") == "1" or not hasattr(torch.cuda, "_sleep") or torch.cuda.is_current_stream_capturing():
-            return True
-        import time
-        try:
-            def spin(streams, cycles=600000):   # ~0.25 ms at 2.4 GHz
-                torch.cuda.synchronize(self.device)
-                t0 = time.perf_counter()
-                for st in streams:
-                    with torch.cuda.stream(st):
-                        torch.cuda._sleep(cycles)
-                for st in streams:
-                    st.synchronize()
-                return time.perf_counter() - t0
-            spin([sa, sb], 1000)                 # (first use of the kernel on these streams)
-            one = min(spin([sa]), spin([sb]))
-            both = min(spin([sa, sb]), spin([sa, sb]))
-            return both < 1.6 * one
-        except Exception:
-            return True
-
-    def _lib_stream(self, role):
-        """tsidb_stream_create: the stream the library recommends for the tick (role 0) / the sim (role 1) of the pipelined
-        step - on disjoint halves of the CUs for up to 512 envs (include/tsidb.h), plain streams above"""
-        st = getattr(self, "_streams", None)
-        if st is None:
-            st = self._streams = {}
-        if role not in st:
-            split = C.c_int(0)
-            _lib.check(self._L, self._h, self._L.tsidb_get_option(self._h, 3, C.byref(split)), "tsidb_get_option(cu_split)")
-            for r in (0, 1):   # (both at once)
-                if split.value:
-                    hs = C.c_void_p()
-                    _lib.check(self._L, self._h, self._L.tsidb_stream_create(self._h, r, C.byref(hs)), "tsidb_stream_create")
-                    st[r] = (torch.cuda.ExternalStream(hs.value, device=self.device), hs)
-                else:
-                    st[r] = (torch.cuda.Stream(device=self.device), None)   # no CU split for this batch size: torch's pool
-            ok = False
-            for _ in range(6):                   # a pair that shares a hardware queue would serialise tick and sim
-                if self._streams_overlap(st[0][0], st[1][0]):
-                    ok = True
-                    break
-                if st[0][1] is not None or st[1][1] is not None:
-                    # the CU-masked pair does not overlap: give up the split for BOTH roles (a tick confined to half the
-                    # CUs beside a sim that spans all of them is a silent regression) and say so
-                    import warnings
-                    warnings.warn("tsid_control_amd: the CU-masked tick / sim streams do not run concurrently on this device; "
-                                  "using ordinary streams for both (no CU split)")
-                    for r in (0, 1):
-                        if st[r][1] is not None:
-                            self._L.tsidb_stream_destroy(self._h, st[r][1])
-                        st[r] = (torch.cuda.Stream(device=self.device), None)
-                else:
-                    st[1] = (torch.cuda.Stream(device=self.device), None)
-            if not ok and not self._streams_overlap(st[0][0], st[1][0]):
-                import warnings
-                warnings.warn("tsid_control_amd: no pair of HIP streams that runs concurrently was found (they share a hardware "
-                              "queue): the pipelined step will run tick and sim one after the other")
-        return st[role][0]
+    def _streams_overlap(self, sa, sb):   # bench.py places its collective's stream with it
+        return streams_overlap(self.device, sa, sb)
 
     @property
     def tick_stream(self):
@@ -577,41 +505,16 @@ class WalkController:
         down by a quarter when they share CU groups: +11-14 % env-steps/s at 256 / 512 envs); otherwise an ordinary stream.
         Optional - step_pipelined() works on any current stream; the sim stream is paired with this one only if the FIRST
         step_pipelined() runs on it."""
-        return self._lib_stream(0)
+        return self._streams.get(_lib.ROLE_TICK, self._call)
 
     def _ensure_pipe(self):
-        """the second stream and the ring of snapshot slots step_pipelined() hands the TSID state to the sim stages through;
-        (re)built when missing or too small for the current sim batch"""
+        """the SimPipeline (sim_pipeline.py: the second stream and the ring of snapshot slots) of step_pipelined(); (re)built
+        when missing or too small for the current sim batch"""
         need = min(16, max(4, 2 * self.sim_batch))
-        P = getattr(self, "_pipe", None)
-        if P is not None and len(P["q"]) >= need:
-            return
-        if P is not None:
+        if self._pipe is None or len(self._pipe.q) < need:
             self.sync_sim()                     # nothing may be pending in the ring that is replaced
-        # ring of snapshot slots: the tick writes its slot itself, so it must wait for the sim that read the slot
-        # K steps ago BEFORE it starts - with only two slots that wait held tick(t) back until sim(t - 2) was done
-        # and cost 12 % at 4096 envs; four slots and the tick stream runs ahead as before
-        # (never fewer than two batches of slots: a tick must not overwrite a snapshot whose sim is still pending; the
-        #  library numbers slots 0 .. 15)
-        K = need
-        qring = torch.empty(K, *self.q.shape, dtype=self.dtype, device=self.device)   # one allocation: a batch of sim
-        vring = torch.empty(K, *self.v.shape, dtype=self.dtype, device=self.device)   # stages names its slots by number
-        # the sim stream: the library's (on the other half of the CUs for up to 512 envs) when the loop runs on
-        # self.tick_stream, an ordinary one otherwise - a CU-masked stream is a BLOCKING stream (hipExtStreamCreateWithCUMask
-        # takes no flags), and beside work on the legacy default stream it would serialise with it
-        ts = getattr(self, "_streams", {}).get(0)
-        on_tick = ts is not None and torch.cuda.current_stream(self.device).cuda_stream == ts[0].cuda_stream
-        if on_tick:
-            sim_stream = self._lib_stream(1)
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            for _ in range(6):                   # (a stream that shares the current one's hardware queue would serialise)
-                sim_stream = torch.cuda.Stream(device=self.device)
-                if self._streams_overlap(cur, sim_stream):
-                    break
-        self._pipe = dict(stream=sim_stream,
-                          par=0, done=[None] * K, pending=[], qring=qring, vring=vring,
-                          q=[qring[k] for k in range(K)], v=[vring[k] for k in range(K)])
+            self._pipe = SimPipeline(self._streams.sim_stream_for(torch.cuda.current_stream(self.device)), self.q, self.v, need)
+        return self._pipe
 
     def gather_rows(self, out=None):
         """[N, 67] = obs, reward, done of the last tick: the per-env row the multi-GPU all-gather carries."""
@@ -636,18 +539,14 @@ class WalkController:
             raise _lib.TsidbError("capture_steps uses the open-loop pipeline (step_pipelined)")
         dt = self.conf.dt
         self.sync_sim()   # the state saved below must include the sim stage a previous step_pipelined() left in flight
-        self._ensure_pipe()   # (the ring sized for the eager batch: it is not rebuilt, and the graph's pointers stay valid, afterwards)
+        P = self._ensure_pipe()   # (the ring sized for the eager batch: it is not rebuilt, and the graph's pointers stay valid, afterwards)
         batch_keep = self.sim_batch
         if sim_batch is not None:
-            self.sim_batch = max(1, min(int(sim_batch), len(self._pipe["q"]) // 2))
+            self.sim_batch = max(1, min(int(sim_batch), len(P.q) // 2))
         self.t_device = torch.full((1,), self.t, dtype=torch.float64, device=self.device)   # float64 whatever the path's dtype
         # warm up outside the capture (lazy kernel loads, cached contiguous tables), then rewind the state
-        keep = {k: getattr(self, k).clone() for k in ("q", "v", "qpos", "qvel", "qacc_warmstart", "com_ref", "posture_ref",
-                                                      "foot_ref", "contact_ref", "contact_active", "frames", "rows", "tau", "dv", "f",
-                                                      "status", "ncon", "con_pairs", "info", "cop_ref")}
-        ro_keep = {k: t.clone() for k, t in self._readouts.items()} if self._readouts is not None else {}
-        sens_keep = self.sensordata.clone() if self.sensordata is not None else None
-        latch_keep = sched.td_latch.clone() if sched is not None and sched.td_latch is not None else None
+        written = list(self._written(sched))
+        saved = [t.clone() for t in written]
         t_keep = self.t
         if sched is not None:
             sched.apply(self, self.t, t_device=self.t_device)
@@ -655,27 +554,18 @@ class WalkController:
         self.t_device += dt
         self.sync_sim()
         torch.cuda.synchronize(self.device)
-        for k, v in keep.items():
-            getattr(self, k).copy_(v)
-        for k, v in ro_keep.items():
-            self._readouts[k].copy_(v)
-        if sens_keep is not None:
-            self.sensordata.copy_(sens_keep)
-        if latch_keep is not None:
-            sched.td_latch.copy_(latch_keep)
+        for t, s in zip(written, saved):
+            t.copy_(s)
         self.t = t_keep
         self.t_device.fill_(self.t)
-        self._pipe["done"] = [None] * len(self._pipe["q"])   # no event from outside the capture may be waited on inside it
-        self._pipe["par"] = 0
-        self._pipe["last_wait"] = None
+        P.forget_events()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for _ in range(n_steps):
                 self.step_pipelined(walk=(sched, 0.0, self.t_device) if sched is not None else None)
                 self.t_device += dt
             self.sync_sim()                 # join the sim stream: the graph ends with every kernel done
-        self._pipe["done"] = [None] * len(self._pipe["q"])
-        self._pipe["last_wait"] = None
+        P.forget_events()
         self.sim_batch = batch_keep
         self.t = t_keep                     # the capture advanced the host clock without running anything
 
@@ -683,7 +573,7 @@ class WalkController:
 
         class _Graph:
             steps = n_steps
-            keep = (self._pipe["qring"], self._pipe["vring"], self._pipe["stream"], self.xfrc, self._readouts, self.sensordata)   # what the captured kernels point at
+            keep = (P.qring, P.vring, P.stream, self.xfrc, *written)   # what the captured kernels point at
 
             def replay(self_inner):
                 g.replay()
@@ -692,68 +582,33 @@ class WalkController:
 
         return _Graph()
 
-    def _flush_sims(self, events=None):
-        """enqueue the sim stages of the ticks step_pipelined() has run since the last flush (oldest first)"""
-        P = self._pipe
-        if not P["pending"]:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        with torch.cuda.stream(P["stream"]):
-            P["stream"].wait_event(ready)
-            pend = list(P["pending"])
-            if events:                       # timing events bracket the last sim step alone
-                head, pend = pend[:-1], pend[-1:]
-                if head:
-                    self._sim_batch(head)
-                events[2].record(P["stream"])
-            self._sim_batch(pend)
-            if events:
-                events[3].record(P["stream"])
-            done = torch.cuda.Event()
-            done.record(P["stream"])
-        for slot in P["pending"]:
-            P["done"][slot] = done
-        P["pending"] = []
-
     def _sim_batch(self, slots):
         """the sim stages of several ticks in ONE launch (tsidb_sim_batch): each env steps len(slots) times, teleporting to
         the snapshot of its tick each time - no launch gaps between the steps"""
-        B = len(slots)
+        B, P = len(slots), self._pipe
         if B == 1:
-            self.sim_step(q_tsid=self._pipe["q"][slots[0]], v_tsid=self._pipe["v"][slots[0]], _from_pipe=True)
+            self.sim_step(q_tsid=P.q[slots[0]], v_tsid=P.v[slots[0]], _from_pipe=True)
             return
-        sl = (C.c_int32 * B)(*slots)
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_sim_batch(self._h, B, _ptr(self._pipe["qring"]), _ptr(self._pipe["vring"]), sl, _ptr(self.qpos),
-                                         _ptr(self.qvel), _ptr(self.qacc_warmstart), None, _ptr(self.ncon), _ptr(self.con_pairs),
-                                         _ptr(self.info), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_sim_batch")
+        self._call("tsidb_sim_batch", B, _ptr(P.qring), _ptr(P.vring), (C.c_int32 * B)(*slots), _ptr(self.qpos), _ptr(self.qvel),
+                   _ptr(self.qacc_warmstart), None, _ptr(self.ncon), _ptr(self.con_pairs), _ptr(self.info), self._stream())
 
     def sync_sim(self):
         """Make the current stream wait for the sim stages step_pipelined() left in flight (or not yet enqueued)."""
-        P = getattr(self, "_pipe", None)
-        if P is not None:
-            self._flush_sims()
-            torch.cuda.current_stream(self.device).wait_stream(P["stream"])
+        if self._pipe is not None:
+            self._pipe.join(torch.cuda.current_stream(self.device), self._sim_batch)
 
     def tick(self, walk=None, _snap=None):
         """TSID stage only (main.py:119-129).  walk = (schedule, t): that tick's walking reference update
         (WalkSchedule.apply(self, t)) runs in the same launch, ahead of the tick (tsidb_tick_walk) - same results."""
         if walk is None and _snap is None:
-            with torch.cuda.device(self.device):
-                rc = self._L.tsidb_tick(self._h, _ptr(self.q), _ptr(self.v), _ptr(self.tau), _ptr(self.dv), _ptr(self.f),
-                                        _ptr(self.status), _ptr(self.rows), self.NROW, _ptr(self.frames), _ptr(self.info), self._stream())
-            _lib.check(self._L, self._h, rc, "tsidb_tick")
+            self._call("tsidb_tick", _ptr(self.q), _ptr(self.v), _ptr(self.tau), _ptr(self.dv), _ptr(self.f), _ptr(self.status),
+                       _ptr(self.rows), self.NROW, _ptr(self.frames), _ptr(self.info), self._stream())
             return self.tau, self.q, self.v, self.status, self.obs
         wa = walk[0].args(self, walk[1], *walk[2:]) if walk is not None else None
         qs, vs = _snap if _snap is not None else (None, None)
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_tick_walk(self._h, C.byref(wa) if wa is not None else None, _ptr(self.q), _ptr(self.v), _ptr(self.tau),
-                                         _ptr(self.dv), _ptr(self.f), _ptr(self.status), _ptr(self.rows), self.NROW, _ptr(self.frames),
-                                         _ptr(self.info), _ptr(qs), _ptr(vs), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_tick_walk")
+        self._call("tsidb_tick_walk", C.byref(wa) if wa is not None else None, _ptr(self.q), _ptr(self.v), _ptr(self.tau),
+                   _ptr(self.dv), _ptr(self.f), _ptr(self.status), _ptr(self.rows), self.NROW, _ptr(self.frames), _ptr(self.info),
+                   _ptr(qs), _ptr(vs), self._stream())
         return self.tau, self.q, self.v, self.status, self.obs
 
     def sim_step(self, teleport=True, q_tsid=None, v_tsid=None, _from_pipe=False):
@@ -765,12 +620,8 @@ class WalkController:
             self.sync_sim()
         src = q_tsid if q_tsid is not None else self.q
         srcv = v_tsid if v_tsid is not None else self.v
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_sim(self._h, _ptr(src) if teleport else None, _ptr(srcv) if teleport else None,
-                                   _ptr(self.qpos), _ptr(self.qvel),
-                                   _ptr(self.qacc_warmstart), None, _ptr(self.ncon), _ptr(self.con_pairs),
-                                   _ptr(self.info), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_sim")
+        self._call("tsidb_sim", _ptr(src) if teleport else None, _ptr(srcv) if teleport else None, _ptr(self.qpos), _ptr(self.qvel),
+                   _ptr(self.qacc_warmstart), None, _ptr(self.ncon), _ptr(self.con_pairs), _ptr(self.info), self._stream())
         return self.qpos, self.qvel
 
     def rbd_terms(self, q=None, v=None):
@@ -781,10 +632,8 @@ class WalkController:
         z = lambda *s: torch.zeros(*s, dtype=self.dtype, device=self.device)
         NV = self.NV
         out = dict(M=z(N, NV, NV), h=z(N, NV), Jcom=z(N, 3, NV), Jf=z(N, 2, 6, NV), oMf=z(N, 2, 12), com=z(N, 3))
-        with torch.cuda.device(self.device):
-            rc = self._L.tsidb_rbd_terms(self._h, _ptr(q), _ptr(v), _ptr(out["M"]), _ptr(out["h"]), _ptr(out["Jcom"]),
-                                         _ptr(out["Jf"]), _ptr(out["oMf"]), _ptr(out["com"]), self._stream())
-        _lib.check(self._L, self._h, rc, "tsidb_rbd_terms")
+        self._call("tsidb_rbd_terms", _ptr(q), _ptr(v), _ptr(out["M"]), _ptr(out["h"]), _ptr(out["Jcom"]), _ptr(out["Jf"]),
+                   _ptr(out["oMf"]), _ptr(out["com"]), self._stream())
         return out
 
     # ------------------------------------------------------------------ reference method surface

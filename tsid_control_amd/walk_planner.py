@@ -8,11 +8,13 @@ the reference's intent and signature; WalkSchedule is the batched table + evalua
 authors: polynomial coefficients per (env, step) held on the device, evaluated each tick as tensor
 expressions (no host round trip).
 """
+import ctypes as C
 from typing import List
 
 import numpy as np
 import torch
 
+from . import _lib
 from .conf import RobotConfig
 from .foot_trajectory import FootTrajectory
 from .footstep_planner import Footstep, FootstepPlanner, resample_path, unicycle_path
@@ -230,8 +232,6 @@ class WalkSchedule:
         whose done flag is set in wc.rows (no host sync), new_paths = advance the env's episode counter first, i.e. draw
         a new path scale.  path [N,P,2] float64 + npts [N]: explicit polylines (world coordinates) instead of the
         unicycle path.  Needs the envs' standing state in wc.cop_frames / wc.com_ref (a reset puts it there)."""
-        import ctypes as C
-        from . import _lib
         if not hasattr(self, "pp"):
             raise _lib.TsidbError("this schedule was built on the host (WalkSchedule(...)): use WalkSchedule.on_device")
         ids, n_ids = None, 0
@@ -249,14 +249,11 @@ class WalkSchedule:
                                       "also when only some envs are replanned)")
             self._path_keep = (path, npts)
         use_rng = path is None and self.scale is None
-        with torch.cuda.device(wc.device):
-            rc = wc._L.tsidb_walk_plan(wc._h, p(ids), n_ids, p(wc.rows) if done_only else None, wc.NROW,
-                                       self.pp.ctypes.data_as(C.c_void_p), PLAN_NPARAMS, p(path), p(npts),
-                                       int(path.shape[1]) if path is not None else 0, p(self.scale), p(self.episode) if use_rng else None,
-                                       int(bool(new_paths)), self.K, p(self.steps), p(self.coef), p(self.side), p(self.nsteps),
-                                       p(self.rest), p(self.com), p(self.flags), p(self.t_offset), p(self.td_latch), float(t),
-                                       p(t_device), wc._stream())
-        _lib.check(wc._L, wc._h, rc, "tsidb_walk_plan")
+        wc._call("tsidb_walk_plan", p(ids), n_ids, p(wc.rows) if done_only else None, wc.NROW, self.pp.ctypes.data_as(C.c_void_p),
+                 PLAN_NPARAMS, p(path), p(npts), int(path.shape[1]) if path is not None else 0, p(self.scale),
+                 p(self.episode) if use_rng else None, int(bool(new_paths)), self.K, p(self.steps), p(self.coef), p(self.side),
+                 p(self.nsteps), p(self.rest), p(self.com), p(self.flags), p(self.t_offset), p(self.td_latch), float(t), p(t_device),
+                 wc._stream())
 
     def enable_touchdown_feedback(self, fraction=0.6):
         """Closed loop: take a step's touch-down as soon as the sim reports the swing foot on the floor after
@@ -366,7 +363,6 @@ class WalkSchedule:
     def args(self, wc, t: float, t_device=None):
         """This tick's reference update as the argument block of tsidb_tick_walk (WalkController.tick(walk=...) /
         step_pipelined(walk=...)): the update then runs in the tick kernel's prologue instead of a launch of its own."""
-        from . import _lib
         if not hasattr(self, "_side32"):   # (host-built schedule: int32 / contiguous copies for the kernel)
             self._side32 = self.side.to(torch.int32).contiguous()
             self._nsteps32 = self.nsteps.to(torch.int32).contiguous()
@@ -385,22 +381,5 @@ class WalkSchedule:
         reference for every env in one kernel (tsidb_walk_update); equivalent to
         wc.update_tasks(*self.sample(t)) followed by wc.com_ref[:] = self.com_ref(t).  t_device: a one-element
         float64 tensor holding the time - read by the kernel instead of `t` (graph capture)."""
-        import ctypes as C
-        from . import _lib
-        if not hasattr(self, "_side32"):   # (host-built schedule: int32 / contiguous copies for the kernel)
-            self._side32 = self.side.to(torch.int32).contiguous()
-            self._nsteps32 = self.nsteps.to(torch.int32).contiguous()
-            self._coef_c, self._rest_c, self._com_c = self.coef.contiguous(), self.rest.contiguous(), self.com.contiguous()
-        p = lambda x: C.c_void_p(x.data_ptr())
-        if self.td_latch is not None:
-            wc.sync_sim()  # the kernel reads the last sim step's contact list: nothing of it may still be in flight
-        with torch.cuda.device(wc.device):
-            rc = wc._L.tsidb_walk_update(wc._h, p(self._coef_c), p(self._side32), p(self._nsteps32), p(self._rest_c),
-                                         p(self._com_c), self.K, float(t), float(self.conf.step_duration),
-                                         float(self.t_start), float(self.omega), float(self.z0), float(self.dz),
-                                         p(wc.frames), p(self.t_offset) if self.t_offset is not None else None,
-                                         p(wc.ncon) if self.td_latch is not None else None,
-                                         p(wc.con_pairs) if self.td_latch is not None else None,
-                                         p(self.td_latch) if self.td_latch is not None else None, float(self.td_fraction),
-                                         p(t_device) if t_device is not None else None, wc._stream())
-        _lib.check(wc._L, wc._h, rc, "tsidb_walk_update")
+        a = self.args(wc, t, t_device)   # (one block for both entry points; tsidb_walk_update takes its fields one by one)
+        wc._call("tsidb_walk_update", *(getattr(a, f) for f, _ in a._fields_), wc._stream())
