@@ -129,6 +129,31 @@ int tsidb_set_env_params(tsidb_handle h, const void *env_params, const void *ter
  * wrenches.  Rejected by a library built without the sim stage.  The pointer is remembered, not copied. */
 int tsidb_set_xfrc(tsidb_handle h, void *xfrc);
 
+/* direct actuator control of the sim stage: mj_data.ctrl, the field a caller of mj_step (main.py:195) writes to drive the
+ * actuators - a policy's joint targets or torques, a residual on top of TSID, replayed commands.  ctrl [N, NA] (device, the
+ * path's arithmetic type) in the MJCF actuator order, the order of act_force (tsidb_set_sim_readouts): actuator a drives the
+ * joint whose TSID position is q[mj_ctrl_qidx[a]] (the blob's section).  As in MuJoCo the values persist until the caller
+ * changes them: every sim step reads them anew (tsidb_sim, every step of a tsidb_sim_batch launch, every substep of
+ * tsidb_step, every step of tsidb_sim_ctrl).  mode says what a value is; with d the actuator's dof:
+ *   TSIDB_CTRL_POSITION  a joint target [rad] for the model's <position> servo, force = clampF(kp (clampC(ctrl) - q_d) - kv qdot_d)
+ *                        with its ctrlrange / forcerange clamps - what mj_step does with mj_data.ctrl.  Replaces the target
+ *                        taken from q_tsid, and replaces tau in the closed loop.
+ *   TSIDB_CTRL_MOTOR     a motor torque [N m], applied unclamped exactly as the closed loop applies tau.  Replaces the servo in
+ *                        the open loop and tau in the closed loop.
+ *   TSIDB_CTRL_RESIDUAL  an offset to the control signal the TSID stage supplies.  In a step driven by position targets a
+ *                        target offset [rad]: clampC(target + ctrl), target = 0 when q_tsid is NULL; in a step driven by tau
+ *                        (closed loop) a torque offset [N m]: tau + ctrl.  An all-zero buffer leaves every result bit-identical.
+ * The base teleport stays what q_tsid decides: ctrl only decides the joints.  In POSITION / MOTOR mode the closed-loop
+ * tsidb_step still runs the tick and writes tau, but the sim is driven by ctrl.  The act_force readout reports the force
+ * applied, in every mode.  A non-finite value skips the env's step like a non-finite joint target (info flag bit 4).
+ * tsidb_reset / tsidb_reset_done zero the rows of the envs they reset (mj_resetData).  NULL with TSIDB_CTRL_OFF (the default)
+ * unregisters: the sim is driven by q_tsid / tau alone, by the kernels that do not read ctrl.  Fails (message via
+ * tsidb_last_error) for an unknown mode, for NULL with another mode than TSIDB_CTRL_OFF or a buffer with TSIDB_CTRL_OFF, and in a
+ * library built without the sim stage.  Changing the registration first waits for the handle's kernels in flight, as
+ * tsidb_set_sensors does.  The pointer is remembered, not copied. */
+enum { TSIDB_CTRL_OFF = 0, TSIDB_CTRL_POSITION = 1, TSIDB_CTRL_MOTOR = 2, TSIDB_CTRL_RESIDUAL = 3 };
+int tsidb_set_ctrl(tsidb_handle h, void *ctrl, int mode);
+
 /* sim-stage readouts of the last sim step (mj_data.contact, mj_contactForce, mj_data.actuator_force); each may be NULL.
  * con_force [N,32,6], con_frame [N,32,9], con_pos [N,32,4] = world position (3) + dist,
  * act_force [N,NA], foot_grf [N,2,6] = world force (3) + CoP (3).  Rows >= ncon are zero.
@@ -138,7 +163,8 @@ int tsidb_set_xfrc(tsidb_handle h, void *xfrc);
  * normal, pointing from geom1 to geom2, and the two tangents (contact.frame; mju_makeFrame).  The floor is geom1 of every
  * floor contact, so the normal points up out of the floor and the force is the floor's push on the robot.  con_pos is
  * contact.pos and contact.dist, taken where the step's collision ran (its start).  act_force is actuator_force in the MJCF
- * actuator order (the ctrl order): the clamped position-servo force, or the motor torque in the closed loop.  foot_grf holds
+ * actuator order (the ctrl order): the clamped position-servo force, or the motor torque in the closed loop (with
+ * tsidb_set_ctrl: the force that mode applied).  foot_grf holds
  * per sole (LF, RF, TSID's contact order) the floor contacts on that sole's sim body summed in the world frame, then their
  * centre of pressure (normal-force-weighted mean of the contact positions; all zero while the sole carries no normal force).
  * Every sim step writes them (a tsidb_sim_batch launch or a tsidb_step with substeps leaves the last step's values); a
@@ -218,6 +244,13 @@ int tsidb_sim(tsidb_handle h, const void *q_tsid, const void *v_tsid, void *qpos
 enum { TSIDB_MAX_SIM_BATCH = 8 };
 int tsidb_sim_batch(tsidb_handle h, int n_steps, const void *q_ring, const void *v_ring, const int32_t *slots, void *qpos, void *qvel,
                     void *qacc_ws, void *qacc, int32_t *ncon, int32_t *con_pairs, int32_t *info, void *stream);
+
+/* n_steps (1 .. TSIDB_MAX_SIM_BATCH) consecutive sim steps in ONE launch, driven by the registered ctrl buffer (tsidb_set_ctrl)
+ * alone: no teleport, no TSID state - what n_steps calls of tsidb_sim with q_tsid = NULL do, bit for bit (see tsidb_sim_batch),
+ * without the launch gaps between them.  ctrl is held over the steps (zero-order hold), so a policy can run at a fraction of the
+ * sim's rate.  ncon / con_pairs / info, the readouts and the sensors are the last step's.  Fails while no buffer is registered. */
+int tsidb_sim_ctrl(tsidb_handle h, int n_steps, void *qpos, void *qvel, void *qacc_ws, void *qacc, int32_t *ncon, int32_t *con_pairs,
+                   int32_t *info, void *stream);
 
 /* whole env step, n_substeps times: tsidb_tick then (if params[SIM_ENABLED]) tsidb_sim.
  * With params[CLOSED_LOOP] (not in the reference, whose coupling is one-way, main.py:126-129,

@@ -12,11 +12,15 @@ LIB_PATH = Path(os.environ.get("TSIDB_LIB_PATH", _HERE / "libtsidb.so"))
 SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "tsidb_set_params", "tsidb_set_refs", "tsidb_reset",
            "tsidb_tick", "tsidb_sim", "tsidb_step", "tsidb_rbd_terms", "tsidb_lds_bytes", "tsidb_walk_update", "tsidb_set_env_params", "tsidb_set_cop_ref",
            "tsidb_reset_done", "tsidb_set_posture_bias", "tsidb_walk_plan", "tsidb_set_option", "tsidb_tick_walk", "tsidb_sim_batch", "tsidb_stream_create", "tsidb_stream_destroy", "tsidb_get_option",
-           "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors"]
+           "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
 ROLE_TICK, ROLE_SIM = 0, 1
+# tsidb_set_ctrl modes (include/tsidb.h TSIDB_CTRL_*) and the most sim steps one launch takes (TSIDB_MAX_SIM_BATCH)
+CTRL_OFF, CTRL_POSITION, CTRL_MOTOR, CTRL_RESIDUAL = 0, 1, 2, 3
+CTRL_MODES = {"position": CTRL_POSITION, "motor": CTRL_MOTOR, "residual": CTRL_RESIDUAL}
+MAX_SIM_BATCH = 8
 
 _libs = {}
 
@@ -90,6 +94,8 @@ def load(path=None):
     L.tsidb_set_env_params.argtypes = [vp, vp, vp]
     L.tsidb_set_xfrc.argtypes = [vp, vp]
     L.tsidb_set_sim_readouts.argtypes = [vp] * 6
+    L.tsidb_set_ctrl.argtypes = [vp, vp, C.c_int]
+    L.tsidb_sim_ctrl.argtypes = [vp, C.c_int] + [vp] * 8
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -230,10 +230,14 @@ template <typename T> struct SimRing { const T *q, *v; unsigned long long slots;
 // only while a buffer is registered (ro, the last argument, is then not read).
 // SE = the step writes the site sensors to ro.sens (tsidb_set_sensors), [N, nsite, NSENS]; likewise selected only while a buffer
 // is registered, and built together with RO = true only (unregistered readouts are NULL pointers there and store nothing).
-template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false, bool RO = false, bool SE = false>
+// CT = the step takes its actuation from ctrl (tsidb_set_ctrl), [N, NA], in the mode ctrl_mode; likewise selected only while a
+// buffer is registered (ctrl and ctrl_mode, the last arguments, are then not read).  Built in two forms: alone, and with RO = true
+// and SE = true (registered readouts or sensors beside ctrl select that one: unregistered readouts are NULL pointers, and without
+// registered sensors the model's site count is zero and no lane writes a row).
+template <typename T, int NW, bool MULTI, int WPE = TSIDB_WPE, bool XF = false, bool RO = false, bool SE = false, bool CT = false>
 __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))) void k_sim(const DevModel<T> *__restrict__ mp, int n, int B, SimRing<T> ring, T *qpos, T *qvel,
                                               T *qacc_ws, const T *env_params, const T *terrain, const T *xfrc, const T *motor_tau, T *qacc, int *ncon,
-                                              int *con, int *info, SimOut<T> ro) {
+                                              int *con, int *info, SimOut<T> ro, const T *ctrl, int ctrl_mode) {
   __shared__ SimLds<T> L;
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   if ((int)blockIdx.x >= n) return;
@@ -250,6 +254,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       if constexpr (XF) asm volatile("" : "+s"(xfrc) : : "memory");
       if constexpr (RO) asm volatile("" : "+s"(ro.con_force), "+s"(ro.con_frame), "+s"(ro.con_pos), "+s"(ro.act_force), "+s"(ro.foot_grf) : : "memory");
       if constexpr (SE) asm volatile("" : "+s"(ro.sens) : : "memory");
+      if constexpr (CT) asm volatile("" : "+s"(ctrl) : : "memory");
     }
     SimOut<T> roe{}; // (the env's rows)
     if constexpr (RO) {
@@ -273,6 +278,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       if (lane < NV) { big += fabs(qvel[E * NV + lane]); chk += fabs(qacc_ws[E * NV + lane]) + (v_tsid ? fabs(v_tsid[E * NV + lane]) : T(0)); }
       if (lane < NA && motor_tau) chk += fabs(motor_tau[E * NA + lane]);
       if constexpr (XF) for (int i = lane; i < NB * 6; i += WAVE) chk += fabs(xfrc[E * NB * 6 + i]); // (external wrenches)
+      if constexpr (CT) { if (lane < NA) chk += fabs(ctrl[E * NA + lane]); } // (direct actuator control)
       big = wave_sum(big);
       skip = __ballot(!(chk <= Eps<T>::inf)) || !(big <= T(SIM_STATE_BOUND));
       if (skip && wv == 0) {
@@ -286,10 +292,10 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       }
     }
     if (!skip)
-      sim_step_env<T, NW, XF, RO, SE>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+      sim_step_env<T, NW, XF, RO, SE, CT>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
                           env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
                           motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
-                          info ? info + E * 4 : nullptr, roe);
+                          info ? info + E * 4 : nullptr, roe, CT ? ctrl + E * NA : nullptr, ctrl_mode);
     if constexpr (MULTI) __syncthreads(); // both wavefronts; the step's state is written before the next step reads it
   }
 }
@@ -323,7 +329,7 @@ template <typename T>
 __global__ __launch_bounds__(WAVE) void k_reset(const DevModel<T> *__restrict__ mp, int n, const int *env_ids, int n_ids, T *q,
                                                 T *v, T *qpos, T *qvel, T *qacc_ws, T *com_ref, T *posture_ref,
                                                 T *foot_ref, T *contact_ref, uint8_t *cact, T *cop_frames, T *cop_ref,
-                                                const T *done_rows, int rows_ld, const T *posture_bias, T *frames, T *xfrc) {
+                                                const T *done_rows, int rows_ld, const T *posture_bias, T *frames, T *xfrc, T *ctrl) {
   __shared__ TickLds<T> L;
   const DevModel<T> &m = *mp;
   const int lane = threadIdx.x;
@@ -375,6 +381,8 @@ __global__ __launch_bounds__(WAVE) void k_reset(const DevModel<T> *__restrict__ 
   if (cop_ref && lane < 3) cop_ref[E * 3 + lane] = lane < 2 ? T(0.5) * (L.oMf[0][9 + lane] + L.oMf[1][9 + lane]) : T(0);
   // external wrenches (tsidb_set_xfrc) end with the episode, as mj_resetData clears xfrc_applied
   if (xfrc) for (int i = lane; i < NB * 6; i += WAVE) xfrc[E * NB * 6 + i] = 0;
+  // direct actuator control (tsidb_set_ctrl) likewise: mj_resetData clears ctrl
+  if (ctrl && lane < NA) ctrl[E * NA + lane] = 0;
 }
 
 template <typename T>
@@ -668,6 +676,8 @@ static void chain_table(const int *parent, int n, int (*chain)[8]) {
 } // namespace
 
 static_assert(MAXSITE == TSIDB_MAXSITE && NSENS == TSIDB_NSENS, "include/tsidb.h and the kernels agree on the sensor rows");
+static_assert((int)CTRL_POSITION == TSIDB_CTRL_POSITION && (int)CTRL_MOTOR == TSIDB_CTRL_MOTOR && (int)CTRL_RESIDUAL == TSIDB_CTRL_RESIDUAL,
+              "include/tsidb.h and the kernels agree on the ctrl modes");
 
 // Batches up to this many envs default to two wavefronts per env in k_sim and to CU-split streams (tsidb_stream_create):
 // measured, DESIGN.md section 5 "Streams"
@@ -695,6 +705,8 @@ struct tsidb_ctx {
   const uint8_t *contact_active = nullptr;
   const void *env_params = nullptr, *terrain = nullptr, *cop_ref = nullptr, *posture_bias = nullptr;
   void *xfrc = nullptr; // [N, NB, 6] external body wrenches (tsidb_set_xfrc); k_reset zeroes the reset envs' rows
+  void *ctrl = nullptr; // [N, NA] direct actuator control (tsidb_set_ctrl) in the mode ctrl_mode; k_reset zeroes the reset envs' rows
+  int ctrl_mode = TSIDB_CTRL_OFF;
   void *ro[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // sim readouts (tsidb_set_sim_readouts): con_force, con_frame, con_pos,
                                                                 // act_force, foot_grf
   bool has_readouts() const { return ro[0] || ro[1] || ro[2] || ro[3] || ro[4]; }
@@ -994,6 +1006,18 @@ extern "C" int tsidb_set_xfrc(tsidb_handle h, void *xfrc) {
   return 0;
 }
 
+extern "C" int tsidb_set_ctrl(tsidb_handle h, void *ctrl, int mode) {
+  GUARD_BEGIN
+  if (mode != TSIDB_CTRL_OFF && mode != TSIDB_CTRL_POSITION && mode != TSIDB_CTRL_MOTOR && mode != TSIDB_CTRL_RESIDUAL)
+    throw std::string("tsidb_set_ctrl: unknown mode (TSIDB_CTRL_OFF, _POSITION, _MOTOR or _RESIDUAL)");
+  if ((ctrl == nullptr) != (mode == TSIDB_CTRL_OFF)) throw std::string("tsidb_set_ctrl: a buffer needs a mode other than TSIDB_CTRL_OFF, and TSIDB_CTRL_OFF a NULL buffer");
+  if (lacks_sim(h, ctrl != nullptr, "tsidb_set_ctrl: ")) throw h->err;
+  wait_for_own_streams(h); // (a sim stage in flight was launched with the old buffer and mode)
+  h->ctrl = ctrl;
+  h->ctrl_mode = mode;
+  GUARD_END
+}
+
 extern "C" int tsidb_set_sim_readouts(tsidb_handle h, void *con_force, void *con_frame, void *con_pos, void *act_force, void *foot_grf) {
   if (!h) return -1;
   void *const p[5] = {con_force, con_frame, con_pos, act_force, foot_grf};
@@ -1057,20 +1081,23 @@ static void launch_tick(tsidb_ctx *h, void *q, void *v, void *tau, void *dv, voi
 // instead of 58 waiting for a slot; at 512 envs on half the CUs the two wavefronts of an env share SIMDs with their
 // neighbours', the sim becomes the slower stream (up to 95 us per step) and the tick stream stalls on the snapshot ring.
 // (a registered xfrc buffer selects the XF = true instantiations, registered readouts the RO = true ones; the float32 build for
-//  three wavefronts per SIMD has neither, nor sensors: the default build, bit-identical to it, runs instead; it is also never picked with
-//  lds_pad != 0)
+//  three wavefronts per SIMD has neither, nor sensors, nor ctrl: the default build, bit-identical to it, runs instead; it is also
+//  never picked with lds_pad != 0)
 template <typename T>
 static auto sim_kernel(const tsidb_ctx *h, int B, bool motor_tau) {
   if constexpr (sizeof(T) == 4)
-    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc && !h->has_readouts() && !h->sens)
+    if (B == 1 && h->sim_waves == 1 && !motor_tau && h->num_envs >= 3072 && !h->lds_pad && !h->xfrc && !h->has_readouts() && !h->sens && !h->ctrl)
       return k_sim<float, 1, false, 3, false, false>;
   // (registered sensors select the SE = true instantiations, which exist with RO = true only: the nearest superset)
-#define TSIDB_SIM_RO(NW, MULTI, XF) {k_sim<T, NW, MULTI, TSIDB_WPE, XF, false>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true, true>}
-  const decltype(&k_sim<T, 1, false>) pick[2][2][2][3] = { // [sim_waves == 2][B > 1][xfrc registered][readouts / sensors registered]
+  // (a registered ctrl buffer selects the CT = true instantiations: without readouts and sensors, or - the nearest superset while
+  //  either is registered - with both)
+#define TSIDB_SIM_RO(NW, MULTI, XF) {k_sim<T, NW, MULTI, TSIDB_WPE, XF, false>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true, true>, \
+                                     k_sim<T, NW, MULTI, TSIDB_WPE, XF, false, false, true>, k_sim<T, NW, MULTI, TSIDB_WPE, XF, true, true, true>}
+  const decltype(&k_sim<T, 1, false>) pick[2][2][2][5] = { // [sim_waves == 2][B > 1][xfrc registered][readouts / sensors / ctrl / ctrl + readouts or sensors registered]
       {{TSIDB_SIM_RO(1, false, false), TSIDB_SIM_RO(1, false, true)}, {TSIDB_SIM_RO(1, true, false), TSIDB_SIM_RO(1, true, true)}},
       {{TSIDB_SIM_RO(2, false, false), TSIDB_SIM_RO(2, false, true)}, {TSIDB_SIM_RO(2, true, false), TSIDB_SIM_RO(2, true, true)}}};
 #undef TSIDB_SIM_RO
-  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr][h->sens ? 2 : h->has_readouts()];
+  return pick[h->sim_waves == 2][B > 1][h->xfrc != nullptr][h->ctrl ? (h->sens || h->has_readouts() ? 4 : 3) : h->sens ? 2 : h->has_readouts()];
 }
 
 // B sim steps in one launch, step b driven by slot slots[b] of the [K, N, NQ] / [K, N, NV] rings q_ring / v_ring (slot 0 if NULL)
@@ -1092,7 +1119,8 @@ static void launch_sim(tsidb_ctx *h, int B, const void *q_ring, const void *v_ri
                          (const DevModel<T> *)h->d_model, h->num_envs, B, SimRing<T>{(const T *)q_ring, (const T *)v_ring, slot_bits},
                          (T *)qpos, (T *)qvel, (T *)qacc_ws, (const T *)h->env_params, (const T *)h->terrain, (const T *)h->xfrc,
                          (const T *)motor_tau, (T *)qacc, ncon, con, info,
-                         SimOut<T>{(T *)h->ro[0], (T *)h->ro[1], (T *)h->ro[2], (T *)h->ro[3], (T *)h->ro[4], {h->foot_body[0], h->foot_body[1]}, (T *)h->sens});
+                         SimOut<T>{(T *)h->ro[0], (T *)h->ro[1], (T *)h->ro[2], (T *)h->ro[3], (T *)h->ro[4], {h->foot_body[0], h->foot_body[1]}, (T *)h->sens},
+                         (const T *)h->ctrl, h->ctrl_mode);
   });
   HIP_OK(hipGetLastError());
 }
@@ -1107,7 +1135,7 @@ static void launch_reset(tsidb_ctx *h, const int32_t *env_ids, int n_ids, void *
     hipLaunchKernelGGL(k_reset<T>, dim3(grid), dim3(WAVE), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, env_ids, n_ids, (T *)q,
                        (T *)v, (T *)qpos, (T *)qvel, (T *)qacc_ws, (T *)h->com_ref, (T *)h->posture_ref, (T *)h->foot_ref,
                        (T *)h->contact_ref, (uint8_t *)h->contact_active, (T *)h->cop_frames, (T *)h->cop_ref, (const T *)done_rows,
-                       rows_ld, (const T *)h->posture_bias, (T *)frames, (T *)h->xfrc);
+                       rows_ld, (const T *)h->posture_bias, (T *)frames, (T *)h->xfrc, (T *)h->ctrl);
   });
   HIP_OK(hipGetLastError());
 }
@@ -1378,6 +1406,15 @@ int tsidb_sim_batch(tsidb_handle h, int n_steps, const void *q_ring, const void 
   GUARD_BEGIN
   if (!qpos || !qvel || !qacc_ws || !q_ring || !slots) throw std::string("tsidb_sim_batch: null buffer");
   launch_sim(h, n_steps, q_ring, v_ring, slots, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
+  GUARD_END
+}
+
+int tsidb_sim_ctrl(tsidb_handle h, int n_steps, void *qpos, void *qvel, void *qacc_ws, void *qacc, int32_t *ncon, int32_t *con_pairs,
+                   int32_t *info, void *stream) {
+  GUARD_BEGIN
+  if (!h->ctrl) throw std::string("tsidb_sim_ctrl: no ctrl buffer registered (call tsidb_set_ctrl first)");
+  if (!qpos || !qvel || !qacc_ws) throw std::string("tsidb_sim_ctrl: null state buffer");
+  launch_sim(h, n_steps, nullptr, nullptr, nullptr, qpos, qvel, qacc_ws, qacc, ncon, con_pairs, info, (hipStream_t)stream);
   GUARD_END
 }
 

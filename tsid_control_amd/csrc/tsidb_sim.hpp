@@ -1171,10 +1171,14 @@ template <typename T> __device__ __forceinline__ void sim_sensors_zero(const Dev
 // runtime NULL test: the test alone cost the multi-step and the three-wavefront float32 kernels VGPR spills.
 // RO: the step writes the readouts of `ro` (tsidb_set_sim_readouts), likewise a template parameter.
 // SE: the step writes the site sensors to ro.sens (tsidb_set_sensors), likewise; built together with RO = true only.
-template <typename T, int NW, bool XF, bool RO, bool SE = false>
+// CT: the step takes its actuation from ctrl (the env's [NA] row, MJCF actuator order; tsidb_set_ctrl), likewise; built without
+// readouts and sensors, and with both.  ctrl_mode (TSIDB_CTRL_POSITION / MOTOR / RESIDUAL) is a run-time value: a uniform scalar that selects
+// between values the step computes anyway, so one instantiation serves the three modes.
+enum { CTRL_POSITION = 1, CTRL_MOTOR = 2, CTRL_RESIDUAL = 3 };
+template <typename T, int NW, bool XF, bool RO, bool SE = false, bool CT = false>
 __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
-                             int *con_out, int *info, const SimOut<T> &ro) {
+                             int *con_out, int *info, const SimOut<T> &ro, const T *ctrl = nullptr, int ctrl_mode = 0) {
   // per-env randomisation (BASELINE config 5), NULL = nominal: mass scale, contact friction, floor plane
   const T mscale = envp ? envp[0] : T(1);
   Floor<T> &fl = L.fl;
@@ -1225,7 +1229,13 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     }
     L.qvel[lane] = val;
   }
-  const T myctrl = (lane < NA && q_tsid) ? q_tsid[m.mj_ctrl_qidx[lane]] : T(0); // joint target of actuator `lane`
+  T myctrl_ = (lane < NA && q_tsid) ? q_tsid[m.mj_ctrl_qidx[lane]] : T(0); // joint target of actuator `lane`
+  if constexpr (CT) {
+    // direct actuator control (mj_data.ctrl): the one value the actuation block needs of it.  POSITION: the servo target;
+    // MOTOR: the force; RESIDUAL: an offset to the target, or - in a step driven by motor torques - to the torque
+    if (lane < NA) myctrl_ = (ctrl_mode == CTRL_RESIDUAL && !motor_tau) ? myctrl_ + ctrl[lane] : ctrl[lane];
+  }
+  const T myctrl = myctrl_;
   for (int i = lane; i < NV * LDM; i += WAVE) L.M[i] = 0;
   __syncthreads();
   const T Oz = L.qpos[2];
@@ -1386,7 +1396,15 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     const T cc = myctrl < m.act_range[lane][0] ? m.act_range[lane][0] : (myctrl > m.act_range[lane][1] ? m.act_range[lane][1] : myctrl);
     T servo = m.mj_act_kp[lane] * (cc - L.qpos[d + 1]) - m.mj_act_kv[lane] * L.qvel[d];
     servo = servo < m.act_range[lane][2] ? m.act_range[lane][2] : (servo > m.act_range[lane][3] ? m.act_range[lane][3] : servo);
-    if constexpr (RO) { // (the readout is stored here, where it is made: nothing of it stays live across the step)
+    if constexpr (CT) {
+      // POSITION: the servo, also where the closed loop hands tau over; MOTOR: ctrl as the force, unclamped like tau;
+      // RESIDUAL: tau + ctrl in the closed loop, else the servo about the shifted target
+      T af = servo;
+      if (ctrl_mode == CTRL_MOTOR) af = myctrl;
+      else if (ctrl_mode == CTRL_RESIDUAL && motor_tau) af = motor_tau[m.mj_ctrl_qidx[lane] - 7] + myctrl;
+      L.xv[d] = af;
+      if constexpr (RO) { if (ro.act_force) ro.act_force[lane] = af; }
+    } else if constexpr (RO) { // (the readout is stored here, where it is made: nothing of it stays live across the step)
       const T af = motor_tau ? motor_tau[m.mj_ctrl_qidx[lane] - 7] : servo;
       L.xv[d] = af;
       if (ro.act_force) ro.act_force[lane] = af;

@@ -86,6 +86,9 @@ class WalkController:
         self.env_params = None
         self.terrain = None
         self.xfrc = None   # external body wrenches [N, NB, 6] (set_xfrc / apply_push); None = none registered
+        self.ctrl = None   # direct actuator control [N, NA] (set_ctrl); None = none registered
+        self.ctrl_mode = None
+        self._ctrl_qidx = None
         self._readouts = None   # sim-stage readout buffers (enable_sim_readouts); None = none registered
         self.con_force = self.con_frame = self.con_pos = self.con_dist = self.actuator_force = self.foot_force = self.foot_cop = None
         self.sensordata = None   # site sensors [N, S, 24] (enable_sensors); None = none registered
@@ -259,6 +262,56 @@ class WalkController:
         if self.xfrc is None:
             return
         self.xfrc[self._xfrc_rows(env_ids)] = 0
+
+    # ------------------------------------------------------------------ direct actuator control (policy-driven stepping)
+    def set_ctrl(self, t=None, mode="position"):
+        """Register t [N, NA] (self.dtype, on self.device, contiguous) as the sim stage's actuator controls - MuJoCo's
+        mj_data.ctrl (include/tsidb.h tsidb_set_ctrl) - in the MJCF actuator order, the order of self.actuator_force
+        (ctrl_from_q / ctrl_from_tau permute TSID-ordered values into it); read by every sim step until changed.
+        mode: "position" = joint targets [rad] for the model's position servos (replaces the targets taken from q, and tau in
+        the closed loop); "motor" = motor torques [N m], unclamped (replaces the servos, or tau); "residual" = an offset to
+        what the TSID stage supplies: to the joint targets [rad] in the open loop, to tau [N m] in the closed loop.  The base
+        teleport of the open loop stays; the closed-loop tick still runs and writes self.tau.
+        The tensor is used in place, not copied: self.ctrl is it.  None unregisters (TSID drives the joints again).
+        reset() / reset_done() zero the rows of the envs they reset.
+        A caller that writes self.ctrl in place while step_pipelined() / capture_steps() is in use must call sync_sim()
+        first, as the methods here do: a sim stage left unlaunched would otherwise read the new values."""
+        self.sync_sim()   # sim stages step_pipelined() has not launched yet belong to the old controls
+        if t is None:
+            self._call("tsidb_set_ctrl", None, _lib.CTRL_OFF)
+            self.ctrl = self.ctrl_mode = None
+            return
+        if mode not in _lib.CTRL_MODES:
+            raise _lib.TsidbError(f"set_ctrl: mode must be one of {sorted(_lib.CTRL_MODES)}, got {mode!r}")
+        self._buffer("set_ctrl", "t", (self.num_envs, self.NA), t)
+        self._call("tsidb_set_ctrl", _ptr(t), _lib.CTRL_MODES[mode])
+        self.ctrl, self.ctrl_mode = t, mode
+
+    def _ctrl_index(self, device):
+        if self._ctrl_qidx is None or self._ctrl_qidx.device != device:
+            self._ctrl_qidx = torch.as_tensor(np.asarray(self.model["mj_ctrl_qidx"], dtype=np.int64), device=device)
+        return self._ctrl_qidx
+
+    def ctrl_from_q(self, q):
+        """[.., NA] joint positions in the actuator (ctrl) order from a TSID q [.., NQ]: q[..., mj_ctrl_qidx]."""
+        return q[..., self._ctrl_index(q.device)]
+
+    def ctrl_from_tau(self, tau):
+        """[.., NA] joint torques in the actuator (ctrl) order from a TSID tau [.., NA]: tau[..., mj_ctrl_qidx - 7]."""
+        return tau[..., self._ctrl_index(tau.device) - 7]
+
+    def sim_steps(self, n):
+        """n sim steps driven by self.ctrl alone (set_ctrl first), no teleport: the controls are held over the steps
+        (zero-order hold), up to 8 steps per launch (tsidb_sim_ctrl) - bit-identical to n sim_step(teleport=False) calls.
+        Returns (qpos, qvel)."""
+        self.sync_sim()
+        n = int(n)
+        while n > 0:
+            b = min(n, _lib.MAX_SIM_BATCH)
+            self._call("tsidb_sim_ctrl", b, _ptr(self.qpos), _ptr(self.qvel), _ptr(self.qacc_warmstart), None, _ptr(self.ncon),
+                       _ptr(self.con_pairs), _ptr(self.info), self._stream())
+            n -= b
+        return self.qpos, self.qvel
 
     # ------------------------------------------------------------------ sim-stage readouts (contacts, forces)
     def enable_sim_readouts(self, con_force=None, con_frame=None, con_pos=None, actuator_force=None, foot_grf=None):
@@ -469,7 +522,7 @@ class WalkController:
         (the default for up to 1024 envs is 8) the last few sim stages are not even launched until the batch is full, so a
         device / stream synchronize does not make the sim state current - sync_sim() launches them and makes the current
         stream wait.  Every entry point of this class that reads or rewrites sim-side data (step, sim_step, reset,
-        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, enable_sim_readouts, disable_sim_readouts, enable_sensors, disable_sensors,
+        reset_done, set_params, set_env_params, set_xfrc, apply_push, clear_pushes, set_ctrl, sim_steps, enable_sim_readouts, disable_sim_readouts, enable_sensors, disable_sensors,
         capture_steps, WalkSchedule.apply with touch-down feedback) calls it.
         `events` = four torch.cuda.Event recorded around the tick (current stream) and around the sim (sim stream), for
         timing."""
@@ -573,7 +626,7 @@ class WalkController:
 
         class _Graph:
             steps = n_steps
-            keep = (P.qring, P.vring, P.stream, self.xfrc, *written)   # what the captured kernels point at
+            keep = (P.qring, P.vring, P.stream, self.xfrc, self.ctrl, *written)   # what the captured kernels point at
 
             def replay(self_inner):
                 g.replay()
