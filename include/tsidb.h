@@ -343,6 +343,88 @@ typedef struct tsidb_walk_args {
 int tsidb_tick_walk(tsidb_handle h, const tsidb_walk_args *walk, void *q, void *v, void *tau, void *dv, void *f, int32_t *status,
                     void *obs, int obs_ld, void *frames, int32_t *info, void *q_snapshot, void *v_snapshot, void *stream);
 
+/* ---- the environment around a policy-driven sim loop (no reference counterpart: the reference's only controller is TSID).
+ * One policy step is tsidb_policy_act, tsidb_sim_ctrl (decimation sim steps), tsidb_policy_reward, tsidb_reset_done,
+ * tsidb_policy_obs on one stream: plain asynchronous launches, no host synchronisation, no allocation, so the step can be
+ * captured in a HIP graph.  All three fail (message via tsidb_last_error) in a library built without the sim stage, while no
+ * ctrl buffer is registered (tsidb_set_ctrl) and before tsidb_policy_config.  The TSIDB_POL_NOBS constant is the v1 robot's:
+ * 11 + 3 NA in general (65 for robot/v0).
+ *
+ * Reward terms, unweighted, in the order of terms [N, TSIDB_POL_NT] and of the weights; v = R^T qvel[0:3] and w = qvel[3:6] are
+ * the base velocities in the body frame (quaternion stored wxyz, normalised on the way in), g = R^T (0, 0, -1) the projected
+ * gravity, cmd = command[e] = (vx, vy, yaw rate):
+ *   0 track_lin_vel  exp(-|cmd_xy - v_xy|^2 / sigma^2)        6 torques        sum_a act_force_a^2 (0 while no act_force readout
+ *   1 track_ang_vel  exp(-(cmd_yaw - w_z)^2 / sigma^2)                         is registered, tsidb_set_sim_readouts)
+ *   2 lin_vel_z      v_z^2                                    7 action_rate    sum_a (last_action_a - prev_action_a)^2
+ *   3 ang_vel_xy     w_x^2 + w_y^2                            8 joint_vel      sum_a qvel[mj_act_dof[a]]^2
+ *   4 orientation    g_x^2 + g_y^2                            9 feet_air_time  sum_f (air_f - t_air) first_contact_f [|cmd_xy| > deadband]
+ *   5 base_height    (z - h_target)^2                         10 alive 1       11 termination  1 if terminated else 0 */
+enum { TSIDB_POL_NT = 12, TSIDB_POL_HIST = 8, TSIDB_POL_NOBS = 71, TSIDB_POL_NPRIV = 4 };
+
+/* tsidb_policy_config's parameter vector (float64, host) */
+enum {
+  TSIDB_POL_P_CLIP = 0 /* actions are clipped to +-clip (>= 0) */, TSIDB_POL_P_ALPHA /* ctrl filter, in (0, 1]; 1 = none */,
+  TSIDB_POL_P_SIGMA /* of both tracking terms, > 0 */, TSIDB_POL_P_H_TARGET, TSIDB_POL_P_T_AIR, TSIDB_POL_P_DEADBAND,
+  TSIDB_POL_P_MAX_EPISODE_STEPS /* policy steps until the timeout; 0 = none */, TSIDB_POL_P_DECIMATION /* sim steps per policy step, >= 1 */,
+  TSIDB_POL_P_SEED /* of the command draws */, TSIDB_POL_P_CMD_LO /*3*/, TSIDB_POL_P_CMD_HI = TSIDB_POL_P_CMD_LO + 3 /*3*/,
+  TSIDB_POL_P_WEIGHTS = TSIDB_POL_P_CMD_HI + 3 /*TSIDB_POL_NT*/, TSIDB_POL_NPARAMS = TSIDB_POL_P_WEIGHTS + TSIDB_POL_NT
+};
+
+/* Copies pol_params [TSIDB_POL_NPARAMS], scale [NA] and default_pos [NA] (host, float64, MJCF actuator order) and
+ * term_body_mask (bit b: a floor contact on sim body b ends the episode; the blob's sim body order, 0 = the torso) into the
+ * handle.  First waits for the kernels in flight, as tsidb_set_params does.  Rejects a wrong n_params, non-finite values, clip < 0,
+ * alpha outside (0, 1], sigma <= 0, decimation < 1, max_episode_steps < 0, cmd_lo > cmd_hi and a mask bit >= the number of sim
+ * bodies. */
+int tsidb_policy_config(tsidb_handle h, const double *pol_params, int n_params, const double *scale, const double *default_pos,
+                        uint32_t term_body_mask);
+
+/* the per-env state of the policy environment: device buffers owned by the caller, in the path's arithmetic type unless an
+ * integer type is named; all but delay and obs are required */
+typedef struct tsidb_policy_bufs {
+  void *act_hist;     /* [TSIDB_POL_HIST, N, NA] ring of clipped actions, slot = episode step & 7 */
+  void *last_action;  /* [N, NA] */
+  void *prev_action;  /* [N, NA] */
+  void *command;      /* [N, 3] vx, vy, yaw rate; redrawn at a restart where cmd_lo != cmd_hi, else the caller's */
+  void *air_time;     /* [N, 2] seconds since the left / right sole last touched the floor */
+  int32_t *ep_len;    /* [N] policy steps taken in the running episode */
+  int32_t *episode;   /* [N] episodes started */
+  const int32_t *delay; /* [N] actuation delay in policy steps, clamped to 0 .. 7; NULL = none */
+  void *terms;        /* [N, TSIDB_POL_NT] the unweighted reward terms of the last tsidb_policy_reward */
+  int32_t *timeout;   /* [N] 1 where the last step ended the episode by its length alone */
+  void *obs;          /* [N, obs_ld]; NULL = tsidb_policy_obs writes no rows */
+  int obs_ld;         /* row stride in elements, >= TSIDB_POL_NOBS + TSIDB_POL_NPRIV */
+} tsidb_policy_bufs;
+
+/* before the sim steps.  Per env e and actuator a (the order of ctrl): act = clip(action, +-clip), a NaN passing through (the sim
+ * step then skips the env, info flag bit 4, which tsidb_policy_reward counts as a termination); act_hist[ep_len & 7] = act;
+ * delayed = the ring entry from delay[e] steps ago, 0 where delay[e] > ep_len[e]; target = default[a] + scale[a] delayed;
+ * ctrl += alpha (target - ctrl), exactly target when alpha = 1; prev_action = last_action, last_action = act.  ctrl is the
+ * registered buffer; whether its values are joint targets or torques is tsidb_set_ctrl's mode.  action [N, NA] (device). */
+int tsidb_policy_act(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *action, void *stream);
+
+/* after the sim steps, before the reset: qpos, qvel, ncon, con_pairs, info as tsidb_sim_ctrl left them.  Writes terms, reward =
+ * sum_k weights[k] terms[k], done and timeout, then the air times and ep_len += 1.  reward and done point at the first env's
+ * values, row_ld elements apart (columns TSIDB_NOBS and TSIDB_NOBS + 1 of the rows tsidb_reset_done reads).  The foot contact
+ * flag c_f is 1 when a live floor row of con_pairs (bit 0x8000 clear) is on a geom of sole f's body; first_contact_f = c_f and
+ * air_f > 0; afterwards air_f = c_f ? 0 : air_f + decimation dt.  terminated: info flag bit 4, a non-finite state,
+ * z < params[DONE_HEIGHT], 1 - 2 (qx^2 + qy^2) < params[DONE_TILT] (tsidb_tick's fall test on the sim quaternion) or a floor
+ * contact on a body of term_body_mask; timeout = not terminated and max_episode_steps > 0 and ep_len + 1 >= max_episode_steps;
+ * done = terminated or timeout. */
+int tsidb_policy_reward(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, const void *qvel, const int32_t *ncon,
+                        const int32_t *con_pairs, const int32_t *info, void *reward, void *done, int row_ld, void *stream);
+
+/* after tsidb_reset_done(done_rows, ...).  Envs whose done flag is set (column TSIDB_NOBS + 1 of done_rows [N, rows_ld]): ring
+ * rows, last_action, prev_action, air_time and ep_len zeroed, episode + 1, the ctrl row set to default in TSIDB_CTRL_POSITION
+ * mode (the filter starts at the default pose; the reset left 0, which stays in the other modes), and command[i] = lo_i +
+ * (hi_i - lo_i) U_i where cmd_lo[i] != cmd_hi[i], U_i = the top 53 bits of hash(seed + i, env, episode) - the hash of
+ * tsidb_walk_plan - over 2^53.  Then for every env the observation row from the current state, physical units, unscaled:
+ *   0-2 base angular velocity (body frame)   3-5 projected gravity   6-8 command   9.. joint position - default (NA, actuator
+ *   order: qpos[mj_act_dof[a] + 1])   then joint velocity (NA: qvel[mj_act_dof[a]])   then last_action (NA)   then the foot
+ *   contact flags LF, RF ((1, 1) for an env just reset: the reset leaves the contact list of the fallen robot)   then the
+ *   privileged tail from column TSIDB_POL_NOBS: base linear velocity (body frame, 3), base height. */
+int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
+                     const void *qvel, const int32_t *ncon, const int32_t *con_pairs, void *stream);
+
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */
 int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void *hbias, void *Jcom, void *Jf,

@@ -1,0 +1,170 @@
+"""The policy environment (PolicyEnv; tsidb_policy_act / _reward / _obs): what it costs around the sim steps, and against the
+same environment logic written with torch ops.  Policy-steps/s, float64, position mode about the standing pose with small
+random actions (the robots stay on their feet: the same contact work throughout), episodes of 200 steps so that restarts are
+part of the load, of
+  (a) sim     the bare wc.sim_steps(decimation) loop - what the sim alone takes
+  (b) torch   TorchEnv below: clip / delay ring / filter, reward terms, termination, reset_done, bookkeeping of the restarted
+              envs and the observation row as element-wise torch ops on the same tensors (commands are redrawn with torch.rand
+              instead of the library's hash; everything else computes what the kernels compute)
+  (c) fused   PolicyEnv.step
+at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the three.
+    python tools/policy_env.py [out.json]          (on an MI355X; default profiles/policy_env.json)
+    python tools/policy_env.py --trace ENVS STEPS  (a short run of (c) alone, for rocprofv3 --kernel-trace --stats)"""
+import json
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+from tsid_control_amd import PolicyEnv, RobotConfig, WalkController, _lib  # noqa: E402
+
+WEIGHTS = dict(track_lin_vel=1.0, track_ang_vel=0.5, lin_vel_z=-2.0, ang_vel_xy=-0.05, orientation=-1.0, base_height=-10.0,
+               action_rate=-0.01, joint_vel=-1e-3, feet_air_time=1.0, alive=0.2, termination=-5.0)
+KW = dict(action_scale=0.25, action_clip=1.0, filter_alpha=0.8, command_range=((0.0, 0.5), (0.0, 0.0), (-0.5, 0.5)), max_episode_steps=200,
+          reward_weights=WEIGHTS)
+
+
+class TorchEnv:
+    """PolicyEnv's step with torch ops in place of the three kernels"""
+
+    def __init__(self, n, decimation, delay):
+        conf = RobotConfig()
+        conf.reference_quirks = False
+        self.wc = wc = WalkController(conf, num_envs=n, device="cuda:0")
+        z = lambda *s, dt=wc.dtype: torch.zeros(*s, dtype=dt, device=wc.device)
+        wc.set_ctrl(z(n, wc.NA), "position")
+        self.n, self.NA, self.decimation, self.delay = n, wc.NA, decimation, delay.long()
+        self.hist, self.last, self.prev = z(8, n, wc.NA), z(n, wc.NA), z(n, wc.NA)
+        self.command, self.air = z(n, 3), z(n, 2)
+        self.ep_len, self.episode = z(n, dt=torch.int64), z(n, dt=torch.int64)
+        self.default = wc.ctrl_from_q(wc.q0)[0].clone()
+        self.scale, self.clip, self.alpha, self.sigma2 = 0.25, 1.0, 0.8, 0.25 ** 2
+        self.h_target, self.t_air, self.deadband, self.max_steps = float(wc.qpos[0, 2]), 0.25, 0.1, 200
+        self.air_dt = decimation * conf.dt
+        self.w = torch.tensor([WEIGHTS.get(k, 0.0) for k in _lib.POL_TERMS], dtype=wc.dtype, device=wc.device)
+        self.dof = torch.as_tensor(np.asarray(wc.model["mj_act_dof"], dtype=np.int64), device=wc.device)
+        self.geom_body = torch.as_tensor(np.asarray(wc.model["mj_geom_body"], dtype=np.int64), device=wc.device)
+        self.feet = (wc._named_site("lf_imu")[0], wc._named_site("rf_imu")[0])
+        self.env_idx = torch.arange(n, device=wc.device)
+        self.lo = torch.tensor([0.0, 0.0, -0.5], dtype=wc.dtype, device=wc.device)
+        self.hi = torch.tensor([0.5, 0.0, 0.5], dtype=wc.dtype, device=wc.device)
+        self.done_height, self.done_tilt = 0.2, float(np.cos(np.deg2rad(45.0)))
+        self.obs = z(n, 11 + 3 * wc.NA + 4)
+
+    def rot(self):
+        q = self.wc.qpos[:, 3:7]
+        q = q / q.norm(dim=1, keepdim=True)
+        w, x, y, z = q.unbind(1)
+        return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z),
+                            2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+
+    def contacts(self):
+        wc = self.wc
+        cp = wc.con_pairs.long()
+        live = (torch.arange(32, device=cp.device)[None, :] < wc.ncon[:, None]) & (cp >= 0) & ((cp & 0x8000) == 0)
+        body = self.geom_body[torch.where(live, cp >> 16, torch.zeros_like(cp))]
+        foot = torch.stack([(live & (body == b)).any(1) for b in self.feet], dim=1)
+        return foot, (live & (body == 0)).any(1)
+
+    def step(self, action):
+        wc = self.wc
+        # act
+        act = action.clamp(-self.clip, self.clip)
+        self.hist[self.ep_len & 7, self.env_idx] = act
+        delayed = self.hist[(self.ep_len - self.delay) & 7, self.env_idx]
+        delayed = torch.where((self.delay > self.ep_len)[:, None], torch.zeros_like(delayed), delayed)
+        target = self.default + self.scale * delayed
+        wc.ctrl += self.alpha * (target - wc.ctrl)
+        self.prev.copy_(self.last)
+        self.last.copy_(act)
+        wc.sim_steps(self.decimation)
+        # reward
+        R = self.rot()
+        v = torch.einsum("nji,nj->ni", R, wc.qvel[:, 0:3])
+        om, cmd = wc.qvel[:, 3:6], self.command
+        foot, torso = self.contacts()
+        first = foot & (self.air > 0)
+        moving = cmd[:, :2].norm(dim=1) > self.deadband
+        finite = torch.isfinite(wc.qpos).all(1) & torch.isfinite(wc.qvel).all(1)
+        up = 1 - 2 * (wc.qpos[:, 4] ** 2 + wc.qpos[:, 5] ** 2)
+        term = ((wc.info[:, 3] & 4) != 0) | ~finite | (wc.qpos[:, 2] < self.done_height) | (up < self.done_tilt) | torso
+        timeout = ~term & (self.ep_len + 1 >= self.max_steps)
+        terms = torch.stack([torch.exp(-((cmd[:, :2] - v[:, :2]) ** 2).sum(1) / self.sigma2), torch.exp(-(cmd[:, 2] - om[:, 2]) ** 2 / self.sigma2),
+                             v[:, 2] ** 2, (om[:, :2] ** 2).sum(1), (R[:, 2, :2] ** 2).sum(1), (wc.qpos[:, 2] - self.h_target) ** 2,
+                             torch.zeros_like(up), ((self.last - self.prev) ** 2).sum(1), (wc.qvel[:, self.dof] ** 2).sum(1),
+                             (torch.where(first, self.air - self.t_air, torch.zeros_like(self.air)).sum(1) * moving),
+                             torch.ones_like(up), term.to(up.dtype)], dim=1)
+        self.air = torch.where(foot, torch.zeros_like(self.air), self.air + self.air_dt)
+        wc.reward.copy_(terms @ self.w)
+        done = term | timeout
+        wc.done.copy_(done.to(wc.dtype))
+        self.ep_len += 1
+        wc.reset_done()
+        # restarted envs, observation
+        keep = (~done)[:, None].to(wc.dtype)
+        self.hist *= keep[None]
+        self.last *= keep
+        self.prev *= keep
+        self.air *= keep
+        self.ep_len *= ~done
+        self.episode += done
+        wc.ctrl.copy_(torch.where(done[:, None], self.default[None, :], wc.ctrl))
+        self.command = torch.where(done[:, None], self.lo + (self.hi - self.lo) * torch.rand_like(self.command), self.command)
+        R = self.rot()
+        foot = self.contacts()[0] | done[:, None]
+        self.obs = torch.cat([wc.qvel[:, 3:6], -R[:, 2, :], self.command, wc.qpos[:, self.dof + 1] - self.default, wc.qvel[:, self.dof],
+                              self.last, foot.to(wc.dtype), torch.einsum("nji,nj->ni", R, wc.qvel[:, 0:3]), wc.qpos[:, 2:3]], dim=1)
+        return self.obs, wc.reward, wc.done
+
+
+def measure(n, decimation, window=300, windows=4, preroll=60):
+    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    fused = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW)
+    eager = TorchEnv(n, decimation, delay)
+    bare_conf = RobotConfig()
+    bare_conf.reference_quirks = False
+    bare = WalkController(bare_conf, num_envs=n, device="cuda:0")
+    bare.set_ctrl(bare.ctrl_from_q(bare.q0).expand(n, -1).contiguous(), "position")
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, fused.NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    run = dict(sim=lambda k: [bare.sim_steps(decimation) for _ in range(k)],
+               torch=lambda k: [eager.step(actions[i & 15]) for i in range(k)],
+               fused=lambda k: [fused.step(actions[i & 15]) for i in range(k)])
+    for fn in run.values():
+        fn(preroll)
+    torch.cuda.synchronize()
+    res = {k: [] for k in run}
+    order = list(run)
+    for w in range(windows):
+        for mode in order[w % 3:] + order[:w % 3]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run[mode](window)
+            torch.cuda.synchronize()
+            res[mode].append(window / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    us = {k: 1e6 / v for k, v in med.items()}
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
+                us_per_policy_step=us, fused_overhead_over_sim_us=us["fused"] - us["sim"], torch_overhead_over_sim_us=us["torch"] - us["sim"],
+                fused_vs_torch=med["fused"] / med["torch"], restarts_fused=int(fused.episode.sum()) - n, restarts_torch=int(eager.episode.sum()),
+                standing_height_min=float(fused.wc.qpos[:, 2].min()))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--trace":
+        n, k = int(sys.argv[2]), int(sys.argv[3])
+        env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=10, **KW)
+        a = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
+        for _ in range(k):
+            env.step(a)
+        torch.cuda.synchronize()
+        sys.exit(0)
+    out_path = sys.argv[1] if len(sys.argv) > 1 else "profiles/policy_env.json"
+    out = dict(device=torch.cuda.get_device_name(0), dtype="f64",
+               runs=[measure(n, d) for n in (4096, 512) for d in (4, 10)])
+    text = json.dumps(out, indent=1)
+    print(text)
+    with open(out_path, "w") as f:
+        f.write(text + "\n")

@@ -12,7 +12,8 @@ LIB_PATH = Path(os.environ.get("TSIDB_LIB_PATH", _HERE / "libtsidb.so"))
 SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "tsidb_set_params", "tsidb_set_refs", "tsidb_reset",
            "tsidb_tick", "tsidb_sim", "tsidb_step", "tsidb_rbd_terms", "tsidb_lds_bytes", "tsidb_walk_update", "tsidb_set_env_params", "tsidb_set_cop_ref",
            "tsidb_reset_done", "tsidb_set_posture_bias", "tsidb_walk_plan", "tsidb_set_option", "tsidb_tick_walk", "tsidb_sim_batch", "tsidb_stream_create", "tsidb_stream_destroy", "tsidb_get_option",
-           "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl"]
+           "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl",
+           "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -21,6 +22,18 @@ ROLE_TICK, ROLE_SIM = 0, 1
 CTRL_OFF, CTRL_POSITION, CTRL_MOTOR, CTRL_RESIDUAL = 0, 1, 2, 3
 CTRL_MODES = {"position": CTRL_POSITION, "motor": CTRL_MOTOR, "residual": CTRL_RESIDUAL}
 MAX_SIM_BATCH = 8
+# the policy environment (include/tsidb.h TSIDB_POL_*): reward terms in the order of the terms row and of the weights, slots of
+# the action ring, privileged columns behind the observation, and the layout of tsidb_policy_config's parameter vector
+POL_TERMS = ("track_lin_vel", "track_ang_vel", "lin_vel_z", "ang_vel_xy", "orientation", "base_height", "torques", "action_rate",
+             "joint_vel", "feet_air_time", "alive", "termination")
+POL_NT, POL_HIST, POL_NPRIV = 12, 8, 4
+POL_P_CLIP, POL_P_ALPHA, POL_P_SIGMA, POL_P_H_TARGET, POL_P_T_AIR, POL_P_DEADBAND, POL_P_MAX_EPISODE_STEPS, POL_P_DECIMATION, \
+    POL_P_SEED, POL_P_CMD_LO, POL_P_CMD_HI, POL_P_WEIGHTS, POL_NPARAMS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 15, 27
+
+
+def pol_nobs(na):
+    """observation columns of the policy environment for a robot with na actuators (TSIDB_POL_NOBS is the v1 robot's)"""
+    return 11 + 3 * na
 
 _libs = {}
 
@@ -36,6 +49,13 @@ class WalkArgs(C.Structure):
                 ("com_z0", C.c_double), ("com_drop", C.c_double), ("frames", C.c_void_p), ("t_offset", C.c_void_p),
                 ("ncon", C.c_void_p), ("con_pairs", C.c_void_p), ("td_latch", C.c_void_p), ("td_fraction", C.c_double),
                 ("t_device", C.c_void_p)]
+
+
+class PolicyBufs(C.Structure):
+    """tsidb_policy_bufs (include/tsidb.h): the per-env state of the policy environment"""
+    _fields_ = [("act_hist", C.c_void_p), ("last_action", C.c_void_p), ("prev_action", C.c_void_p), ("command", C.c_void_p),
+                ("air_time", C.c_void_p), ("ep_len", C.c_void_p), ("episode", C.c_void_p), ("delay", C.c_void_p),
+                ("terms", C.c_void_p), ("timeout", C.c_void_p), ("obs", C.c_void_p), ("obs_ld", C.c_int)]
 
 
 def dims9(L):
@@ -96,6 +116,10 @@ def load(path=None):
     L.tsidb_set_sim_readouts.argtypes = [vp] * 6
     L.tsidb_set_ctrl.argtypes = [vp, vp, C.c_int]
     L.tsidb_sim_ctrl.argtypes = [vp, C.c_int] + [vp] * 8
+    L.tsidb_policy_config.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint32]
+    L.tsidb_policy_act.argtypes = [vp, vp, vp, vp]
+    L.tsidb_policy_reward.argtypes = [vp, vp, vp, vp, i32p, i32p, i32p, vp, vp, C.c_int, vp]
+    L.tsidb_policy_obs.argtypes = [vp, vp, vp, C.c_int, vp, vp, i32p, i32p, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -3,6 +3,7 @@
 #include "tsidb_common.hpp"
 #include "tsidb_sim.hpp"
 #include "tsidb_tick.hpp"
+#include "tsidb_policy.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -400,13 +401,6 @@ __global__ __launch_bounds__(256) void k_walk(int n, WalkArgs<T> wa) {
 // z the parabola / cubic through the knots), rest placements, and the CoM plan: DCM end points backwards from the final
 // stand, then one LIPM segment (ctrl/LIPM.py:34-49 in closed form) per phase - the tables WalkSchedule.__init__ builds on
 // the host, so that a reset with a new path never leaves the GPU.  Arithmetic in float64 whatever the path's type.
-__device__ __forceinline__ unsigned long long plan_hash(unsigned long long seed, unsigned long long env, unsigned long long episode) {
-  unsigned long long x = seed ^ (env * 0x9E3779B97F4A7C15ull) ^ (episode * 0xD1B54A32D192ED03ull);
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __device__ __forceinline__ void plan_poly(int nk, const double *x, const double *f, double *c) { // Newton's divided differences
   double d1[3] = {0, 0, 0}, d2[2] = {0, 0}, d3 = 0;
   for (int i = 0; i + 1 < nk; i++) d1[i] = (f[i + 1] - f[i]) / (x[i + 1] - x[i]);
@@ -678,6 +672,8 @@ static void chain_table(const int *parent, int n, int (*chain)[8]) {
 static_assert(MAXSITE == TSIDB_MAXSITE && NSENS == TSIDB_NSENS, "include/tsidb.h and the kernels agree on the sensor rows");
 static_assert((int)CTRL_POSITION == TSIDB_CTRL_POSITION && (int)CTRL_MOTOR == TSIDB_CTRL_MOTOR && (int)CTRL_RESIDUAL == TSIDB_CTRL_RESIDUAL,
               "include/tsidb.h and the kernels agree on the ctrl modes");
+static_assert(POL_NT == TSIDB_POL_NT && POL_HIST == TSIDB_POL_HIST && POL_NPRIV == TSIDB_POL_NPRIV && (NA != 20 || POL_NOBS == TSIDB_POL_NOBS),
+              "include/tsidb.h and the kernels agree on the policy environment's rows");
 
 // Batches up to this many envs default to two wavefronts per env in k_sim and to CU-split streams (tsidb_stream_create):
 // measured, DESIGN.md section 5 "Streams"
@@ -716,6 +712,10 @@ struct tsidb_ctx {
   double site_pos[TSIDB_MAXSITE][3] = {}, site_R[TSIDB_MAXSITE][9] = {};
   void *sens = nullptr; // [N, n_sites, TSIDB_NSENS]
   unsigned long long foot_geoms[2] = {0, 0}; // bit g: collision geom g is on that body
+  // the policy environment (tsidb_policy_config): its parameter vector, the action scale and default pose, the body mask
+  bool pol_set = false;
+  double pol[TSIDB_POL_NPARAMS] = {}, pol_scale[NA] = {}, pol_def[NA] = {};
+  unsigned pol_mask = 0;
   std::string err;
 };
 
@@ -1139,6 +1139,113 @@ static void launch_reset(tsidb_ctx *h, const int32_t *env_ids, int n_ids, void *
   });
   HIP_OK(hipGetLastError());
 }
+
+// ---- the policy environment (tsidb_policy.hpp)
+template <typename T>
+static PolicyCfg<T> policy_cfg(const tsidb_ctx *h) {
+  const double *p = h->pol;
+  PolicyCfg<T> c;
+  c.clip = (T)p[TSIDB_POL_P_CLIP]; c.alpha = (T)p[TSIDB_POL_P_ALPHA]; c.sigma = (T)p[TSIDB_POL_P_SIGMA]; c.h_target = (T)p[TSIDB_POL_P_H_TARGET];
+  c.t_air = (T)p[TSIDB_POL_P_T_AIR]; c.deadband = (T)p[TSIDB_POL_P_DEADBAND]; c.air_dt = (T)(p[TSIDB_POL_P_DECIMATION] * h->params[P_DT]);
+  c.done_height = (T)h->params[P_DONE_HEIGHT]; c.done_tilt = (T)h->params[P_DONE_TILT];
+  for (int k = 0; k < POL_NT; k++) c.w[k] = (T)p[TSIDB_POL_P_WEIGHTS + k];
+  for (int a = 0; a < NA; a++) { c.scale[a] = (T)h->pol_scale[a]; c.def[a] = (T)h->pol_def[a]; }
+  for (int i = 0; i < 3; i++) { c.cmd_lo[i] = p[TSIDB_POL_P_CMD_LO + i]; c.cmd_hi[i] = p[TSIDB_POL_P_CMD_HI + i]; }
+  c.seed = (unsigned long long)p[TSIDB_POL_P_SEED]; c.foot_geoms[0] = h->foot_geoms[0]; c.foot_geoms[1] = h->foot_geoms[1];
+  c.term_mask = h->pol_mask; c.max_steps = (int)p[TSIDB_POL_P_MAX_EPISODE_STEPS]; c.position_mode = h->ctrl_mode == TSIDB_CTRL_POSITION;
+  return c;
+}
+
+// what every tsidb_policy_* launch needs first; returns the buffers in the path's type
+template <typename T>
+static PolicyBufs<T> policy_bufs(tsidb_ctx *h, const tsidb_policy_bufs *b, const char *who) {
+  if (lacks_sim(h, true, who)) throw h->err;
+  if (!h->ctrl) throw std::string(who) + "no ctrl buffer registered (call tsidb_set_ctrl first)";
+  if (!h->pol_set) throw std::string(who) + "not configured (call tsidb_policy_config first)";
+  if (!b || !b->act_hist || !b->last_action || !b->prev_action || !b->command || !b->air_time || !b->ep_len || !b->episode || !b->terms || !b->timeout)
+    throw std::string(who) + "null buffer in tsidb_policy_bufs";
+  if (b->obs && b->obs_ld < POL_NOBS + POL_NPRIV) throw std::string(who) + "obs row stride must be at least TSIDB_POL_NOBS + TSIDB_POL_NPRIV";
+  return PolicyBufs<T>{(T *)b->act_hist, (T *)b->last_action, (T *)b->prev_action, (T *)b->command, (T *)b->air_time, b->ep_len, b->episode,
+                       b->delay, (T *)b->terms, b->timeout, (T *)b->obs, b->obs_ld};
+}
+
+static dim3 policy_grid(const tsidb_ctx *h) { return dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK); }
+
+extern "C" {
+
+int tsidb_policy_config(tsidb_handle h, const double *pol_params, int n_params, const double *scale, const double *default_pos,
+                        uint32_t term_body_mask) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_config: ";
+  if (lacks_sim(h, true, who)) throw h->err;
+  if (!pol_params || n_params != TSIDB_POL_NPARAMS || !scale || !default_pos) throw std::string(who) + "needs TSIDB_POL_NPARAMS parameters, scale [NA] and default_pos [NA]";
+  for (int i = 0; i < n_params; i++) if (!std::isfinite(pol_params[i])) throw std::string(who) + "non-finite parameter";
+  for (int a = 0; a < NA; a++) if (!std::isfinite(scale[a]) || !std::isfinite(default_pos[a])) throw std::string(who) + "non-finite scale or default position";
+  const double *p = pol_params;
+  if (p[TSIDB_POL_P_CLIP] < 0) throw std::string(who) + "clip must be >= 0";
+  if (!(p[TSIDB_POL_P_ALPHA] > 0 && p[TSIDB_POL_P_ALPHA] <= 1)) throw std::string(who) + "alpha must be in (0, 1]";
+  if (!(p[TSIDB_POL_P_SIGMA] > 0)) throw std::string(who) + "sigma must be positive";
+  if (p[TSIDB_POL_P_DECIMATION] < 1 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] < 0 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] > 2147483647.0 || p[TSIDB_POL_P_SEED] < 0)
+    throw std::string(who) + "decimation must be >= 1, max_episode_steps 0 .. 2^31 - 1, seed >= 0";
+  for (int i = 0; i < 3; i++) if (p[TSIDB_POL_P_CMD_LO + i] > p[TSIDB_POL_P_CMD_HI + i]) throw std::string(who) + "command range: lo > hi";
+  if (NB < 32 && (term_body_mask >> NB)) throw std::string(who) + "term_body_mask names a body the robot does not have";
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->pol, pol_params, sizeof h->pol);
+  memcpy(h->pol_scale, scale, sizeof h->pol_scale);
+  memcpy(h->pol_def, default_pos, sizeof h->pol_def);
+  h->pol_mask = term_body_mask;
+  h->pol_set = true;
+  GUARD_END
+}
+
+int tsidb_policy_act(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *action, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_act: ");
+    if (!action) throw std::string("tsidb_policy_act: null action");
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_act<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, policy_cfg<T>(h), b, (const T *)action, (T *)h->ctrl);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_reward(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, const void *qvel, const int32_t *ncon,
+                        const int32_t *con_pairs, const int32_t *info, void *reward, void *done, int row_ld, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_reward: ");
+    if (!qpos || !qvel || !ncon || !con_pairs || !info || !reward || !done || row_ld < 1) throw std::string("tsidb_policy_reward: null buffer or row stride < 1");
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_reward<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
+                       policy_cfg<T>(h), b, (const T *)qpos, (const T *)qvel, ncon, con_pairs, info, (const T *)h->ro[3], (T *)reward, (T *)done, row_ld);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
+                     const void *qvel, const int32_t *ncon, const int32_t *con_pairs, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_obs: ");
+    if (!done_rows || rows_ld < NROW) throw std::string("tsidb_policy_obs: needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)");
+    if (!qpos || !qvel || !ncon || !con_pairs) throw std::string("tsidb_policy_obs: null buffer");
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_obs<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
+                       policy_cfg<T>(h), b, (const T *)done_rows, rows_ld, (const T *)qpos, (const T *)qvel, ncon, con_pairs, (T *)h->ctrl);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+} // extern "C"
 
 extern "C" {
 

@@ -122,6 +122,15 @@ struct DevModel {
   T site_pos[MAXSITE][3], site_R[MAXSITE][9];
 };
 
+// per-env random draws on the device (the episode plan, the policy environment's commands): SplitMix64 of (seed, env, episode)
+__device__ __forceinline__ unsigned long long plan_hash(unsigned long long seed, unsigned long long env, unsigned long long episode) {
+  unsigned long long x = seed ^ (env * 0x9E3779B97F4A7C15ull) ^ (episode * 0xD1B54A32D192ED03ull);
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 // ------------------------------------------------------------------ small vector helpers
 template <typename T> __device__ __forceinline__ void cross3(const T *a, const T *b, T *c) {
   T x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];

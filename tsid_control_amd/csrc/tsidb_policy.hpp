@@ -1,0 +1,216 @@
+// tsidb_policy.hpp - the environment around a policy-driven sim loop (include/tsidb.h tsidb_policy_*): action -> ctrl
+// before the sim steps, reward / termination after them, bookkeeping of the restarted envs and the observation row after the
+// reset.  No reference counterpart: the reference runs one TSID-driven episode (main.py:113-124).
+//
+// Shape of all three kernels, as k_reset: one wavefront per env, lane = column of the env's rows (coalesced row loads and
+// stores), wave reductions (DPP) for the sums over actuators and wave votes for the flags over contacts; four envs per
+// workgroup, no LDS, no barrier.  Everything an env needs is a few hundred bytes: the kernels are launch- and latency-bound,
+// and a wavefront per env keeps every load of a row one transaction.
+#pragma once
+#include "tsidb_common.hpp"
+
+namespace tsidb {
+
+constexpr int POL_NT = 12;              // reward terms (TSIDB_POL_NT)
+constexpr int POL_HIST = 8;             // slots of the action history ring (TSIDB_POL_HIST): delays of 0 .. 7 policy steps
+constexpr int POL_NOBS = 11 + 3 * NA;   // observation columns (TSIDB_POL_NOBS for the v1 robot)
+constexpr int POL_NPRIV = 4;            // privileged tail: base linear velocity (body frame), base height
+constexpr int POL_ENVS_PER_BLOCK = 4;
+enum { POL_T_TRACK_LIN = 0, POL_T_TRACK_ANG, POL_T_LIN_VEL_Z, POL_T_ANG_VEL_XY, POL_T_ORIENTATION, POL_T_BASE_HEIGHT, POL_T_TORQUES,
+       POL_T_ACTION_RATE, POL_T_JOINT_VEL, POL_T_FEET_AIR_TIME, POL_T_ALIVE, POL_T_TERMINATION };
+
+// tsidb_policy_config's values in the path's arithmetic type, passed to the kernels by value
+template <typename T>
+struct PolicyCfg {
+  T clip, alpha, sigma, h_target, t_air, deadband, air_dt /* decimation * dt */, done_height, done_tilt;
+  T w[POL_NT], scale[NA], def[NA];
+  double cmd_lo[3], cmd_hi[3];
+  unsigned long long seed, foot_geoms[2];
+  unsigned term_mask;
+  int max_steps, position_mode;
+};
+
+// tsidb_policy_bufs in the path's arithmetic type
+template <typename T>
+struct PolicyBufs {
+  T *hist, *last, *prev, *command, *air;
+  int *ep_len, *episode;
+  const int *delay;
+  T *terms;
+  int *timeout;
+  T *obs;
+  int obs_ld;
+};
+
+// the env of this wavefront (-1: none); wave-uniform, and said so to the compiler: row bases become scalar registers
+__device__ __forceinline__ int pol_env(int n) {
+  const int e = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * POL_ENVS_PER_BLOCK + (threadIdx.x >> 6)));
+  return e < n ? e : -1;
+}
+
+// lanes 0 .. 31 look at one row of the contact list each: bit 0 / 1 = a live floor contact on the left / right sole, bit 2 = one
+// on a body of term_mask; the same bits on every lane
+template <typename T>
+__device__ __forceinline__ int pol_contacts(const DevModel<T> &m, const PolicyCfg<T> &c, const int *ncon, const int *con_pairs, size_t E, int lane) {
+  bool lf = false, rf = false, tb = false;
+  if (lane < MAXCON && lane < ncon[E]) {
+    const int cp = con_pairs[E * MAXCON + lane];
+    const int g = cp >> 16;
+    if (cp >= 0 && !(cp & 0x8000) && g < NG) {   // live floor row
+      lf = (c.foot_geoms[0] >> g) & 1ull;
+      rf = (c.foot_geoms[1] >> g) & 1ull;
+      tb = (c.term_mask >> m.geom_body[g]) & 1u;
+    }
+  }
+  return (__any(lf) ? 1 : 0) | (__any(rf) ? 2 : 0) | (__any(tb) ? 4 : 0);
+}
+
+// ---------------------------------------------------------------------------- action -> ctrl (before the sim steps)
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_act(int n, PolicyCfg<T> c, PolicyBufs<T> b, const T *__restrict__ action, T *ctrl) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= NA) return;
+  const size_t E = (size_t)e, row = E * NA + lane, slab = (size_t)n * NA;
+  const int len = b.ep_len[E];
+  int d = b.delay ? b.delay[E] : 0;
+  d = d < 0 ? 0 : d > POL_HIST - 1 ? POL_HIST - 1 : d;
+  const T a = action[row];
+  const T act = a > c.clip ? c.clip : a < -c.clip ? -c.clip : a;   // (NaN passes: the sim step then skips the env)
+  b.hist[(size_t)(len & (POL_HIST - 1)) * slab + row] = act;
+  T delayed = act;
+  if (d > len) delayed = 0;
+  else if (d > 0) delayed = b.hist[(size_t)((len - d) & (POL_HIST - 1)) * slab + row];   // (this lane wrote it d steps ago)
+  const T target = c.def[lane] + c.scale[lane] * delayed;
+  const T old = ctrl[row];
+  ctrl[row] = c.alpha == T(1) ? target : old + c.alpha * (target - old);
+  b.prev[row] = b.last[row];
+  b.last[row] = act;
+}
+
+// ---------------------------------------------------------------------------- reward / done (after the sim steps)
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_reward(const DevModel<T> *__restrict__ mp, int n, PolicyCfg<T> c, PolicyBufs<T> b,
+                                                                             const T *__restrict__ qpos, const T *__restrict__ qvel, const int *__restrict__ ncon,
+                                                                             const int *__restrict__ con_pairs, const int *__restrict__ info,
+                                                                             const T *__restrict__ act_force, T *reward, T *done, int row_ld) {
+  const DevModel<T> &m = *mp;
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  const T *qp = qpos + E * NQ, *qv = qvel + E * NV;
+  // the state, a lane per column: finite?
+  const T myq = lane < NQ ? qp[lane] : T(0), myv = lane < NV ? qv[lane] : T(0);
+  const bool finite = !__any(!isfinite(myq) || !isfinite(myv));
+  // sums over the actuators
+  T tq = 0, ar = 0, jv = 0;
+  if (lane < NA) {
+    const T f = act_force ? act_force[E * NA + lane] : T(0), da = b.last[E * NA + lane] - b.prev[E * NA + lane], qd = qv[m.mj_act_dof[lane]];
+    tq = f * f; ar = da * da; jv = qd * qd;
+  }
+  wave_sum3(tq, ar, jv);
+  const int con = pol_contacts(m, c, ncon, con_pairs, E, lane);
+  // the base: every lane the same values
+  T R[9];
+  quat_to_R(qp[4], qp[5], qp[6], qp[3], R);   // wxyz storage
+  const T vx = R[0] * qv[0] + R[3] * qv[1] + R[6] * qv[2], vy = R[1] * qv[0] + R[4] * qv[1] + R[7] * qv[2],
+          vz = R[2] * qv[0] + R[5] * qv[1] + R[8] * qv[2];
+  const T wx = qv[3], wy = qv[4], wz = qv[5];
+  const T cx = b.command[E * 3], cy = b.command[E * 3 + 1], cw = b.command[E * 3 + 2];
+  const T ex = cx - vx, ey = cy - vy, ew = cw - wz, s2 = c.sigma * c.sigma, dz = qp[2] - c.h_target;
+  const bool moving = sqrt(cx * cx + cy * cy) > c.deadband;
+  const T air0 = b.air[E * 2], air1 = b.air[E * 2 + 1];
+  const bool c0 = con & 1, c1 = con & 2;
+  T fa = 0;
+  if (moving && c0 && air0 > T(0)) fa += air0 - c.t_air;
+  if (moving && c1 && air1 > T(0)) fa += air1 - c.t_air;
+  const int len = b.ep_len[E];
+  const T up = 1 - 2 * (qp[4] * qp[4] + qp[5] * qp[5]);   // the tick's tilt measure, on the sim quaternion
+  const bool terminated = (info[E * 4 + 3] & 4) || !finite || qp[2] < c.done_height || up < c.done_tilt || (con & 4);
+  const bool timeout = !terminated && c.max_steps > 0 && len + 1 >= c.max_steps;
+  T t[POL_NT];
+  t[POL_T_TRACK_LIN] = exp(-(ex * ex + ey * ey) / s2);
+  t[POL_T_TRACK_ANG] = exp(-(ew * ew) / s2);
+  t[POL_T_LIN_VEL_Z] = vz * vz;
+  t[POL_T_ANG_VEL_XY] = wx * wx + wy * wy;
+  t[POL_T_ORIENTATION] = R[6] * R[6] + R[7] * R[7];   // projected gravity = -(third row of R)
+  t[POL_T_BASE_HEIGHT] = dz * dz;
+  t[POL_T_TORQUES] = tq;
+  t[POL_T_ACTION_RATE] = ar;
+  t[POL_T_JOINT_VEL] = jv;
+  t[POL_T_FEET_AIR_TIME] = fa;
+  t[POL_T_ALIVE] = 1;
+  t[POL_T_TERMINATION] = terminated ? T(1) : T(0);
+  T rew = 0, mine = 0;
+#pragma unroll
+  for (int k = 0; k < POL_NT; k++) {
+    rew += c.w[k] * t[k];
+    mine = lane == k ? t[k] : mine;
+  }
+  if (lane < POL_NT) b.terms[E * POL_NT + lane] = mine;
+  if (lane < 2) b.air[E * 2 + lane] = (lane ? c1 : c0) ? T(0) : (lane ? air1 : air0) + c.air_dt;
+  if (lane == 0) {
+    reward[E * row_ld] = rew;
+    done[E * row_ld] = terminated || timeout ? T(1) : T(0);
+    b.timeout[E] = timeout ? 1 : 0;
+    b.ep_len[E] = len + 1;
+  }
+}
+
+// ---------------------------------------------------------------------------- restarted envs + observation (after the reset)
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_obs(const DevModel<T> *__restrict__ mp, int n, PolicyCfg<T> c, PolicyBufs<T> b,
+                                                                          const T *__restrict__ done_rows, int rows_ld, const T *__restrict__ qpos,
+                                                                          const T *__restrict__ qvel, const int *__restrict__ ncon,
+                                                                          const int *__restrict__ con_pairs, T *ctrl) {
+  const DevModel<T> &m = *mp;
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  const bool fresh = done_rows[E * rows_ld + NROW - 1] != T(0);   // (the done column, NOBS + 1)
+  int con = pol_contacts(m, c, ncon, con_pairs, E, lane);
+  T last = lane < NA ? b.last[E * NA + lane] : T(0);
+  T cmd = lane < 3 ? b.command[E * 3 + lane] : T(0);
+  if (fresh) {
+    con = 3;   // (the reset leaves ncon and con_pairs of the fallen robot: a restarted env stands on both feet)
+    last = 0;
+    if (lane < NA) {
+      const size_t row = E * NA + lane, slab = (size_t)n * NA;
+#pragma unroll
+      for (int s = 0; s < POL_HIST; s++) b.hist[(size_t)s * slab + row] = 0;
+      b.last[row] = 0;
+      b.prev[row] = 0;
+      if (c.position_mode) ctrl[row] = c.def[lane];   // (the filter starts at the default pose; k_reset left 0)
+    }
+    if (lane < 2) b.air[E * 2 + lane] = 0;
+    const int ep = b.episode[E] + 1;
+    if (lane == 0) { b.ep_len[E] = 0; b.episode[E] = ep; }
+    if (lane < 3 && c.cmd_lo[lane] != c.cmd_hi[lane]) {
+      const double u = (double)(plan_hash(c.seed + (unsigned long long)lane, (unsigned long long)e, (unsigned long long)ep) >> 11) * (1.0 / 9007199254740992.0);
+      cmd = (T)(c.cmd_lo[lane] + (c.cmd_hi[lane] - c.cmd_lo[lane]) * u);
+      b.command[E * 3 + lane] = cmd;
+    }
+  }
+  if (!b.obs) return;
+  const T *qp = qpos + E * NQ, *qv = qvel + E * NV;
+  T R[9];
+  quat_to_R(qp[4], qp[5], qp[6], qp[3], R);   // wxyz storage
+  T *o = b.obs + E * b.obs_ld;
+  if (lane < 3) {
+    const T g = lane == 0 ? R[6] : lane == 1 ? R[7] : R[8], r0 = lane == 0 ? R[0] : lane == 1 ? R[1] : R[2],
+            r1 = lane == 0 ? R[3] : lane == 1 ? R[4] : R[5];
+    o[lane] = qv[3 + lane];                    // base angular velocity: body frame as stored
+    o[3 + lane] = -g;                          // R^T (0, 0, -1)
+    o[6 + lane] = cmd;
+    o[POL_NOBS + lane] = r0 * qv[0] + r1 * qv[1] + g * qv[2];   // privileged: R^T v
+  }
+  if (lane < NA) {
+    const int dof = m.mj_act_dof[lane];
+    o[9 + lane] = qp[dof + 1] - c.def[lane];
+    o[9 + NA + lane] = qv[dof];
+    o[9 + 2 * NA + lane] = last;
+  }
+  if (lane < 2) o[9 + 3 * NA + lane] = (con >> lane) & 1 ? T(1) : T(0);
+  if (lane == 3) o[POL_NOBS + 3] = qp[2];
+}
+
+} // namespace tsidb
