@@ -36,7 +36,8 @@ else:
 torch.cuda.synchronize()
 L = _lib.load()
 n = min(N, 8192)
-buf = np.zeros((n, 32), dtype=np.uint64)
+NSTAMP = 48   # tsidb_common.hpp
+buf = np.zeros((n, NSTAMP), dtype=np.uint64)
 L.tsidb_debug_stamps.argtypes = [C.c_void_p, C.c_int]
 rc = L.tsidb_debug_stamps(buf.ctypes.data_as(C.c_void_p), n)
 assert rc == 0
@@ -74,5 +75,14 @@ for nm, ix in zip(names_s, idx_s):
     d = np.median(b[:, ix[1]] - b[:, ix[0]])
     print(f"  {nm:24s} {d:10.0f} cyc  {100*d/tot:5.1f}%")
 print(f"  {'total':24s} {tot:10.0f} cyc")
-for nm, k in (("  newton: eval+grad", 24), ("  newton: Hessian build", 25), ("  newton: chol+solve", 26), ("  newton: line search+move", 27)):
+for nm, k in (("  newton: eval+grad", 24), ("  newton: Hessian build (tail: see the fixed phases below)", 25), ("  newton: chol+solve", 26), ("  newton: line search+move", 27)):
     print(f"{nm:26s} {np.median(b[:, k]):10.0f} cyc (sum over iterations)")
+# the fixed phases of k_sim (DESIGN.md section 5 "Fixed phases of k_sim"): the collision phase's look-ups and the pieces of a full Hessian build
+print("k_sim fixed phases:")
+for nm, ix in (("  floor search", (18, 32)), ("  bounding spheres of the geoms", (32, 33)), ("  sphere rounds", (33, 34)), ("  box pass", (34, 35)),
+               ("  narrow phase + hand-over", (35, 19))):
+    print(f"{nm:34s} {np.median(b[:, ix[1]] - b[:, ix[0]]):10.0f} cyc")
+for nm, k in (("  hessian: W + stage 1 (group sums)", 36), ("  hessian: stage 2 (all-body K)", 37), ("  hessian: G = K S", 38), ("  hessian: M -> H copy + chain walk", 39),
+              ("  hessian: friction diagonal, robot<->robot", 25)):
+    print(f"{nm:42s} {np.median(b[:, k]):10.0f} cyc (sum over the step's full builds)")
+print(f"{'  hessian: full builds, all pieces':42s} {np.median(b[:, [25, 36, 37, 38, 39]].sum(axis=1)):10.0f} cyc")

@@ -270,13 +270,17 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
     const size_t slot = (size_t)((ring.slots >> (4 * b)) & 15ull);
     const T *q_tsid = ring.q ? ring.q + slot * (size_t)n * NQ : nullptr, *v_tsid = ring.v ? ring.v + slot * (size_t)n * NV : nullptr;
     bool skip;
+    SimIn<T> in{};
     {
       // non-finite sim state / targets, or a sim state that has diverged (sum of |qpos| + |qvel| beyond SIM_STATE_BOUND:
       // the reference's own loop gets there, its teleported sim accumulates velocity until the contact forces explode -
       // and products of such values overflow to inf / NaN inside the step): skip the step, failure bit 4 in info[3]
+      // (the values loaded here are the ones the step stages: sim_step_env takes them, it does not read the rows again)
       T chk = 0, big = 0;
-      if (lane < NQ) { big += fabs(qpos[E * NQ + lane]); chk += q_tsid ? fabs(q_tsid[E * NQ + lane]) : T(0); }
-      if (lane < NV) { big += fabs(qvel[E * NV + lane]); chk += fabs(qacc_ws[E * NV + lane]) + (v_tsid ? fabs(v_tsid[E * NV + lane]) : T(0)); }
+      if (lane < NQ) { in.qpos = qpos[E * NQ + lane]; if (q_tsid) in.qt = q_tsid[E * NQ + lane]; }
+      if (lane < NV) { in.qvel = qvel[E * NV + lane]; if (v_tsid) in.vt = v_tsid[E * NV + lane]; }
+      if (lane < NQ) { big += fabs(in.qpos); chk += q_tsid ? fabs(in.qt) : T(0); }
+      if (lane < NV) { big += fabs(in.qvel); chk += fabs(qacc_ws[E * NV + lane]) + (v_tsid ? fabs(in.vt) : T(0)); }
       if (lane < NA && motor_tau) chk += fabs(motor_tau[E * NA + lane]);
       if constexpr (XF) for (int i = lane; i < NB * 6; i += WAVE) chk += fabs(xfrc[E * NB * 6 + i]); // (external wrenches)
       if constexpr (CT) { if (lane < NA) chk += fabs(ctrl[E * NA + lane]); } // (direct actuator control)
@@ -293,7 +297,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(WPE))
       }
     }
     if (!skip)
-      sim_step_env<T, NW, XF, RO, SE, CT>(*mq, L, lane, wv, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
+      sim_step_env<T, NW, XF, RO, SE, CT>(*mq, L, lane, wv, in, q_tsid ? q_tsid + E * NQ : nullptr, v_tsid ? v_tsid + E * NV : nullptr, qpos + E * NQ, qvel + E * NV, qacc_ws + E * NV,
                           env_params ? env_params + E * 8 : nullptr, terrain ? terrain + E * 20 : nullptr, XF ? xfrc + E * NB * 6 : nullptr,
                           motor_tau ? motor_tau + E * NA : nullptr, qacc ? qacc + E * NV : nullptr, ncon ? ncon + e : nullptr, con ? con + E * MAXCON : nullptr,
                           info ? info + E * 4 : nullptr, roe, CT ? ctrl + E * NA : nullptr, ctrl_mode);
@@ -885,8 +889,9 @@ static void build_model(tsidb_ctx *h, DevModel<T> &m) {
     const int *pp = b.i32("mj_pairs", 0);
     m.npair = (int)(np2 / 2);
     for (int k = 0; k < m.npair; k++) {
-      m.pair_a[k] = pp[2 * k]; m.pair_b[k] = pp[2 * k + 1];
       if (pp[2 * k] < 0 || pp[2 * k] >= NG || pp[2 * k + 1] < 0 || pp[2 * k + 1] >= NG) throw std::string("model blob: bad geom pair");
+      // (geoms and bodies fit a byte each: NB <= NG <= 64; geom_body was range-checked above)
+      m.pair_pk[k] = (unsigned)pp[2 * k] | (unsigned)pp[2 * k + 1] << 8 | (unsigned)m.geom_body[pp[2 * k]] << 16 | (unsigned)m.geom_body[pp[2 * k + 1]] << 24;
     }
     const double *hc = b.f64("mj_hull_center", NG * 3), *hb = b.f64("mj_hull_box", NG * 6);
     for (int i = 0; i < NG * 3; i++) m.hcen[i / 3][i % 3] = (T)hc[i];
@@ -1583,7 +1588,7 @@ int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void 
 
 #ifdef TSIDB_STAMPS
 int tsidb_debug_stamps(unsigned long long *out, int n) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 32 * (size_t)n);
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * NSTAMP * (size_t)n);
 }
 #endif
 

@@ -6,7 +6,8 @@
 
 #ifdef TSIDB_STAMPS
 // diagnostic build only (tools/stamp_profile.py): shader-clock stamps per phase, never in the product .so
-__device__ unsigned long long g_stamp[8192][32];
+constexpr int NSTAMP = 48; // slots per workgroup: 0-15 k_tick, 16-31 k_sim, 32-39 k_sim's fixed phases (collision look-ups, Hessian build)
+__device__ unsigned long long g_stamp[8192][NSTAMP];
 #define TSIDB_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_stamp[blockIdx.x][k] = __builtin_amdgcn_s_memtime(); } while (0)
 // accumulate the time since the previous TSIDB_LAP into slot k (for phases inside loops)
 #define TSIDB_LAP_INIT() unsigned long long lap_t_ = __builtin_amdgcn_s_memtime()
@@ -114,7 +115,8 @@ struct DevModel {
   const int *hull_eadr, *hull_edge;
   // robot<->robot collision: candidate body pairs (after excludes and the parent-child filter), the hulls'
   // centres of mass and body-frame bounding boxes (centre, half extents)
-  int npair, pair_a[MAXPAIR], pair_b[MAXPAIR]; // geom pairs
+  int npair;
+  unsigned pair_pk[MAXPAIR]; // candidate geom pairs, one packed word each (derived at load): geom a | geom b << 8 | body of a << 16 | body of b << 24
   T hcen[NG][3], hbox[NG][6];
   // site sensors (tsidb_set_sensors): body, position and orientation (row-major) of each site in its body's frame.  Last in the
   // block: the offsets of everything above are those of a library without them

@@ -34,7 +34,8 @@ struct SimLds {
   union { // tree-pass scratch is dead once bias forces and M exist; the Newton loop reuses the space
     struct { T V[NB][6], A[NB][6], f[NB][6], Yc[NB][10]; };
     struct {
-      T K[NB][21];      // per-body contact inertia (packed sym 6x6), composite over subtrees (Newton loop)
+      T K[NB][21];      // Newton loop scratch: the gradient's per-group wrenches, the robot<->robot g_k staging (the composite
+                        // contact inertias it was sized for are summed in registers now, never stored)
       T hn[MAXHH][3];   // robot<->robot contacts: normal (geom1 -> geom2); copied here from the staging below once the
       int hb1[MAXHH];   //                        collision phase is over; body of geom1
     };
@@ -47,8 +48,8 @@ struct SimLds {
       // collision-time scratch BEHIND the body frames (dead before the Newton loop writes Wc / H).  It used to overlay the
       // tree-pass scratch; here it also survives the two-wavefront variant, where the collision phase runs beside the
       // bias / mass-matrix phase that still reads f and Yc.
-      int fcand[64];    // candidate pairs that passed the sphere and the box test: the narrow phase's work list
-      int pcand[128];   // candidate pairs that passed the bounding-sphere test (a batch list)
+      int fcand[64];    // candidate pairs (their packed words, DevModel::pair_pk) that passed the sphere and the box test: the narrow phase's work list
+      int pcand[128];   // candidate pairs (packed words) that passed the bounding-sphere test (a batch list)
       T terr[20];       // stepped-terrain table of this env
       T scen[NG][4];    // bounding spheres of the geoms in the world (relative to O): centre, radius
       T hn_s[MAXHH][3]; // narrow-phase output (staging of hn / hb1)
@@ -466,15 +467,33 @@ template <typename T> __device__ __forceinline__ T terrain_h(const T *terr, T X,
 // if its lower bound does not exceed the best value found so far, and every such chunk is scanned, so the result
 // equals the exhaustive search.  TERR: Rw = the body's world rotation, (px, py) = its world position; the lower
 // bound then subtracts the highest terrain cell the chunk's box can reach.
+// What a hull search reads first about its geom: the vertex range, the number of chunks and the lane's chunk box (lane =
+// chunk) - a scalar table look-up and a dependent global load.  Loaded apart from the search, so that the floor loop can
+// have the NEXT candidate's in flight while the current candidate is searched.
+template <typename T> struct HullHead { int v0, v1, nch; T bx[6]; };
+template <typename T> __device__ __forceinline__ HullHead<T> hull_head(const DevModel<T> &m, int lane, int b) {
+  HullHead<T> h;
+  h.v0 = m.hull_adr[b]; h.v1 = m.hull_adr[b + 1];
+  const int c0 = m.chunk_adr[b];
+  h.nch = m.chunk_adr[b + 1] - c0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) h.bx[i] = 0;
+  if (lane < h.nch) {
+    const T *bx = m.chunk_box + 6 * (c0 + lane);
+#pragma unroll
+    for (int i = 0; i < 6; i++) h.bx[i] = bx[i];
+  }
+  return h;
+}
+
 template <typename T, bool TERR>
-__device__ __forceinline__ int hull_argmin(const DevModel<T> &m, int lane, int b, T r6, T r7, T r8, T pz, T tie, const T *terr,
+__device__ __forceinline__ int hull_argmin(const DevModel<T> &m, int lane, const HullHead<T> &hd, T r6, T r7, T r8, T pz, T tie, const T *terr,
                                            const T *Rw, T px, T py, T hmax_all, T &zmin_out) {
   const T INF = Eps<T>::inf;
-  const int v0 = m.hull_adr[b], v1 = m.hull_adr[b + 1];
-  const int c0 = m.chunk_adr[b], nch = m.chunk_adr[b + 1] - c0;
+  const int v0 = hd.v0, v1 = hd.v1, nch = hd.nch;
   T zlb = INF;
   if (lane < nch) {
-    const T *bx = m.chunk_box + 6 * (c0 + lane);
+    const T *bx = hd.bx;
     zlb = r6 * bx[0] + r7 * bx[1] + r8 * bx[2] + pz - (fabs(r6) * bx[3] + fabs(r7) * bx[4] + fabs(r8) * bx[5]);
     zlb -= fabs(zlb) * T(4) * Eps<T>::v; // rounding slack: never prune a chunk that could matter
     if constexpr (TERR) {
@@ -591,14 +610,13 @@ template <typename T> __device__ __forceinline__ T origin_tri_closest(const T *a
 // support searches per step (hull_argmin: chunk bounds on the lanes, then 64 vertices per scan).
 // Placements L.R / L.p are relative to the base origin O; so is pos.  Returns true with depth >= 0, unit dir
 // (geom1 -> geom2) and pos.
-// a, b: geom indices; their hulls are placed by the bodies that carry them.  margin > 0 (robot/v0/robot.xml:4): each
+// a, b: geom indices; their hulls are placed by the bodies ba, bb that carry them.  margin > 0 (robot/v0/robot.xml:4): each
 // hull is inflated by margin / 2 along the support direction (as mjc_Convex does), the caller takes dist = margin - depth.
 template <typename T>
-__device__ __forceinline__ bool mpr_penetration(const DevModel<T> &m, const SimLds<T> &L, int lane, int a, int b, T margin, T &depth, T *dir_out, T *pos) {
+__device__ __forceinline__ bool mpr_penetration(const DevModel<T> &m, const SimLds<T> &L, int lane, int a, int b, int ba, int bb, T margin, T &depth, T *dir_out, T *pos) {
   const T TOL = sizeof(T) == 8 ? T(1e-10) : T(2e-6), TIE = sizeof(T) == 8 ? T(1e-12) : T(1e-7);
   const T TINY2 = sizeof(T) == 8 ? T(1e-30) : T(1e-20), SIDE = sizeof(T) == 8 ? T(1e-14) : T(1e-9);
   constexpr int MAXIT = 64;
-  const int ba = m.geom_body[a], bb = m.geom_body[b];
   const T *Ra = L.R[ba], *Rb = L.R[bb], *pa = L.p[ba], *pb = L.p[bb];
   auto wvert = [&](const T *R, const T *p, int i, T *w) {
     const T v[3] = {m.hull_x[i], m.hull_y[i], m.hull_z[i]};
@@ -610,8 +628,8 @@ __device__ __forceinline__ bool mpr_penetration(const DevModel<T> &m, const SimL
     T ra[3], rb[3], zz, wa[3], wb[3];
     mat3Tvec(Ra, d, ra);
     mat3Tvec(Rb, d, rb);
-    ia = hull_argmin<T, false>(m, lane, a, -ra[0], -ra[1], -ra[2], T(0), TIE, nullptr, nullptr, T(0), T(0), T(0), zz);
-    ib = hull_argmin<T, false>(m, lane, b, rb[0], rb[1], rb[2], T(0), TIE, nullptr, nullptr, T(0), T(0), T(0), zz);
+    ia = hull_argmin<T, false>(m, lane, hull_head(m, lane, a), -ra[0], -ra[1], -ra[2], T(0), TIE, nullptr, nullptr, T(0), T(0), T(0), zz);
+    ib = hull_argmin<T, false>(m, lane, hull_head(m, lane, b), rb[0], rb[1], rb[2], T(0), TIE, nullptr, nullptr, T(0), T(0), T(0), zz);
     wvert(Ra, pa, ia, wa);
     wvert(Rb, pb, ib, wb);
     v[0] = wa[0] - wb[0]; v[1] = wa[1] - wb[1]; v[2] = wa[2] - wb[2];
@@ -782,8 +800,7 @@ __device__ __forceinline__ bool spheres_overlap(const SimLds<T> &L, int a, int b
   return !(dot3(d, d) > rr * rr);
 }
 template <typename T>
-__device__ __forceinline__ bool boxes_may_touch(const DevModel<T> &m, const SimLds<T> &L, int a, int b, T margin) {
-  const int ba = m.geom_body[a], bb = m.geom_body[b]; // a, b: geoms
+__device__ __forceinline__ bool boxes_may_touch(const DevModel<T> &m, const SimLds<T> &L, int a, int b, int ba, int bb, T margin) { // a, b: geoms; ba, bb: their bodies
   const T *Ra = L.R[ba], *Rb = L.R[bb];
   T ca[3], cb[3], d[3];
   mat3vec(Ra, m.hbox[a], ca);
@@ -1175,8 +1192,12 @@ template <typename T> __device__ __forceinline__ void sim_sensors_zero(const Dev
 // readouts and sensors, and with both.  ctrl_mode (TSIDB_CTRL_POSITION / MOTOR / RESIDUAL) is a run-time value: a uniform scalar that selects
 // between values the step computes anyway, so one instantiation serves the three modes.
 enum { CTRL_POSITION = 1, CTRL_MOTOR = 2, CTRL_RESIDUAL = 3 };
+// the env's state as the kernel's finite / diverged check loaded it, lane = element: qpos[lane], qvel[lane] and, where the step
+// teleports, q_tsid[lane], v_tsid[lane] (zero where there is no such element).  The step stages these values instead of
+// reading the four rows from global memory a second time - one dependent round trip less before the first flop.
+template <typename T> struct SimIn { T qpos, qvel, qt, vt; };
 template <typename T, int NW, bool XF, bool RO, bool SE = false, bool CT = false>
-__device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
+__device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L, int lane, int wv, const SimIn<T> &in, const T *q_tsid, const T *v_tsid, T *qpos_g, T *qvel_g,
                              T *qacc_ws_g, const T *envp, const T *terr_g, const T *xfrc, const T *motor_tau, T *qacc_out, int *ncon_out,
                              int *con_out, int *info, const SimOut<T> &ro, const T *ctrl = nullptr, int ctrl_mode = 0) {
   // per-env randomisation (BASELINE config 5), NULL = nominal: mass scale, contact friction, floor plane
@@ -1203,33 +1224,36 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
 
   TSIDB_STAMP(16);
   // ---- stage state; teleport the base and map joint targets (main.py:192-194)
-  if (lane < NQ) {
-    T val = qpos_g[lane];
+  {
+    // (TSID keeps the base quaternion xyzw, the sim wxyz: element 3 takes q_tsid[6], elements 4..6 take q_tsid[3..5])
+    const T qt_wxyz = __shfl(in.qt, lane == 3 ? 6 : (lane > 0 ? lane - 1 : 0), WAVE);
+    T val = in.qpos;
     if (q_tsid) {
-      if (lane < 3) val = q_tsid[lane];
-      else if (lane < 7) val = quirks ? q_tsid[lane] : (lane == 3 ? q_tsid[6] : q_tsid[lane - 1]);
+      if (lane < 3) val = in.qt;
+      else if (lane < 7) val = quirks ? in.qt : qt_wxyz;
     }
-    L.qpos[lane] = val;
+    if (lane < NQ) L.qpos[lane] = val;
   }
-  if (lane < NV) {
-    T val = qvel_g[lane];
+  {
+    T val = in.qvel;
     if (q_tsid && v_tsid && !quirks && lane < 6) {
       // the base is kinematic in this mode: its velocity comes with its pose (the reference writes
       // qpos[:7] only, main.py:192, which is harmless only while the robot stands still).  TSID: linear
       // and angular velocity in the body frame; sim: linear in the world frame, angular in the body frame.
       if (lane < 3) {
-        const T x = q_tsid[3], y = q_tsid[4], z = q_tsid[5], w = q_tsid[6];
+        const T x = rdlane(in.qt, 3), y = rdlane(in.qt, 4), z = rdlane(in.qt, 5), w = rdlane(in.qt, 6);
         const T r0 = lane == 0 ? 1 - 2 * (y * y + z * z) : lane == 1 ? 2 * (x * y + w * z) : 2 * (x * z - w * y);
         const T r1 = lane == 0 ? 2 * (x * y - w * z) : lane == 1 ? 1 - 2 * (x * x + z * z) : 2 * (y * z + w * x);
         const T r2 = lane == 0 ? 2 * (x * z + w * y) : lane == 1 ? 2 * (y * z - w * x) : 1 - 2 * (x * x + y * y);
-        val = r0 * v_tsid[0] + r1 * v_tsid[1] + r2 * v_tsid[2];
+        val = r0 * rdlane(in.vt, 0) + r1 * rdlane(in.vt, 1) + r2 * rdlane(in.vt, 2);
       } else {
-        val = v_tsid[lane];
+        val = in.vt;
       }
     }
-    L.qvel[lane] = val;
+    if (lane < NV) L.qvel[lane] = val;
   }
-  T myctrl_ = (lane < NA && q_tsid) ? q_tsid[m.mj_ctrl_qidx[lane]] : T(0); // joint target of actuator `lane`
+  const T qt_act = __shfl(in.qt, lane < NA ? m.mj_ctrl_qidx[lane] : 0, WAVE);
+  T myctrl_ = (lane < NA && q_tsid) ? qt_act : T(0); // joint target of actuator `lane`
   if constexpr (CT) {
     // direct actuator control (mj_data.ctrl): the one value the actuation block needs of it.  POSITION: the servo target;
     // MOTOR: the force; RESIDUAL: an offset to the target, or - in a step driven by motor torques - to the torque
@@ -1478,19 +1502,24 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     wsync<NW>();
   }
   const bool pm_rule = m.params[P_PLANE_MESH] != 0; // upstream's plane <-> mesh rule instead of "every neighbour in the margin"
+  // (the candidates' hull heads are loaded one candidate ahead: in double support and at touch-down the second foot's
+  //  table look-ups run beside the first foot's search instead of after it)
+  HullHead<T> head_next = hull_head(m, lane, cand_geoms ? __ffsll((long long)cand_geoms) - 1 : 0);
   for (unsigned long long bm = cand_geoms; bm; bm &= bm - 1) {
     const int g = __ffsll((long long)bm) - 1, b = m.geom_body[g];
+    const HullHead<T> head = head_next;
+    if (bm & (bm - 1)) head_next = hull_head(m, lane, __ffsll((long long)(bm & (bm - 1))) - 1);
     const T *Rb = L.R[b];
     // floor normal in the body frame; "z" below = signed distance to the floor
     const T r6 = fl.n[0] * Rb[0] + fl.n[1] * Rb[3] + fl.n[2] * Rb[6];
     const T r7 = fl.n[0] * Rb[1] + fl.n[1] * Rb[4] + fl.n[2] * Rb[7];
     const T r8 = fl.n[0] * Rb[2] + fl.n[1] * Rb[5] + fl.n[2] * Rb[8];
     const T pz = dot3(fl.n, L.p[b]) + nO;
-    const int v0 = m.hull_adr[g];
+    const int v0 = head.v0;
     T zmin;
-    const int best = has_terr ? hull_argmin<T, true>(m, lane, g, r6, r7, r8, pz, tie_tol, L.terr, Rb, L.p[b][0] + Ow[0],
+    const int best = has_terr ? hull_argmin<T, true>(m, lane, head, r6, r7, r8, pz, tie_tol, L.terr, Rb, L.p[b][0] + Ow[0],
                                                      L.p[b][1] + Ow[1], hmax_all, zmin)
-                              : hull_argmin<T, false>(m, lane, g, r6, r7, r8, pz, tie_tol, nullptr, nullptr, T(0), T(0), T(0), zmin);
+                              : hull_argmin<T, false>(m, lane, head, r6, r7, r8, pz, tie_tol, nullptr, nullptr, T(0), T(0), T(0), zmin);
     if (!(zmin <= margin)) continue; // (also when zmin is NaN)
     // the support vertex, then its hull-graph neighbours within the margin
     const int e0 = m.hull_eadr[best];
@@ -1534,10 +1563,21 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     ncon += __popcll(mask);
     ncon = ncon > MAXCON ? MAXCON : ncon;
   }
+  TSIDB_STAMP(32);
   nfl = ncon; // contacts [0, nfl) are floor contacts (shared frame), [nfl, ncon) robot<->robot ones
   // ---- collision: robot<->robot convex-hull pairs (robot.xml:13-15 after the excludes of :18-52 and the
   //      parent-child filter): mid phase one lane per pair, narrow phase (MPR) one pair at a time on the wave
   if (m.params[P_SELF_COLLISION] != 0) {
+    // the candidate pairs, one packed word each (DevModel::pair_pk: geoms and their bodies, a byte apiece): everything the
+    // three phases below need to know about a pair, in ONE load - issued here, ahead of the sphere hand-over, so that the
+    // table's round trip runs beside it.  The v1 robot (170 pairs) has all its rounds in flight at once; the v0 robot
+    // (1044 pairs) loads one round ahead.  The survivor lists carry the word, not the pair's index.
+    constexpr int PAIR_ROUNDS = MAXPAIR / WAVE;
+    constexpr bool PAIRS_AHEAD = PAIR_ROUNDS <= 4;
+    const int npair = m.npair;
+    unsigned pk[PAIRS_AHEAD ? PAIR_ROUNDS : 1];
+#pragma unroll
+    for (int r = 0; r < (PAIRS_AHEAD ? PAIR_ROUNDS : 1); r++) pk[r] = m.pair_pk[r * WAVE + lane];
     // bounding spheres of all bodies in the world (lane = body)
     if (lane < NG) {
       const int gb = m.geom_body[lane];
@@ -1547,23 +1587,23 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
       L.scen[lane][3] = m.rbound[lane][3];
     }
     wsync<NW>();
+    TSIDB_STAMP(33);
     // broad phase, one lane per pair: sphere test, survivors compacted into a list; the box test then runs on the list
     // 64 entries at a time (once, at the end, for the v1 robot's ~30 survivors; the v0 robot has 1044 pairs)
     int nsph = 0, ncand = 0;
     bool over = false, over64 = false;
     auto box_pass = [&](int cnt) { // pcand[0, cnt) -> survivors appended to fcand, in pair order
-      const int k = lane < cnt ? L.pcand[lane] : 0;
-      const bool may = lane < cnt && boxes_may_touch(m, L, m.pair_a[k], m.pair_b[k], margin);
+      const unsigned w = lane < cnt ? (unsigned)L.pcand[lane] : 0u;
+      const bool may = lane < cnt && boxes_may_touch(m, L, (int)(w & 255u), (int)((w >> 8) & 255u), (int)((w >> 16) & 255u), (int)(w >> 24), margin);
       const unsigned long long mk = __ballot(may);
       const int pos = ncand + __popcll(mk & ((1ull << lane) - 1ull));
-      if (may && pos < WAVE) L.fcand[pos] = k;
+      if (may && pos < WAVE) L.fcand[pos] = (int)w;
       ncand += __popcll(mk);
     };
-    for (int k0 = 0; k0 < m.npair; k0 += WAVE) {
-      const int k = k0 + lane;
-      const bool may = k < m.npair && spheres_overlap(L, m.pair_a[k], m.pair_b[k], margin);
+    auto sphere_round = [&](unsigned w, int k0) { // pairs [k0, k0 + 64), lane's packed word w
+      const bool may = k0 + lane < npair && spheres_overlap(L, (int)(w & 255u), (int)((w >> 8) & 255u), margin);
       const unsigned long long mk = __ballot(may);
-      if (may) L.pcand[nsph + __popcll(mk & ((1ull << lane) - 1ull))] = k; // nsph <= 64 here: the list holds 128
+      if (may) L.pcand[nsph + __popcll(mk & ((1ull << lane) - 1ull))] = (int)w; // nsph <= 64 here: the list holds 128
       nsph += __popcll(mk);
       if (nsph > WAVE) {
         wsync<NW>();
@@ -1574,16 +1614,30 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
         nsph -= WAVE;
         wsync<NW>();
       }
+    };
+    if constexpr (PAIRS_AHEAD) {
+#pragma unroll
+      for (int r = 0; r < PAIR_ROUNDS; r++)
+        if (r * WAVE < npair) sphere_round(pk[r], r * WAVE);
+    } else {
+      unsigned cur = pk[0];
+      for (int k0 = 0; k0 < npair; k0 += WAVE) {
+        const unsigned nxt = k0 + WAVE < MAXPAIR ? m.pair_pk[k0 + WAVE + lane] : 0u; // (the table is MAXPAIR long: in bounds)
+        sphere_round(cur, k0);
+        cur = nxt;
+      }
     }
     wsync<NW>();
+    TSIDB_STAMP(34);
     box_pass(nsph);
     if (ncand > WAVE) { ncand = WAVE; over64 = true; }
     wsync<NW>();
+    TSIDB_STAMP(35);
     for (int ci = 0; ci < ncand; ci++) {
-      const int k = L.fcand[ci];
-      const int ga = m.pair_a[k], gb = m.pair_b[k], a = m.geom_body[ga], b = m.geom_body[gb]; // geoms, their bodies
+      const unsigned w = (unsigned)L.fcand[ci];
+      const int ga = (int)(w & 255u), gb = (int)((w >> 8) & 255u), a = (int)((w >> 16) & 255u), b = (int)(w >> 24); // geoms, their bodies
       T depth, dir[3], pos[3];
-      if (!mpr_penetration(m, L, lane, ga, gb, margin, depth, dir, pos)) continue;
+      if (!mpr_penetration(m, L, lane, ga, gb, a, b, margin, depth, dir, pos)) continue;
       if (ncon - nfl >= MAXHH || ncon >= MAXCON) { over = true; continue; }
       if (lane == 0) {
         L.cbody[ncon] = b;
@@ -1748,6 +1802,7 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
     const bool grouped = nfl > 2;
     unsigned prevbits = 0; // bit 0: this lane's friction row was in its quadratic zone, bit 1 + i: contact row i was active
     TSIDB_LAP_ZERO(24); TSIDB_LAP_ZERO(25); TSIDB_LAP_ZERO(26); TSIDB_LAP_ZERO(27); TSIDB_LAP_ZERO(28);
+    TSIDB_LAP_ZERO(36); TSIDB_LAP_ZERO(38); TSIDB_LAP_ZERO(39);
     TSIDB_LAP_INIT();
     while (true) {
       // ---- constraint state at the current point: forces, active rows, cost
@@ -1917,10 +1972,11 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
       }
       wsync<NW>();
       // composite contact inertia K[a] = sum of the contact inertias of every body in a's subtree.  Contacts arrive grouped
-      // by body.  Stage 1: lane e sums entry e over each group, in place (the group's first contact keeps the sum).  Stage 2:
-      // the 21 NB entries of K are dealt to the lanes, each adds up the groups whose body has `a` among its ancestors -
-      // plain loads and one store per entry (the first version pushed every group sum to every ancestor with dependent
-      // LDS read-modify-writes, after zeroing K: 3-4 k cycles of latency per build; same sums in the same order)
+      // by body.  Stage 1: lane e sums entry e over each group, in place (the group's first contact keeps the sum).  K itself
+      // is never stored: only the bodies on the contact bodies' root paths are read back, each by the lanes of its own dofs,
+      // so lane k adds up the group sums whose body has k's body among its ancestors in registers - the same additions in
+      // the same order that filled K[body of k] when all 21 NB entries were dealt to the lanes (seven rounds over the
+      // wavefront, each walking cbody -> anc -> Wc per group, and a barrier), from group sums read at wave-uniform addresses
       unsigned touched = 0;
       {
         for (unsigned long long gm = gfirst; gm; gm &= gm - 1) {
@@ -1936,30 +1992,31 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
         }
       }
       wsync<NW>();
-      for (int id = lane; id < NB * 21; id += WAVE) {
-        const int a = id / 21, e = id - 21 * a;
-        T acc = 0;
-        for (unsigned long long gm = gfirst; gm; gm &= gm - 1) {
-          const int cf = __ffsll((long long)gm) - 1;
-          if ((L.anc[L.cbody[cf]] >> a) & 1u) acc += L.Wc[cf][e];
-        }
-        L.K[a][e] = acc;
-      }
-      // (K sits in the tree-pass scratch, Wc in the H region: H is written only after the barrier below)
-      wsync<NW>();
+      TSIDB_LAP(36);
       T Gk[6] = {0, 0, 0, 0, 0, 0};
       const bool mine = lane < NV && ((touched >> (lane < 6 ? 0 : lane - 5)) & 1u);
       if (mine) { // G = K[body of dof k] S_k, before Wc's space becomes H
         const int k = lane, bk = k < 6 ? 0 : k - 5;
+        T Kk[21];
+#pragma unroll
+        for (int e = 0; e < 21; e++) Kk[e] = 0;
+        for (unsigned long long gm = gfirst; gm; gm &= gm - 1) {
+          const int cf = __ffsll((long long)gm) - 1;
+          if ((L.anc[L.cbody[cf]] >> bk) & 1u) {
+#pragma unroll
+            for (int e = 0; e < 21; e++) Kk[e] += L.Wc[cf][e];
+          }
+        }
 #pragma unroll
         for (int i = 0; i < 6; i++) {
           T sacc = 0;
 #pragma unroll
-          for (int j = 0; j < 6; j++) sacc += L.K[bk][sym_idx(i, j)] * L.S[k][j];
+          for (int j = 0; j < 6; j++) sacc += Kk[sym_idx(i, j)] * L.S[k][j];
           Gk[i] = sacc;
         }
       }
       wsync<NW>();
+      TSIDB_LAP(38);
       for (int i = lane; i < NV * LDM; i += WAVE) L.H[i] = L.M[i];
       wsync<NW>();
       if (mine) { // H[i][k] = H[k][i] = M[i][k] + S_i . G_k for the dofs i <= k on k's root path: written once, by lane k alone
@@ -1980,6 +2037,7 @@ __device__ __forceinline__ void sim_step_env(const DevModel<T> &m, SimLds<T> &L,
         }
       }
       wsync<NW>();
+      TSIDB_LAP(39);
       if (fact) L.H[lane * LDM + lane] += rs.fD;
       wsync<NW>();
       // robot<->robot contacts (rare): H += J^T A J with J = the contact point's relative velocity per unit dof
