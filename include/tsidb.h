@@ -425,6 +425,78 @@ int tsidb_policy_reward(tsidb_handle h, const tsidb_policy_bufs *bufs, const voi
 int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
                      const void *qvel, const int32_t *ncon, const int32_t *con_pairs, void *stream);
 
+/* ---- randomisation of the policy environment: per-episode reset noise, per-step observation noise, pushes and command
+ * resampling, all on the device and all off by default.  No random state is stored anywhere: every draw is
+ *   U = (hash(key, env_offset + env, counter) >> 11) / 2^53   in float64 whatever the path's type,
+ * hash = the one of tsidb_walk_plan and of the restart command draw above, so a draw is a pure function of (seed, stream, column,
+ * env, episode, ep_len): a captured graph replays it, and a batch split over ranks (env_offset = the rank's first env) draws
+ * what the unsplit batch draws.  Symmetric noise is amp (2 U - 1), formed in float64, cast to the path's type, then added.
+ *
+ * Key layout: key = seed + ((stream * 256 + column) * 2^32), seed = TSIDB_POL_DR_SEED below 2^32, stream >= 1, column < 256.  No
+ * two (stream, column) pairs share a key, and none equals the restart command draw's keys TSIDB_POL_P_SEED + (0, 1, 2) while that
+ * seed is below 2^32 as well.  Streams, their column and their counter (episode and ep_len are the env's entries of
+ * tsidb_policy_bufs):
+ *   stream  draw                     column              counter
+ *   1       reset joint position     actuator            the episode about to start (episode + 1 when the kernel runs)
+ *   2       reset joint velocity     actuator            same
+ *   3       reset base lin velocity  component x, y, z   same
+ *   4       reset base ang velocity  component x, y, z   same
+ *   5       reset yaw                -                   same
+ *   6       reset x, y               component x, y      same
+ *   7       observation noise        observation column  episode * 2^32 + ep_len, both as tsidb_policy_obs leaves them
+ *   8       push phase               -                   episode
+ *   9       push magnitude           -                   episode * 2^32 + k, k = the number of the push in the episode
+ *   10      push azimuth             -                   same
+ *   11      command zeroing          -                   episode + k * 2^32, k = the number of the resample (0 = the restart)
+ * The command components themselves keep their keys TSIDB_POL_P_SEED + i and use the counter episode + k * 2^32: resample 0 is
+ * the restart draw described at tsidb_policy_obs.  env_offset enters every draw, that one included. */
+enum {
+  TSIDB_POL_DR_SEED = 0 /* integer in [0, 2^32) */, TSIDB_POL_DR_ENV_OFFSET /* integer in [0, 2^31) */,
+  TSIDB_POL_DR_RESET_JOINT_POS /* rad */, TSIDB_POL_DR_RESET_JOINT_VEL /* rad/s */, TSIDB_POL_DR_RESET_BASE_LIN_VEL /*3, m/s, world*/,
+  TSIDB_POL_DR_RESET_BASE_ANG_VEL = TSIDB_POL_DR_RESET_BASE_LIN_VEL + 3 /*3, rad/s, as qvel stores it*/,
+  TSIDB_POL_DR_RESET_YAW = TSIDB_POL_DR_RESET_BASE_ANG_VEL + 3 /* rad */, TSIDB_POL_DR_RESET_XY /* m */,
+  TSIDB_POL_DR_RESET_LIFT /* m, added to base z, not random */,
+  TSIDB_POL_DR_NOISE_ANG_VEL, TSIDB_POL_DR_NOISE_GRAVITY, TSIDB_POL_DR_NOISE_JOINT_POS, TSIDB_POL_DR_NOISE_JOINT_VEL,
+  TSIDB_POL_DR_PUSH_INTERVAL /* policy steps; 0 = no pushes */, TSIDB_POL_DR_PUSH_DURATION /* policy steps */,
+  TSIDB_POL_DR_PUSH_FORCE_LO /* N */, TSIDB_POL_DR_PUSH_FORCE_HI,
+  TSIDB_POL_DR_COMMAND_INTERVAL /* policy steps; 0 = commands change at restarts only */, TSIDB_POL_DR_COMMAND_ZERO_PROB,
+  TSIDB_POL_DR_NPARAMS
+};
+
+/* Copies dr_params [TSIDB_POL_DR_NPARAMS] (host, float64) into the handle; NULL with n_params 0 switches every group off again
+ * (all values 0, the state of a new handle).  First waits for the kernels in flight, as tsidb_policy_config does.  Rejects a
+ * wrong n_params, non-finite values, a negative amplitude, force, interval, seed or offset, a seed >= 2^32, an offset or interval
+ * >= 2^31, push_duration > push_interval, push_force_lo > push_force_hi and a command_zero_prob outside [0, 1]; nothing of a
+ * rejected vector is taken. */
+int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params);
+
+/* before the sim steps (after or before tsidb_policy_act): the push of this policy step into the torso force xfrc[e, 0, 0:3] of
+ * the buffer registered with tsidb_set_xfrc; every other element of xfrc is the caller's.  Per env, with len = ep_len[e] (the
+ * policy steps completed in the episode: the value before tsidb_policy_reward increments it) and P = push_interval:
+ * phase = floor(U_phase P); for len >= phase, k = (len - phase) / P and r = (len - phase) % P, and the push is active iff
+ * r < push_duration.  An active push is F = m (cos a, sin a, 0) with m = lo + (hi - lo) U_mag(k), a = 2 pi U_azimuth(k), formed
+ * in float64 and cast; an inactive one writes 0.  Written every step.  Fails while no xfrc buffer is registered; launches nothing
+ * and succeeds while push_interval or push_duration is 0. */
+int tsidb_policy_perturb(tsidb_handle h, const tsidb_policy_bufs *bufs, void *stream);
+
+/* after tsidb_reset_done(done_rows, ...) and before tsidb_policy_obs, which then observes the randomised state.  Envs whose done
+ * flag is set, in the sim state the reset wrote: qpos[mj_act_dof[a] + 1] += reset_joint_pos noise, qvel[mj_act_dof[a]] +=
+ * reset_joint_vel noise, qvel[0:3] and qvel[3:6] += their component's noise, qpos[0:2] += reset_xy noise, qpos[2] += reset_lift,
+ * and the base quaternion (wxyz) becomes (c, 0, 0, s) * quat, c = cos(t / 2), s = sin(t / 2) of t = reset_yaw (2 U - 1) formed
+ * in float64 and cast - a rotation about world z - divided by its norm.  A group whose amplitude is 0 adds nothing.  The TSID
+ * state q, v is left as the reset wrote it: the policy environment runs no tick, and a caller that does must copy the state over.
+ * Launches nothing and succeeds while every reset_* value is 0. */
+int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, void *qpos,
+                             void *qvel, void *stream);
+
+/* tsidb_policy_obs with randomisation configured (any noise amplitude, command_interval, command_zero_prob or env_offset non-zero;
+ * otherwise the launch is the unrandomised kernel, bit for bit).  Commands: an env is resampled when it was not restarted,
+ * command_interval > 0, ep_len > 0 and ep_len % command_interval == 0, with k = ep_len / command_interval; a restart is k = 0.
+ * At either, with probability command_zero_prob (U < prob) all three components become 0; otherwise the components with
+ * cmd_lo != cmd_hi are redrawn and the others stay as they are.  Noise: columns 0-2 += noise_ang_vel, 3-5 += noise_gravity,
+ * 9 .. 9 + NA - 1 += noise_joint_pos, 9 + NA .. 9 + 2 NA - 1 += noise_joint_vel draws (stream 7, column = the observation column);
+ * command, last action, contact flags and the privileged tail stay exact, and qpos / qvel are not touched. */
+
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */
 int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void *hbias, void *Jcom, void *Jf,

@@ -9,7 +9,10 @@ part of the load, of
   (c) fused   PolicyEnv.step
 at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the three.
     python tools/policy_env.py [out.json]          (on an MI355X; default profiles/policy_env.json)
-    python tools/policy_env.py --trace ENVS STEPS  (a short run of (c) alone, for rocprofv3 --kernel-trace --stats)"""
+    python tools/policy_env.py --trace ENVS STEPS  (a short run of (c) alone, for rocprofv3 --kernel-trace --stats)
+    python tools/policy_env.py --randomize [out.json]   (c) with every group of the randomisation on (PolicyRandomization: reset
+              noise, observation noise, pushes of at most 1 N, command resampling) against (c) with it off, in alternating
+              windows, at 4096 and 512 envs, decimation 4 and 10; default profiles/policy_dr.json"""
 import json
 import sys
 import time
@@ -152,7 +155,50 @@ def measure(n, decimation, window=300, windows=4, preroll=60):
                 standing_height_min=float(fused.wc.qpos[:, 2].min()))
 
 
+RANDOMIZATION = dict(seed=1, reset_joint_pos=0.05, reset_joint_vel=0.2, reset_base_lin_vel=0.1, reset_base_ang_vel=0.2, reset_yaw=np.pi,
+                     reset_xy=0.5, reset_lift=0.005, noise_ang_vel=0.2, noise_gravity=0.05, noise_joint_pos=0.01, noise_joint_vel=1.5,
+                     push_interval=50, push_duration=5, push_force_lo=0.2, push_force_hi=1.0, command_interval=100, command_zero_prob=0.1)
+
+
+def measure_randomize(n, decimation, window=300, windows=4, preroll=60):
+    """(c) with everything on against (c) with everything off: policy-steps/s in alternating windows of one process"""
+    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    envs = dict(off=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW),
+                on=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, randomization=RANDOMIZATION, **KW))
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, envs["on"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    for env in envs.values():
+        for i in range(preroll):
+            env.step(actions[i & 15])
+    torch.cuda.synchronize()
+    res = {k: [] for k in envs}
+    for w in range(windows):
+        for mode in (("off", "on"), ("on", "off"))[w & 1]:
+            env = envs[mode]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(window):
+                env.step(actions[i & 15])
+            torch.cuda.synchronize()
+            res[mode].append(window / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    us = {k: 1e6 / v for k, v in med.items()}
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
+                us_per_policy_step=us, on_over_off=med["on"] / med["off"], randomisation_us_per_policy_step=us["on"] - us["off"],
+                restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
+                standing_height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--randomize":
+        out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_dr.json"
+        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", randomization=RANDOMIZATION,
+                   runs=[measure_randomize(n, d) for n in (4096, 512) for d in (4, 10)])
+        text = json.dumps(out, indent=1)
+        print(text)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--trace":
         n, k = int(sys.argv[2]), int(sys.argv[3])
         env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=10, **KW)

@@ -13,9 +13,9 @@ def __getattr__(name):
     if name in ("WalkPlanner", "WalkSchedule", "op3_walking_conf", "op3_walking_posture", "op3_closed_loop_walking_conf"):
         from . import walk_planner
         return getattr(walk_planner, name)
-    if name == "PolicyEnv":
-        from .policy_env import PolicyEnv
-        return PolicyEnv
+    if name in ("PolicyEnv", "PolicyRandomization"):
+        from . import policy_env
+        return getattr(policy_env, name)
     if name in ("Footstep", "Support", "FootstepPlanner"):
         from . import footstep_planner
         return getattr(footstep_planner, name)

@@ -13,7 +13,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_tick", "tsidb_sim", "tsidb_step", "tsidb_rbd_terms", "tsidb_lds_bytes", "tsidb_walk_update", "tsidb_set_env_params", "tsidb_set_cop_ref",
            "tsidb_reset_done", "tsidb_set_posture_bias", "tsidb_walk_plan", "tsidb_set_option", "tsidb_tick_walk", "tsidb_sim_batch", "tsidb_stream_create", "tsidb_stream_destroy", "tsidb_get_option",
            "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl",
-           "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs"]
+           "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs",
+           "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -29,6 +30,16 @@ POL_TERMS = ("track_lin_vel", "track_ang_vel", "lin_vel_z", "ang_vel_xy", "orien
 POL_NT, POL_HIST, POL_NPRIV = 12, 8, 4
 POL_P_CLIP, POL_P_ALPHA, POL_P_SIGMA, POL_P_H_TARGET, POL_P_T_AIR, POL_P_DEADBAND, POL_P_MAX_EPISODE_STEPS, POL_P_DECIMATION, \
     POL_P_SEED, POL_P_CMD_LO, POL_P_CMD_HI, POL_P_WEIGHTS, POL_NPARAMS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 15, 27
+
+# tsidb_policy_randomize's parameter vector (include/tsidb.h TSIDB_POL_DR_*), in its order; the two base velocity amplitudes
+# take three slots each (x, y, z)
+POL_DR_FIELDS = ("seed", "env_offset", "reset_joint_pos", "reset_joint_vel", "reset_base_lin_vel", "reset_base_ang_vel", "reset_yaw",
+                 "reset_xy", "reset_lift", "noise_ang_vel", "noise_gravity", "noise_joint_pos", "noise_joint_vel", "push_interval",
+                 "push_duration", "push_force_lo", "push_force_hi", "command_interval", "command_zero_prob")
+POL_DR_SEED, POL_DR_ENV_OFFSET, POL_DR_RESET_JOINT_POS, POL_DR_RESET_JOINT_VEL, POL_DR_RESET_BASE_LIN_VEL, POL_DR_RESET_BASE_ANG_VEL, \
+    POL_DR_RESET_YAW, POL_DR_RESET_XY, POL_DR_RESET_LIFT, POL_DR_NOISE_ANG_VEL, POL_DR_NOISE_GRAVITY, POL_DR_NOISE_JOINT_POS, \
+    POL_DR_NOISE_JOINT_VEL, POL_DR_PUSH_INTERVAL, POL_DR_PUSH_DURATION, POL_DR_PUSH_FORCE_LO, POL_DR_PUSH_FORCE_HI, \
+    POL_DR_COMMAND_INTERVAL, POL_DR_COMMAND_ZERO_PROB, POL_DR_NPARAMS = 0, 1, 2, 3, 4, 7, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23
 
 
 def pol_nobs(na):
@@ -120,6 +131,9 @@ def load(path=None):
     L.tsidb_policy_act.argtypes = [vp, vp, vp, vp]
     L.tsidb_policy_reward.argtypes = [vp, vp, vp, vp, i32p, i32p, i32p, vp, vp, C.c_int, vp]
     L.tsidb_policy_obs.argtypes = [vp, vp, vp, C.c_int, vp, vp, i32p, i32p, vp]
+    L.tsidb_policy_randomize.argtypes = [vp, vp, C.c_int]
+    L.tsidb_policy_perturb.argtypes = [vp, vp, vp]
+    L.tsidb_policy_reset_noise.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -720,6 +720,7 @@ struct tsidb_ctx {
   bool pol_set = false;
   double pol[TSIDB_POL_NPARAMS] = {}, pol_scale[NA] = {}, pol_def[NA] = {};
   unsigned pol_mask = 0;
+  double pol_dr[TSIDB_POL_DR_NPARAMS] = {}; // tsidb_policy_randomize's vector; all 0 = every group off
   std::string err;
 };
 
@@ -1174,6 +1175,32 @@ static PolicyBufs<T> policy_bufs(tsidb_ctx *h, const tsidb_policy_bufs *b, const
                        b->delay, (T *)b->terms, b->timeout, (T *)b->obs, b->obs_ld};
 }
 
+static PolicyDR policy_dr(const tsidb_ctx *h) {
+  const double *p = h->pol_dr;
+  PolicyDR d;
+  d.seed = (unsigned long long)p[TSIDB_POL_DR_SEED]; d.env_offset = (unsigned long long)p[TSIDB_POL_DR_ENV_OFFSET];
+  d.reset_joint_pos = p[TSIDB_POL_DR_RESET_JOINT_POS]; d.reset_joint_vel = p[TSIDB_POL_DR_RESET_JOINT_VEL];
+  for (int i = 0; i < 3; i++) { d.reset_lin[i] = p[TSIDB_POL_DR_RESET_BASE_LIN_VEL + i]; d.reset_ang[i] = p[TSIDB_POL_DR_RESET_BASE_ANG_VEL + i]; }
+  d.reset_yaw = p[TSIDB_POL_DR_RESET_YAW]; d.reset_xy = p[TSIDB_POL_DR_RESET_XY]; d.reset_lift = p[TSIDB_POL_DR_RESET_LIFT];
+  d.noise_ang_vel = p[TSIDB_POL_DR_NOISE_ANG_VEL]; d.noise_gravity = p[TSIDB_POL_DR_NOISE_GRAVITY];
+  d.noise_joint_pos = p[TSIDB_POL_DR_NOISE_JOINT_POS]; d.noise_joint_vel = p[TSIDB_POL_DR_NOISE_JOINT_VEL];
+  d.force_lo = p[TSIDB_POL_DR_PUSH_FORCE_LO]; d.force_hi = p[TSIDB_POL_DR_PUSH_FORCE_HI]; d.zero_prob = p[TSIDB_POL_DR_COMMAND_ZERO_PROB];
+  d.push_interval = (int)p[TSIDB_POL_DR_PUSH_INTERVAL]; d.push_duration = (int)p[TSIDB_POL_DR_PUSH_DURATION];
+  d.command_interval = (int)p[TSIDB_POL_DR_COMMAND_INTERVAL];
+  return d;
+}
+// which groups of the randomisation are on: a launch whose group is entirely off is not made
+static bool dr_any(const tsidb_ctx *h, int first, int last) {
+  for (int i = first; i <= last; i++) if (h->pol_dr[i] != 0) return true;
+  return false;
+}
+static bool dr_push_on(const tsidb_ctx *h) { return h->pol_dr[TSIDB_POL_DR_PUSH_INTERVAL] >= 1 && h->pol_dr[TSIDB_POL_DR_PUSH_DURATION] >= 1; }
+static bool dr_reset_on(const tsidb_ctx *h) { return dr_any(h, TSIDB_POL_DR_RESET_JOINT_POS, TSIDB_POL_DR_RESET_LIFT); }
+static bool dr_obs_on(const tsidb_ctx *h) {
+  return dr_any(h, TSIDB_POL_DR_NOISE_ANG_VEL, TSIDB_POL_DR_NOISE_JOINT_VEL) || dr_any(h, TSIDB_POL_DR_COMMAND_INTERVAL, TSIDB_POL_DR_COMMAND_ZERO_PROB) ||
+         h->pol_dr[TSIDB_POL_DR_ENV_OFFSET] != 0;
+}
+
 static dim3 policy_grid(const tsidb_ctx *h) { return dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK); }
 
 extern "C" {
@@ -1243,8 +1270,69 @@ int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *
     if (!done_rows || rows_ld < NROW) throw std::string("tsidb_policy_obs: needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)");
     if (!qpos || !qvel || !ncon || !con_pairs) throw std::string("tsidb_policy_obs: null buffer");
     h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_obs<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
-                       policy_cfg<T>(h), b, (const T *)done_rows, rows_ld, (const T *)qpos, (const T *)qvel, ncon, con_pairs, (T *)h->ctrl);
+    const auto kern = dr_obs_on(h) ? &k_policy_obs<T, true> : &k_policy_obs<T, false>;   // (off: the unrandomised kernel, bit for bit)
+    hipLaunchKernelGGL(kern, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s,
+                       (const DevModel<T> *)h->d_model, h->num_envs, policy_cfg<T>(h), b, (const T *)done_rows, rows_ld, (const T *)qpos,
+                       (const T *)qvel, ncon, con_pairs, (T *)h->ctrl, policy_dr(h));
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_randomize: ";
+  if (lacks_sim(h, true, who)) throw h->err;
+  double p[TSIDB_POL_DR_NPARAMS] = {};
+  if (dr_params || n_params) {
+    if (!dr_params || n_params != TSIDB_POL_DR_NPARAMS) throw std::string(who) + "needs TSIDB_POL_DR_NPARAMS parameters (or NULL, 0: everything off)";
+    for (int i = 0; i < n_params; i++) {
+      if (!std::isfinite(dr_params[i])) throw std::string(who) + "non-finite parameter";
+      if (dr_params[i] < 0) throw std::string(who) + "negative parameter (amplitudes, forces, intervals, seed, offset and probability are all >= 0)";
+      p[i] = dr_params[i];
+    }
+    for (int i : {(int)TSIDB_POL_DR_SEED, (int)TSIDB_POL_DR_ENV_OFFSET, (int)TSIDB_POL_DR_PUSH_INTERVAL, (int)TSIDB_POL_DR_PUSH_DURATION, (int)TSIDB_POL_DR_COMMAND_INTERVAL})
+      if (p[i] != std::floor(p[i])) throw std::string(who) + "seed, env_offset and the intervals must be whole numbers";
+    if (p[TSIDB_POL_DR_SEED] >= 4294967296.0) throw std::string(who) + "seed must be below 2^32";
+    if (p[TSIDB_POL_DR_ENV_OFFSET] >= 2147483648.0 || p[TSIDB_POL_DR_PUSH_INTERVAL] >= 2147483648.0 || p[TSIDB_POL_DR_COMMAND_INTERVAL] >= 2147483648.0)
+      throw std::string(who) + "env_offset and the intervals must be below 2^31";
+    if (p[TSIDB_POL_DR_PUSH_DURATION] > p[TSIDB_POL_DR_PUSH_INTERVAL]) throw std::string(who) + "push_duration > push_interval";
+    if (p[TSIDB_POL_DR_PUSH_FORCE_LO] > p[TSIDB_POL_DR_PUSH_FORCE_HI]) throw std::string(who) + "push_force_lo > push_force_hi";
+    if (p[TSIDB_POL_DR_COMMAND_ZERO_PROB] > 1) throw std::string(who) + "command_zero_prob must be in [0, 1]";
+  }
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->pol_dr, p, sizeof h->pol_dr);
+  GUARD_END
+}
+
+int tsidb_policy_perturb(tsidb_handle h, const tsidb_policy_bufs *bufs, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_perturb: ");
+    if (!dr_push_on(h)) return;
+    if (!h->xfrc) throw std::string("tsidb_policy_perturb: no xfrc buffer registered (call tsidb_set_xfrc first)");
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_perturb<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, policy_dr(h), (T *)h->xfrc);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, void *qpos, void *qvel,
+                             void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_reset_noise: ");
+    if (!done_rows || rows_ld < NROW) throw std::string("tsidb_policy_reset_noise: needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)");
+    if (!qpos || !qvel) throw std::string("tsidb_policy_reset_noise: null buffer");
+    if (!dr_reset_on(h)) return;
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_reset_noise<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, b,
+                       policy_dr(h), (const T *)done_rows, rows_ld, (T *)qpos, (T *)qvel);
   });
   HIP_OK(hipGetLastError());
   GUARD_END

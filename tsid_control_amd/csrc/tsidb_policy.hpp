@@ -1,8 +1,11 @@
 // tsidb_policy.hpp - the environment around a policy-driven sim loop (include/tsidb.h tsidb_policy_*): action -> ctrl
 // before the sim steps, reward / termination after them, bookkeeping of the restarted envs and the observation row after the
-// reset.  No reference counterpart: the reference runs one TSID-driven episode (main.py:113-124).
+// reset; with a randomisation configured (tsidb_policy_randomize) also the push of the step before the sim steps, noise on the
+// state of the envs just reset, command resampling and observation noise - every draw a hash of (seed, stream, column, env,
+// episode, ep_len), no random state anywhere.  No reference counterpart: the reference runs one TSID-driven episode
+// (main.py:113-124).
 //
-// Shape of all three kernels, as k_reset: one wavefront per env, lane = column of the env's rows (coalesced row loads and
+// Shape of all the kernels, as k_reset: one wavefront per env, lane = column of the env's rows (coalesced row loads and
 // stores), wave reductions (DPP) for the sums over actuators and wave votes for the flags over contacts; four envs per
 // workgroup, no LDS, no barrier.  Everything an env needs is a few hundred bytes: the kernels are launch- and latency-bound,
 // and a wavefront per env keeps every load of a row one transaction.
@@ -41,6 +44,32 @@ struct PolicyBufs {
   T *obs;
   int obs_ld;
 };
+
+// tsidb_policy_randomize's values, passed to the kernels by value.  float64 whatever the path's type: the draws are formed in
+// float64 and cast (include/tsidb.h)
+struct PolicyDR {
+  unsigned long long seed, env_offset;
+  double reset_joint_pos, reset_joint_vel, reset_lin[3], reset_ang[3], reset_yaw, reset_xy, reset_lift;
+  double noise_ang_vel, noise_gravity, noise_joint_pos, noise_joint_vel;
+  double force_lo, force_hi, zero_prob;
+  int push_interval, push_duration, command_interval;
+};
+enum { DR_S_JOINT_POS = 1, DR_S_JOINT_VEL, DR_S_LIN_VEL, DR_S_ANG_VEL, DR_S_YAW, DR_S_XY, DR_S_OBS, DR_S_PUSH_PHASE, DR_S_PUSH_MAG, DR_S_PUSH_DIR,
+       DR_S_CMD_ZERO };
+
+// U in [0, 1): the top 53 bits of the hash over 2^53
+__device__ __forceinline__ double pol_uniform(unsigned long long key, unsigned long long env, unsigned long long counter) {
+  return (double)(plan_hash(key, env, counter) >> 11) * (1.0 / 9007199254740992.0);
+}
+// the draw of (stream, column): key = seed + ((stream * 256 + column) << 32)
+__device__ __forceinline__ double pol_draw(const PolicyDR &d, int stream, int column, unsigned long long env, unsigned long long counter) {
+  return pol_uniform(d.seed + ((unsigned long long)(stream * 256 + column) << 32), env, counter);
+}
+// amp (2 U - 1) in float64, cast
+template <typename T>
+__device__ __forceinline__ T pol_noise(const PolicyDR &d, double amp, int stream, int column, unsigned long long env, unsigned long long counter) {
+  return (T)(amp * (2.0 * pol_draw(d, stream, column, env, counter) - 1.0));
+}
 
 // the env of this wavefront (-1: none); wave-uniform, and said so to the compiler: row bases become scalar registers
 __device__ __forceinline__ int pol_env(int n) {
@@ -157,16 +186,20 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_reward(con
 }
 
 // ---------------------------------------------------------------------------- restarted envs + observation (after the reset)
-template <typename T>
+// DR = false: no randomisation configured, d is not read.  DR = true (chosen on the host, tsidb_policy_obs): env_offset in the
+// command draw, command resampling and zeroing, noise on the observation columns.
+template <typename T, bool DR>
 __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_obs(const DevModel<T> *__restrict__ mp, int n, PolicyCfg<T> c, PolicyBufs<T> b,
                                                                           const T *__restrict__ done_rows, int rows_ld, const T *__restrict__ qpos,
                                                                           const T *__restrict__ qvel, const int *__restrict__ ncon,
-                                                                          const int *__restrict__ con_pairs, T *ctrl) {
+                                                                          const int *__restrict__ con_pairs, T *ctrl, PolicyDR d) {
   const DevModel<T> &m = *mp;
   const int e = pol_env(n), lane = threadIdx.x & 63;
   if (e < 0) return;
   const size_t E = (size_t)e;
   const bool fresh = done_rows[E * rows_ld + NROW - 1] != T(0);   // (the done column, NOBS + 1)
+  int ep_now = 0, len_now = 0;   // DR: episode and ep_len as this kernel leaves them
+  if constexpr (DR) { ep_now = b.episode[E] + (fresh ? 1 : 0); len_now = fresh ? 0 : b.ep_len[E]; }
   int con = pol_contacts(m, c, ncon, con_pairs, E, lane);
   T last = lane < NA ? b.last[E * NA + lane] : T(0);
   T cmd = lane < 3 ? b.command[E * 3 + lane] : T(0);
@@ -184,10 +217,25 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_obs(const 
     if (lane < 2) b.air[E * 2 + lane] = 0;
     const int ep = b.episode[E] + 1;
     if (lane == 0) { b.ep_len[E] = 0; b.episode[E] = ep; }
-    if (lane < 3 && c.cmd_lo[lane] != c.cmd_hi[lane]) {
-      const double u = (double)(plan_hash(c.seed + (unsigned long long)lane, (unsigned long long)e, (unsigned long long)ep) >> 11) * (1.0 / 9007199254740992.0);
-      cmd = (T)(c.cmd_lo[lane] + (c.cmd_hi[lane] - c.cmd_lo[lane]) * u);
-      b.command[E * 3 + lane] = cmd;
+    if constexpr (!DR) {
+      if (lane < 3 && c.cmd_lo[lane] != c.cmd_hi[lane]) {
+        const double u = (double)(plan_hash(c.seed + (unsigned long long)lane, (unsigned long long)e, (unsigned long long)ep) >> 11) * (1.0 / 9007199254740992.0);
+        cmd = (T)(c.cmd_lo[lane] + (c.cmd_hi[lane] - c.cmd_lo[lane]) * u);
+        b.command[E * 3 + lane] = cmd;
+      }
+    }
+  }
+  const unsigned long long ge = DR ? d.env_offset + (unsigned long long)e : 0ull;
+  if constexpr (DR) {
+    // a restart is resample 0 of its episode; resample k when ep_len reaches k * command_interval
+    const bool resample = !fresh && d.command_interval > 0 && len_now > 0 && len_now % d.command_interval == 0;
+    if (fresh || resample) {
+      const unsigned long long ctr = (unsigned long long)ep_now + ((unsigned long long)(resample ? len_now / d.command_interval : 0) << 32);
+      const bool zero = d.zero_prob > 0 && pol_draw(d, DR_S_CMD_ZERO, 0, ge, ctr) < d.zero_prob;
+      if (lane < 3 && (zero || c.cmd_lo[lane] != c.cmd_hi[lane])) {
+        cmd = zero ? T(0) : (T)(c.cmd_lo[lane] + (c.cmd_hi[lane] - c.cmd_lo[lane]) * pol_uniform(c.seed + (unsigned long long)lane, ge, ctr));
+        b.command[E * 3 + lane] = cmd;
+      }
     }
   }
   if (!b.obs) return;
@@ -198,19 +246,92 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_obs(const 
   if (lane < 3) {
     const T g = lane == 0 ? R[6] : lane == 1 ? R[7] : R[8], r0 = lane == 0 ? R[0] : lane == 1 ? R[1] : R[2],
             r1 = lane == 0 ? R[3] : lane == 1 ? R[4] : R[5];
-    o[lane] = qv[3 + lane];                    // base angular velocity: body frame as stored
-    o[3 + lane] = -g;                          // R^T (0, 0, -1)
+    if constexpr (DR) {   // noise on the observation columns only; an amplitude of 0 adds nothing
+      const unsigned long long ctr = ((unsigned long long)ep_now << 32) | (unsigned long long)len_now;
+      T w = qv[3 + lane], pg = -g;
+      if (d.noise_ang_vel != 0) w += pol_noise<T>(d, d.noise_ang_vel, DR_S_OBS, lane, ge, ctr);
+      if (d.noise_gravity != 0) pg += pol_noise<T>(d, d.noise_gravity, DR_S_OBS, 3 + lane, ge, ctr);
+      o[lane] = w;
+      o[3 + lane] = pg;
+    } else {
+      o[lane] = qv[3 + lane];                    // base angular velocity: body frame as stored
+      o[3 + lane] = -g;                          // R^T (0, 0, -1)
+    }
     o[6 + lane] = cmd;
     o[POL_NOBS + lane] = r0 * qv[0] + r1 * qv[1] + g * qv[2];   // privileged: R^T v
   }
   if (lane < NA) {
     const int dof = m.mj_act_dof[lane];
-    o[9 + lane] = qp[dof + 1] - c.def[lane];
-    o[9 + NA + lane] = qv[dof];
+    if constexpr (DR) {
+      const unsigned long long ctr = ((unsigned long long)ep_now << 32) | (unsigned long long)len_now;
+      T jp = qp[dof + 1] - c.def[lane], jv = qv[dof];
+      if (d.noise_joint_pos != 0) jp += pol_noise<T>(d, d.noise_joint_pos, DR_S_OBS, 9 + lane, ge, ctr);
+      if (d.noise_joint_vel != 0) jv += pol_noise<T>(d, d.noise_joint_vel, DR_S_OBS, 9 + NA + lane, ge, ctr);
+      o[9 + lane] = jp;
+      o[9 + NA + lane] = jv;
+    } else {
+      o[9 + lane] = qp[dof + 1] - c.def[lane];
+      o[9 + NA + lane] = qv[dof];
+    }
     o[9 + 2 * NA + lane] = last;
   }
   if (lane < 2) o[9 + 3 * NA + lane] = (con >> lane) & 1 ? T(1) : T(0);
   if (lane == 3) o[POL_NOBS + 3] = qp[2];
+}
+
+// ---------------------------------------------------------------------------- push of this policy step (before the sim steps)
+// lanes 0 .. 2 write the torso force xfrc[e, 0, 0:3]; every other element of xfrc stays the caller's
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_perturb(int n, PolicyBufs<T> b, PolicyDR d, T *xfrc) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= 3) return;
+  const size_t E = (size_t)e;
+  const unsigned long long ge = d.env_offset + (unsigned long long)e, ep = (unsigned long long)b.episode[E];
+  const int len = b.ep_len[E];   // (policy steps completed in the episode)
+  const int phase = (int)(pol_draw(d, DR_S_PUSH_PHASE, 0, ge, ep) * (double)d.push_interval);   // floor: the product is >= 0
+  double f = 0;
+  if (len >= phase && (len - phase) % d.push_interval < d.push_duration) {
+    const unsigned long long ctr = (ep << 32) | (unsigned long long)((len - phase) / d.push_interval);
+    const double mag = d.force_lo + (d.force_hi - d.force_lo) * pol_draw(d, DR_S_PUSH_MAG, 0, ge, ctr);
+    const double az = 6.283185307179586 * pol_draw(d, DR_S_PUSH_DIR, 0, ge, ctr);
+    f = lane == 0 ? mag * cos(az) : lane == 1 ? mag * sin(az) : 0.0;
+  }
+  xfrc[E * NB * 6 + lane] = (T)f;
+}
+
+// ---------------------------------------------------------------------------- reset noise (after the reset, before k_policy_obs)
+// the sim state of the envs just reset; the TSID state q, v stays as the reset wrote it (the policy environment runs no tick)
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_reset_noise(const DevModel<T> *__restrict__ mp, int n, PolicyBufs<T> b, PolicyDR d,
+                                                                                  const T *__restrict__ done_rows, int rows_ld, T *qpos, T *qvel) {
+  const DevModel<T> &m = *mp;
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  if (done_rows[E * rows_ld + NROW - 1] == T(0)) return;
+  T *qp = qpos + E * NQ, *qv = qvel + E * NV;
+  const unsigned long long ge = d.env_offset + (unsigned long long)e, ep = (unsigned long long)(b.episode[E] + 1);   // (the episode about to start)
+  // the yawed quaternion, every lane the same values (read before any lane writes)
+  T w = qp[3], x = qp[4], y = qp[5], z = qp[6];
+  if (d.reset_yaw != 0) {
+    const double th = d.reset_yaw * (2.0 * pol_draw(d, DR_S_YAW, 0, ge, ep) - 1.0);
+    const T ch = (T)cos(0.5 * th), sh = (T)sin(0.5 * th);
+    const T w1 = ch * w - sh * z, x1 = ch * x - sh * y, y1 = ch * y + sh * x, z1 = ch * z + sh * w;
+    const T nrm = sqrt(w1 * w1 + x1 * x1 + y1 * y1 + z1 * z1);
+    w = w1 / nrm; x = x1 / nrm; y = y1 / nrm; z = z1 / nrm;
+  }
+  if (lane < NA) {
+    const int dof = m.mj_act_dof[lane];
+    if (d.reset_joint_pos != 0) qp[dof + 1] += pol_noise<T>(d, d.reset_joint_pos, DR_S_JOINT_POS, lane, ge, ep);
+    if (d.reset_joint_vel != 0) qv[dof] += pol_noise<T>(d, d.reset_joint_vel, DR_S_JOINT_VEL, lane, ge, ep);
+  }
+  if (lane < 3) {
+    if (d.reset_lin[lane] != 0) qv[lane] += pol_noise<T>(d, d.reset_lin[lane], DR_S_LIN_VEL, lane, ge, ep);
+    if (d.reset_ang[lane] != 0) qv[3 + lane] += pol_noise<T>(d, d.reset_ang[lane], DR_S_ANG_VEL, lane, ge, ep);
+    if (lane < 2) { if (d.reset_xy != 0) qp[lane] += pol_noise<T>(d, d.reset_xy, DR_S_XY, lane, ge, ep); }
+    else if (d.reset_lift != 0) qp[2] += (T)d.reset_lift;
+  }
+  if (d.reset_yaw != 0 && lane >= 3 && lane < 7) qp[lane] = lane == 3 ? w : lane == 4 ? x : lane == 5 ? y : z;
 }
 
 } // namespace tsidb
