@@ -304,6 +304,105 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return __builtin_amdgcn_readlane(v, 63);
 }
 
+// ---- float64 broadcasts inside the FMA (DESIGN.md section 5 "Register factorisations")
+// A float64 v_readlane broadcast is two scalar-unit reads plus the v_readlane -> VALU wait state for every FMA it feeds.
+// Where one loop broadcasts ONE register x at several compile-time lanes j to consumers on lanes 0..31 (DPP rows 0, 1),
+//   row_dup(x)              one v_permlane16_swap per dword: lo holds x's lanes 0..15 in rows 0 AND 1, hi its lanes 16..31
+//                           (rows 2, 3 get x's rows 2 resp. 3: lanes >= 32 compute with those - nothing may read them);
+//   bcast_fnma<MASK>(a,d,m) a[j] = fma(-x[j], m, a[j]) for every j in MASK as v_fmac_f64_dpp a[j], -lo|hi, m
+//                           row_newbcast:(j & 15) - the operation `a[j] -= m * rdlane(x, j)` contracts to, bit for bit.
+// Inline asm gets no hazard handling: a DPP read of a VGPR the previous VALU instruction wrote needs two wait states.
+// The FMAs therefore come in asm groups of up to eight with an s_nop 1 at the group's head (the choice over "make the
+// operand old enough": it also covers a copy of lo / hi the register allocator may place right in front of the group);
+// inside a group only the a[j] are written, never a DPP source.
+// (the lanes are template arguments: loops over them are unroll_for, whose index is a compile-time constant)
+template <int K> struct IntC { static constexpr int value = K; };
+template <int K0, int K1, typename F> __device__ __forceinline__ void unroll_for(F &&f) {
+  if constexpr (K0 < K1) { f(IntC<K0>{}); unroll_for<K0 + 1, K1>(f); }
+}
+struct RowDup { double lo, hi; };
+typedef unsigned tsidb_v2u_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ RowDup row_dup(double x) {
+  const unsigned long long v = __builtin_bit_cast(unsigned long long, x);
+  // permlane16_swap(p, q): rows 1 / 3 of p <-> rows 0 / 2 of q
+  const tsidb_v2u_t l = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  const tsidb_v2u_t h = __builtin_amdgcn_permlane16_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+  RowDup d;
+  d.lo = __builtin_bit_cast(double, ((unsigned long long)h[0] << 32) | l[0]);
+  d.hi = __builtin_bit_cast(double, ((unsigned long long)h[1] << 32) | l[1]);
+  return d;
+}
+constexpr int mask_bit_at(unsigned mask, int n) { // index of the n-th set bit (n < popcount)
+  int r = -1;
+  for (int b = 0; b < 32; b++)
+    if ((mask >> b) & 1u) { if (n == 0 && r < 0) r = b; n--; }
+  return r;
+}
+constexpr int mask_count(unsigned mask) { int c = 0; for (; mask; mask &= mask - 1) c++; return c; }
+constexpr unsigned mask_drop_low(unsigned mask, int n) { for (; n > 0 && mask; n--) mask &= mask - 1; return mask; }
+#define TSIDB_BF(i) "v_fmac_f64_dpp %[a" #i "], -%[x" #i "], %[m] row_newbcast:%[j" #i "] row_mask:0xf bank_mask:0xf\n"
+#define TSIDB_BO(i) [a##i] "+v"(a[mask_bit_at(MASK, i)])
+#define TSIDB_BI(i) [x##i] "v"(mask_bit_at(MASK, i) < 16 ? d.lo : d.hi), [j##i] "n"(mask_bit_at(MASK, i) & 15)
+template <unsigned MASK, int N> __device__ __forceinline__ void bcast_fnma(double (&a)[N], const RowDup &d, double m) {
+  constexpr int C = mask_count(MASK);
+  static_assert(N >= 32 || (MASK >> (N & 31)) == 0u, "lanes of the accumulator array");
+  if constexpr (C == 1) asm volatile("s_nop 1\n" TSIDB_BF(0) : TSIDB_BO(0) : [m] "v"(m), TSIDB_BI(0));
+  else if constexpr (C == 2) asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) : TSIDB_BO(0), TSIDB_BO(1) : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1));
+  else if constexpr (C == 3)
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2) : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2));
+  else if constexpr (C == 4)
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) TSIDB_BF(3)
+                 : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2), TSIDB_BO(3)
+                 : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2), TSIDB_BI(3));
+  else if constexpr (C == 5)
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) TSIDB_BF(3) TSIDB_BF(4)
+                 : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2), TSIDB_BO(3), TSIDB_BO(4)
+                 : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2), TSIDB_BI(3), TSIDB_BI(4));
+  else if constexpr (C == 6)
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) TSIDB_BF(3) TSIDB_BF(4) TSIDB_BF(5)
+                 : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2), TSIDB_BO(3), TSIDB_BO(4), TSIDB_BO(5)
+                 : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2), TSIDB_BI(3), TSIDB_BI(4), TSIDB_BI(5));
+  else if constexpr (C == 7)
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) TSIDB_BF(3) TSIDB_BF(4) TSIDB_BF(5) TSIDB_BF(6)
+                 : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2), TSIDB_BO(3), TSIDB_BO(4), TSIDB_BO(5), TSIDB_BO(6)
+                 : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2), TSIDB_BI(3), TSIDB_BI(4), TSIDB_BI(5), TSIDB_BI(6));
+  else if constexpr (C >= 8) {
+    asm volatile("s_nop 1\n" TSIDB_BF(0) TSIDB_BF(1) TSIDB_BF(2) TSIDB_BF(3) TSIDB_BF(4) TSIDB_BF(5) TSIDB_BF(6) TSIDB_BF(7)
+                 : TSIDB_BO(0), TSIDB_BO(1), TSIDB_BO(2), TSIDB_BO(3), TSIDB_BO(4), TSIDB_BO(5), TSIDB_BO(6), TSIDB_BO(7)
+                 : [m] "v"(m), TSIDB_BI(0), TSIDB_BI(1), TSIDB_BI(2), TSIDB_BI(3), TSIDB_BI(4), TSIDB_BI(5), TSIDB_BI(6), TSIDB_BI(7));
+    bcast_fnma<mask_drop_low(MASK, 8)>(a, d, m);
+  }
+}
+#undef TSIDB_BF
+#undef TSIDB_BO
+#undef TSIDB_BI
+//   bcast_fnma2<MASK>(s0, s1, d, m)  s_(j & 1) = fma(-x[j], m[j], s_(j & 1)) for every j in MASK, ascending: the two chains
+//                           of `s0 -= m[j] * rdlane(x, j); s1 -= m[j + 1] * rdlane(x, j + 1)`, interleaved.
+// One asm text serves every count: the assembler's .if drops the slots a group does not fill (their operands repeat
+// slot 0's registers).  Groups of four per chain: each FMA brings its own multiplier, and an asm statement takes 30 operands.
+#define TSIDB_BF(c, i, sg) ".if %[n" c "] > " #i "\nv_fmac_f64_dpp %[" c "], " sg "%[x" c #i "], %[m" c #i "] row_newbcast:%[j" c #i "] row_mask:0xf bank_mask:0xf\n.endif\n"
+#define TSIDB_BI(c, M, i) [x##c##i] "v"(mask_bit_at(M, i) >= 16 ? d.hi : d.lo), [m##c##i] "v"(m[mask_bit_at(M, i) < 0 ? 0 : mask_bit_at(M, i)]), \
+                          [j##c##i] "n"(mask_bit_at(M, i) < 0 ? 0 : (mask_bit_at(M, i) & 15))
+#define TSIDB_BG(sg)                                                                                                              \
+  asm volatile("s_nop 1\n" TSIDB_BF("e", 0, sg) TSIDB_BF("o", 0, sg) TSIDB_BF("e", 1, sg) TSIDB_BF("o", 1, sg)                    \
+               TSIDB_BF("e", 2, sg) TSIDB_BF("o", 2, sg) TSIDB_BF("e", 3, sg) TSIDB_BF("o", 3, sg)                                \
+               : [e] "+v"(s0), [o] "+v"(s1)                                                                                       \
+               : [ne] "n"(CE), [no] "n"(CO), TSIDB_BI(e, E, 0), TSIDB_BI(o, O, 0), TSIDB_BI(e, E, 1), TSIDB_BI(o, O, 1),          \
+                 TSIDB_BI(e, E, 2), TSIDB_BI(o, O, 2), TSIDB_BI(e, E, 3), TSIDB_BI(o, O, 3))
+template <unsigned MASK, int N>
+__device__ __forceinline__ void bcast_fnma2(double &s0, double &s1, const RowDup &d, const double (&m)[N]) {
+  static_assert(N >= 32 || (MASK >> (N & 31)) == 0u, "lanes of the multiplier array");
+  constexpr unsigned E = MASK & 0x55555555u, O = MASK & 0xaaaaaaaau;
+  constexpr int CE = mask_count(E) < 4 ? mask_count(E) : 4, CO = mask_count(O) < 4 ? mask_count(O) : 4;
+  if constexpr (MASK != 0u) {
+    TSIDB_BG("-");
+    bcast_fnma2<mask_drop_low(E, 4) | mask_drop_low(O, 4)>(s0, s1, d, m);
+  }
+}
+#undef TSIDB_BF
+#undef TSIDB_BI
+#undef TSIDB_BG
+
 template <int CTRL, int ROW_MASK, typename T> __device__ __forceinline__ T dpp_min_step(T v) {
   // lanes a disabled row would leave at 0 must not win the min: feed the lane's own value instead
   T w;

@@ -97,42 +97,61 @@ __device__ __forceinline__ int sym_idx(int i, int j) { // packed upper index of 
 // once, ancestors' entries read back at uniform addresses: one LDS instruction instead of the two v_readlane a
 // float64 broadcast costs): 0.260 ms - the values then sit in VGPRs the kernel does not have (86 spilled) and the
 // per-pivot LDS round trip is exposed.
+// What did pay (DESIGN.md section 5 "Register factorisations"): the broadcast inside the FMA.  The float64 tree-sparse
+// form prepares two row-replicated copies of the pivot's column (row_dup: one v_permlane16_swap per dword) and feeds
+// them to v_fmac_f64_dpp row_newbcast - no SGPRs, no v_readlane -> VALU wait, the same operations bit for bit.  The dense
+// variant and float32 keep the v_readlane groups.
 template <typename T, bool DENSE>
 __device__ __forceinline__ T chol26_solve(T (&a)[NV], T rhs, int lane, bool &spd) {
   int ln = lane; // (re-read here: the lane < k / lane == k masks are not kept from one inlined copy of this routine to the next)
   asm volatile("" : "+v"(ln));
   int notspd = 0; // (a VGPR flag pinned per pivot: the 26 compare masks kept to be and-ed at the end are 52 SGPRs)
   T rd[NV]; // 1 / U[k][k], wave-uniform
-#pragma unroll
-  for (int t = 0; t < NV; t++) {
-    const int k = NV - 1 - t;
+  auto pivot = [&](int k) __attribute__((always_inline)) -> T {
     const T akk = rdlane(a[k], k);
     notspd = akk > 0 ? notspd : 1;
     asm volatile("" : "+v"(notspd));
     const T rk = rsqrt_t(akk > 0 ? akk : T(1));
     rd[k] = rk;
-    T uik = ln < k ? a[k] * rk : (ln == k ? akk * rk : T(0));
+    const T uik = ln < k ? a[k] * rk : (ln == k ? akk * rk : T(0));
     a[k] = uik;
-    // Broadcasts four at a time: READ four (eight v_readlane), then the four FMAs.  Left alone the compiler either
-    // issues the whole row's broadcasts as one burst (2 SGPRs each, parked in VGPR lanes with v_writelane / v_readlane
-    // until their turn) or one at a time, v_readlane x2 - s_nop 1 - v_fma, where every FMA waits out the
-    // v_readlane -> VALU hazard.  The empty asm takes the four values as SGPR inputs (so they exist before it) and
-    // "changes" uik (so the FMAs and the next reads come after it) and the previous group's last result (so that group's
-    // FMAs come before it).
-    int jl = -1; // (compile-time after unrolling)
+    return uik;
+  };
+  if constexpr (!DENSE && sizeof(T) == 8) {
+    // float64, tree-sparse: column k's entries reach their FMAs as DPP row broadcasts (tsidb_common.hpp: row_dup /
+    // bcast_fnma) - no SGPRs, no v_readlane -> VALU wait.  uik is zero on lanes > k, so lanes >= 32 stay exact zeros.
+    unroll_for<0, NV>([&](auto tt) {
+      constexpr int k = NV - 1 - decltype(tt)::value;
+      const T uik = pivot(k);
+      constexpr unsigned ANC = MJ_DOFANC[k] & ((1u << k) - 1u);
+      if constexpr (ANC != 0u) bcast_fnma<ANC>(a, row_dup(uik), uik); // a[j] -= uik * U[j][k], j an ancestor of k
+    });
+  } else {
 #pragma unroll
-    for (int j0 = 0; j0 < k; j0 += 4) {
-      const bool p0 = DENSE || ((MJ_DOFANC[k] >> j0) & 1u), p1 = j0 + 1 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 1)) & 1u)),
-                 p2 = j0 + 2 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 2)) & 1u)), p3 = j0 + 3 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 3)) & 1u));
-      if (!(p0 || p1 || p2 || p3)) continue;
-      const T u0 = p0 ? rdlane(uik, j0) : T(0), u1 = p1 ? rdlane(uik, j0 + 1) : T(0), u2 = p2 ? rdlane(uik, j0 + 2) : T(0),
-              u3 = p3 ? rdlane(uik, j0 + 3) : T(0);
-      if (jl >= 0) asm volatile("" : "+v"(uik), "+v"(a[jl]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      else asm volatile("" : "+v"(uik) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      if (p0) { a[j0] -= uik * u0; jl = j0; }
-      if (p1) { a[j0 + 1] -= uik * u1; jl = j0 + 1; }
-      if (p2) { a[j0 + 2] -= uik * u2; jl = j0 + 2; }
-      if (p3) { a[j0 + 3] -= uik * u3; jl = j0 + 3; }
+    for (int t = 0; t < NV; t++) {
+      const int k = NV - 1 - t;
+      T uik = pivot(k);
+      // Broadcasts four at a time: READ four (eight v_readlane), then the four FMAs.  Left alone the compiler either
+      // issues the whole row's broadcasts as one burst (2 SGPRs each, parked in VGPR lanes with v_writelane / v_readlane
+      // until their turn) or one at a time, v_readlane x2 - s_nop 1 - v_fma, where every FMA waits out the
+      // v_readlane -> VALU hazard.  The empty asm takes the four values as SGPR inputs (so they exist before it) and
+      // "changes" uik (so the FMAs and the next reads come after it) and the previous group's last result (so that group's
+      // FMAs come before it).
+      int jl = -1; // (compile-time after unrolling)
+#pragma unroll
+      for (int j0 = 0; j0 < k; j0 += 4) {
+        const bool p0 = DENSE || ((MJ_DOFANC[k] >> j0) & 1u), p1 = j0 + 1 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 1)) & 1u)),
+                   p2 = j0 + 2 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 2)) & 1u)), p3 = j0 + 3 < k && (DENSE || ((MJ_DOFANC[k] >> (j0 + 3)) & 1u));
+        if (!(p0 || p1 || p2 || p3)) continue;
+        const T u0 = p0 ? rdlane(uik, j0) : T(0), u1 = p1 ? rdlane(uik, j0 + 1) : T(0), u2 = p2 ? rdlane(uik, j0 + 2) : T(0),
+                u3 = p3 ? rdlane(uik, j0 + 3) : T(0);
+        if (jl >= 0) asm volatile("" : "+v"(uik), "+v"(a[jl]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        else asm volatile("" : "+v"(uik) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        if (p0) { a[j0] -= uik * u0; jl = j0; }
+        if (p1) { a[j0 + 1] -= uik * u1; jl = j0 + 1; }
+        if (p2) { a[j0 + 2] -= uik * u2; jl = j0 + 2; }
+        if (p3) { a[j0 + 3] -= uik * u3; jl = j0 + 3; }
+      }
     }
   }
   spd = notspd == 0;
@@ -149,25 +168,37 @@ __device__ __forceinline__ T chol26_solve(T (&a)[NV], T rhs, int lane, bool &spd
     acc -= a[k] * y[k];
   }
   T xs[NV], x = 0;
+  if constexpr (!DENSE && sizeof(T) == 8) {
+    // (row k's ancestor entries as DPP row broadcasts of a[k]; s0 / s1 are then right on lanes < 32, which is where x is read)
+    unroll_for<0, NV>([&](auto kk) {
+      constexpr int k = decltype(kk)::value;
+      T s0 = y[k], s1 = 0;
+      constexpr unsigned ANC = MJ_DOFANC[k] & ((1u << k) - 1u);
+      if constexpr (ANC != 0u) bcast_fnma2<ANC>(s0, s1, row_dup(a[k]), xs); // s_(i & 1) -= U[i][k] * xs[i]
+      xs[k] = (s0 + s1) * rd[k];
+      if (ln == k) x = xs[k];
+    });
+  } else {
 #pragma unroll
-  for (int t = NV - 1; t >= 0; t--) {
-    const int k = NV - 1 - t;
-    T s0 = y[k], s1 = 0, ak = a[k]; // two chains: a dependent f64 FMA waits for its predecessor
+    for (int t = NV - 1; t >= 0; t--) {
+      const int k = NV - 1 - t;
+      T s0 = y[k], s1 = 0, ak = a[k]; // two chains: a dependent f64 FMA waits for its predecessor
 #pragma unroll
-    for (int i0 = 0; i0 < k; i0 += 4) { // (broadcasts four at a time, as above)
-      const bool p0 = DENSE || ((MJ_DOFANC[k] >> i0) & 1u), p1 = i0 + 1 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 1)) & 1u)),
-                 p2 = i0 + 2 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 2)) & 1u)), p3 = i0 + 3 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 3)) & 1u));
-      if (!(p0 || p1 || p2 || p3)) continue;
-      const T u0 = p0 ? rdlane(ak, i0) : T(0), u1 = p1 ? rdlane(ak, i0 + 1) : T(0), u2 = p2 ? rdlane(ak, i0 + 2) : T(0),
-              u3 = p3 ? rdlane(ak, i0 + 3) : T(0);
-      asm volatile("" : "+v"(ak), "+v"(s0), "+v"(s1) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      if (p0) s0 -= u0 * xs[i0];
-      if (p1) s1 -= u1 * xs[i0 + 1];
-      if (p2) s0 -= u2 * xs[i0 + 2];
-      if (p3) s1 -= u3 * xs[i0 + 3];
+      for (int i0 = 0; i0 < k; i0 += 4) { // (broadcasts four at a time, as above)
+        const bool p0 = DENSE || ((MJ_DOFANC[k] >> i0) & 1u), p1 = i0 + 1 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 1)) & 1u)),
+                   p2 = i0 + 2 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 2)) & 1u)), p3 = i0 + 3 < k && (DENSE || ((MJ_DOFANC[k] >> (i0 + 3)) & 1u));
+        if (!(p0 || p1 || p2 || p3)) continue;
+        const T u0 = p0 ? rdlane(ak, i0) : T(0), u1 = p1 ? rdlane(ak, i0 + 1) : T(0), u2 = p2 ? rdlane(ak, i0 + 2) : T(0),
+                u3 = p3 ? rdlane(ak, i0 + 3) : T(0);
+        asm volatile("" : "+v"(ak), "+v"(s0), "+v"(s1) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        if (p0) s0 -= u0 * xs[i0];
+        if (p1) s1 -= u1 * xs[i0 + 1];
+        if (p2) s0 -= u2 * xs[i0 + 2];
+        if (p3) s1 -= u3 * xs[i0 + 3];
+      }
+      xs[k] = (s0 + s1) * rd[k];
+      if (ln == k) x = xs[k];
     }
-    xs[k] = (s0 + s1) * rd[k];
-    if (ln == k) x = xs[k];
   }
   return x;
 }
@@ -191,30 +222,43 @@ __device__ __forceinline__ void chol26_factor(T (&a)[NV], T &rdv, int lane, bool
   asm volatile("" : "+v"(ln));
   int notspd = 0;
   rdv = 0;
-#pragma unroll
-  for (int t = 0; t < NV; t++) {
-    const int k = NV - 1 - t;
+  auto pivot = [&](int k) __attribute__((always_inline)) -> T {
     const T akk = rdlane(a[k], k);
     notspd = akk > 0 ? notspd : 1;
     asm volatile("" : "+v"(notspd));
     const T rk = rsqrt_t(akk > 0 ? akk : T(1));
     rdv = ln == k ? rk : rdv;
-    T uik = ln < k ? a[k] * rk : (ln == k ? akk * rk : T(0));
+    const T uik = ln < k ? a[k] * rk : (ln == k ? akk * rk : T(0));
     a[k] = uik;
-    int jl = -1; // (broadcasts four at a time, read ahead of their FMAs: see chol26_solve)
+    return uik;
+  };
+  if constexpr (sizeof(T) == 8) { // (DPP row broadcasts: see chol26_solve)
+    unroll_for<0, NV>([&](auto tt) {
+      constexpr int k = NV - 1 - decltype(tt)::value;
+      const T uik = pivot(k);
+      constexpr unsigned ANC = MJ_DOFANC[k] & ((1u << k) - 1u);
+      if constexpr (ANC != 0u) bcast_fnma<ANC>(a, row_dup(uik), uik);
+    });
+  } else {
 #pragma unroll
-    for (int j0 = 0; j0 < k; j0 += 4) {
-      const bool p0 = (MJ_DOFANC[k] >> j0) & 1u, p1 = j0 + 1 < k && ((MJ_DOFANC[k] >> (j0 + 1)) & 1u),
-                 p2 = j0 + 2 < k && ((MJ_DOFANC[k] >> (j0 + 2)) & 1u), p3 = j0 + 3 < k && ((MJ_DOFANC[k] >> (j0 + 3)) & 1u);
-      if (!(p0 || p1 || p2 || p3)) continue;
-      const T u0 = p0 ? rdlane(uik, j0) : T(0), u1 = p1 ? rdlane(uik, j0 + 1) : T(0), u2 = p2 ? rdlane(uik, j0 + 2) : T(0),
-              u3 = p3 ? rdlane(uik, j0 + 3) : T(0);
-      if (jl >= 0) asm volatile("" : "+v"(uik), "+v"(a[jl]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      else asm volatile("" : "+v"(uik) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      if (p0) { a[j0] -= uik * u0; jl = j0; }
-      if (p1) { a[j0 + 1] -= uik * u1; jl = j0 + 1; }
-      if (p2) { a[j0 + 2] -= uik * u2; jl = j0 + 2; }
-      if (p3) { a[j0 + 3] -= uik * u3; jl = j0 + 3; }
+    for (int t = 0; t < NV; t++) {
+      const int k = NV - 1 - t;
+      T uik = pivot(k);
+      int jl = -1; // (broadcasts four at a time, read ahead of their FMAs: see chol26_solve)
+#pragma unroll
+      for (int j0 = 0; j0 < k; j0 += 4) {
+        const bool p0 = (MJ_DOFANC[k] >> j0) & 1u, p1 = j0 + 1 < k && ((MJ_DOFANC[k] >> (j0 + 1)) & 1u),
+                   p2 = j0 + 2 < k && ((MJ_DOFANC[k] >> (j0 + 2)) & 1u), p3 = j0 + 3 < k && ((MJ_DOFANC[k] >> (j0 + 3)) & 1u);
+        if (!(p0 || p1 || p2 || p3)) continue;
+        const T u0 = p0 ? rdlane(uik, j0) : T(0), u1 = p1 ? rdlane(uik, j0 + 1) : T(0), u2 = p2 ? rdlane(uik, j0 + 2) : T(0),
+                u3 = p3 ? rdlane(uik, j0 + 3) : T(0);
+        if (jl >= 0) asm volatile("" : "+v"(uik), "+v"(a[jl]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        else asm volatile("" : "+v"(uik) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        if (p0) { a[j0] -= uik * u0; jl = j0; }
+        if (p1) { a[j0 + 1] -= uik * u1; jl = j0 + 1; }
+        if (p2) { a[j0 + 2] -= uik * u2; jl = j0 + 2; }
+        if (p3) { a[j0 + 3] -= uik * u3; jl = j0 + 3; }
+      }
     }
   }
   spd = notspd == 0;

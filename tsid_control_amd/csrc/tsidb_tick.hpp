@@ -83,6 +83,55 @@ __device__ __forceinline__ double rdlane(double v, int src) {
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
 }
 
+// The tick's 26 x 26 Cholesky in registers (right-looking; lane i holds row i of the matrix in a[], and of L in a[0..i]
+// afterwards); lane k of rdv = 1 / L[k][k]; notspd is set when a pivot is not positive.
+// DPPB (float64 only): column k's entries reach their FMAs as DPP row broadcasts (row_dup / bcast_fnma, tsidb_common.hpp)
+// instead of v_readlane pairs - same operations, same bits on lanes 0..31.  Lanes >= 32 end up with other values than
+// the v_readlane form leaves there; the caller reads a[] on lanes < NV only.
+template <typename T, bool DPPB> __device__ __forceinline__ void tick_chol(T (&a)[NV], T &rdv, int &notspd, int &ln) {
+  static_assert(!DPPB || sizeof(T) == 8, "the DPP form is float64 only");
+  // (notspd: a VGPR flag, pinned per pivot: 26 compare masks kept to be and-ed at the end are 52 SGPRs)
+  asm volatile("" : "+v"(ln));
+  auto pivot = [&](int k) __attribute__((always_inline)) -> T {
+    const T akk = rdlane(a[k], k);
+    notspd = akk > 0 ? notspd : 1;
+    asm volatile("" : "+v"(notspd));
+    const T rk = rsqrt_t(akk > 0 ? akk : T(1));
+    if (ln == k) rdv = rk;
+    const T lik = ln == k ? akk * rk : a[k] * rk;
+    a[k] = lik;
+    return lik;
+  };
+  if constexpr (DPPB) {
+    unroll_for<0, NV>([&](auto kk) {
+      constexpr int k = decltype(kk)::value;
+      const T lik = pivot(k);
+      // a[j] -= lik * L[j][k], j = k + 1 .. NV - 1
+      if constexpr (k + 1 < NV) bcast_fnma<((1u << NV) - 1u) & ~((2u << k) - 1u)>(a, row_dup(lik), lik);
+    });
+  } else {
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      // broadcasts four at a time, read ahead of their FMAs (left alone: v_readlane x2 - s_nop 1 - v_fma per entry, every
+      // FMA waiting out the v_readlane -> VALU hazard).  The empty asm takes the four values as SGPR inputs, so they exist
+      // before it, and "changes" lik and the previous group's last result, so that group's FMAs come before it and this
+      // group's after.
+      T lk = pivot(k);
+#pragma unroll
+      for (int j0 = k + 1; j0 < NV; j0 += 4) {
+        const bool p1 = j0 + 1 < NV, p2 = j0 + 2 < NV, p3 = j0 + 3 < NV;
+        const T u0 = rdlane(lk, j0), u1 = p1 ? rdlane(lk, p1 ? j0 + 1 : 0) : T(0), u2 = p2 ? rdlane(lk, p2 ? j0 + 2 : 0) : T(0),
+                u3 = p3 ? rdlane(lk, p3 ? j0 + 3 : 0) : T(0);
+        if (j0 > k + 1) asm volatile("" : "+v"(lk), "+v"(a[j0 - 1]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        else asm volatile("" : "+v"(lk) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
+        a[j0] -= lk * u0;
+        if (p1) a[j0 + 1] -= lk * u1;
+        if (p2) a[j0 + 2] -= lk * u2;
+        if (p3) a[j0 + 3] -= lk * u3;
+      }
+    }
+  }
+}
 
 // --------------------------------------------------------------------------- rigid-body terms
 // Inputs L.qs, L.vs.  Outputs: L.Dyn (M part, rest zero), L.h, L.Jf, L.Jcom, L.oMf, L.vf, L.af,
@@ -1417,35 +1466,8 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
   TSIDB_STAMP(3);
   // ---- Cholesky in registers (right-looking; lane i holds row i of L in a[0..i]); rd[k] = 1/L[k][k]
   T rdv = 0; // lane k: 1 / L[k][k]
-  int notspd = 0; // (a VGPR flag, pinned per pivot: 26 compare masks kept to be and-ed at the end are 52 SGPRs)
-  asm volatile("" : "+v"(ln));
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    const T akk = rdlane(a[k], k);
-    notspd = akk > 0 ? notspd : 1;
-    asm volatile("" : "+v"(notspd));
-    const T rk = rsqrt_t(akk > 0 ? akk : T(1));
-    if (ln == k) rdv = rk;
-    const T lik = ln == k ? akk * rk : a[k] * rk;
-    a[k] = lik;
-    // broadcasts four at a time, read ahead of their FMAs (left alone: v_readlane x2 - s_nop 1 - v_fma per entry, every
-    // FMA waiting out the v_readlane -> VALU hazard).  The empty asm takes the four values as SGPR inputs, so they exist
-    // before it, and "changes" lik and the previous group's last result, so that group's FMAs come before it and this
-    // group's after.
-    T lk = lik;
-#pragma unroll
-    for (int j0 = k + 1; j0 < NV; j0 += 4) {
-      const bool p1 = j0 + 1 < NV, p2 = j0 + 2 < NV, p3 = j0 + 3 < NV;
-      const T u0 = rdlane(lk, j0), u1 = p1 ? rdlane(lk, p1 ? j0 + 1 : 0) : T(0), u2 = p2 ? rdlane(lk, p2 ? j0 + 2 : 0) : T(0),
-              u3 = p3 ? rdlane(lk, p3 ? j0 + 3 : 0) : T(0);
-      if (j0 > k + 1) asm volatile("" : "+v"(lk), "+v"(a[j0 - 1]) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      else asm volatile("" : "+v"(lk) : "s"(u0), "s"(u1), "s"(u2), "s"(u3));
-      a[j0] -= lk * u0;
-      if (p1) a[j0 + 1] -= lk * u1;
-      if (p2) a[j0 + 2] -= lk * u2;
-      if (p3) a[j0 + 3] -= lk * u3;
-    }
-  }
+  int notspd = 0;
+  tick_chol<T, sizeof(T) == 8>(a, rdv, notspd, ln);
   TSIDB_STAMP(4);
   // (the substitutions broadcast L's entries again: carried over from the factorisation they would be 650 SGPRs,
   //  i.e. spilled to VGPR lanes and reloaded - more instructions than reading them again)
