@@ -754,6 +754,15 @@ static void build_model(tsidb_ctx *h, DevModel<T> &m) {
   }
   m.mass = (T)mass;
   memcpy(m.frame_parent, b.i32("pin_frame_parent", 2), sizeof m.frame_parent);
+  for (int f = 0; f < 2; f++) { // k_tick's Hessian assembly leaves out the frame Jacobians' structural zeros by TSID_FRAME_DOFS
+    if (m.frame_parent[f] < 0 || m.frame_parent[f] >= NJ) throw std::string("model blob: contact frame's parent joint out of range");
+    unsigned dofs = 0x3Fu;
+    for (int j = 1; j < NJ; j++)
+      if ((m.pin_anc[m.frame_parent[f]] >> j) & 1u) dofs |= 1u << (5 + j);
+    if (dofs != TSID_FRAME_DOFS[f])
+      throw std::string("model blob's contact-frame joint chains differ from the topology this library was compiled for "
+                        "(regenerate csrc/tsidb_topology.hpp with model_compiler.py and rebuild)");
+  }
   const double *fp = b.f64("pin_frame_place", 24), *q0 = b.f64("pin_q0", NQ);
   for (int i = 0; i < 24; i++) m.frame_place[i / 12][i % 12] = (T)fp[i];
   for (int i = 0; i < NQ; i++) m.q0[i] = (T)q0[i];

@@ -1024,25 +1024,49 @@ __device__ __forceinline__ void tick_qp(const DevModel<T> &m, TickLds<T> &L, QpC
       if (spd && fast_eq) {
         // S = B^T B, one pair (c <= d) per lane and round: 26 dv rows from LDS, the force rows for base-dynamics pairs
         __syncthreads();
-        for (int pidx = lane; pidx < NPAIR; pidx += WAVE) {
-          int d = (int)((sqrtf((float)(8 * pidx + 1)) - 1.0f) * 0.5f); // (pair index -> (c, d), d >= c; float is exact enough
-          d += (d + 1) * (d + 2) / 2 <= pidx ? 1 : 0;                   //  for < 200 pairs, one correction step either way)
-          d -= d * (d + 1) / 2 > pidx ? 1 : 0;
-          const int cc = pidx - d * (d + 1) / 2;
-          T s0 = 0, s1 = 0;
+        // HALFP (single support: 78 pairs are one full round and one of 14 lanes): the two partial sums of a pair, s0 over
+        // the even rows and s1 over the odd ones, go to two neighbouring lanes - 156 half-length jobs in three rounds, i.e.
+        // one and a half full rounds - and are added as before, s0 + s1.
+        constexpr bool HALFP = NS == 1;
+        if constexpr (HALFP) {
+          for (int jdx = lane; jdx < 2 * NPAIR; jdx += WAVE) { // (lanes 2 k, 2 k + 1 share pair k: both in the round or both out)
+            const int pidx = jdx >> 1, hf = jdx & 1;
+            int d = (int)((sqrtf((float)(8 * pidx + 1)) - 1.0f) * 0.5f);
+            d += (d + 1) * (d + 2) / 2 <= pidx ? 1 : 0;
+            d -= d * (d + 1) / 2 > pidx ? 1 : 0;
+            const int cc = pidx - d * (d + 1) / 2;
+            T sh = 0;
 #pragma unroll
-          for (int r = 0; r < NV; r += 2) {
-            s0 += Bl[r * PP + cc] * Bl[r * PP + d];
-            s1 += Bl[(r + 1) * PP + cc] * Bl[(r + 1) * PP + d];
-          }
-          if constexpr (NS > 0) {
+            for (int r = 0; r < NV; r += 2) sh += Bl[(r + hf) * PP + cc] * Bl[(r + hf) * PP + d];
             if (cc >= NC) { // (d >= cc): both are base-dynamics columns
-              const T *fa = fcl + (cc - NC) * 12 * NS, *fb = fcl + (d - NC) * 12 * NS;
+              const T *fa = fcl + (cc - NC) * 12 * NS + hf, *fb = fcl + (d - NC) * 12 * NS + hf;
 #pragma unroll
-              for (int e = 0; e < 12 * NS; e += 2) { s0 += fa[e] * fb[e]; s1 += fa[e + 1] * fb[e + 1]; }
+              for (int e = 0; e < 12 * NS; e += 2) sh += fa[e] * fb[e];
             }
+            const T other = dpp_mov<0xB1, 0xf>(sh); // quad_perm [1,0,3,2]: the neighbour's half
+            if (hf == 0) Sl[pidx] = sh + other;
           }
-          Sl[pidx] = s0 + s1;
+        } else {
+          for (int pidx = lane; pidx < NPAIR; pidx += WAVE) {
+            int d = (int)((sqrtf((float)(8 * pidx + 1)) - 1.0f) * 0.5f); // (pair index -> (c, d), d >= c; float is exact enough
+            d += (d + 1) * (d + 2) / 2 <= pidx ? 1 : 0;                   //  for < 200 pairs, one correction step either way)
+            d -= d * (d + 1) / 2 > pidx ? 1 : 0;
+            const int cc = pidx - d * (d + 1) / 2;
+            T s0 = 0, s1 = 0;
+#pragma unroll
+            for (int r = 0; r < NV; r += 2) {
+              s0 += Bl[r * PP + cc] * Bl[r * PP + d];
+              s1 += Bl[(r + 1) * PP + cc] * Bl[(r + 1) * PP + d];
+            }
+            if constexpr (NS > 0) {
+              if (cc >= NC) { // (d >= cc): both are base-dynamics columns
+                const T *fa = fcl + (cc - NC) * 12 * NS, *fb = fcl + (d - NC) * 12 * NS;
+#pragma unroll
+                for (int e = 0; e < 12 * NS; e += 2) { s0 += fa[e] * fb[e]; s1 += fa[e + 1] * fb[e + 1]; }
+              }
+            }
+            Sl[pidx] = s0 + s1;
+          }
         }
         __syncthreads();
         TSIDB_STAMP(10);
@@ -1413,8 +1437,13 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
   if (lane >= 6 && lane < NV) gi -= w_post * L.k.apost[lane - 6];
   // H[i][j] = sum_r w_r J_r[i] J_r[j]: lane i keeps w_r J_r[i]; J_r[j] is read back from the Jacobians in LDS at a
   // wave-uniform address (one ds_read2_b64 per two values, in the LDS pipe beside the FMAs) instead of a v_readlane
-  // pair + wait states per value from the neighbour's registers: 390 broadcast values per tick
+  // pair + wait states per value from the neighbour's registers: 390 broadcast values per tick.
+  // SKIP0 (the float64 reference stack): the foot rows' products with a column off the frame's root path are left out.
+  // rbd_terms writes an exact +0 there (TSID_FRAME_DOFS is the compile-time form of its ancestor test; tsidb_create
+  // checks the blob against it), both accumulators start at +0, fma(w, +-0, acc) is acc for acc != 0 and +0 + +-0 is
+  // +0, so with finite weights no bit changes - 168 of the 390 FMAs and their LDS reads on the v1 robot.
   {
+    constexpr bool SKIP0 = sizeof(T) == 8 && !COP;
     T wjt[15];
 #pragma unroll
     for (int r = 0; r < 12; r++) wjt[r] = w_foot * jt[r];
@@ -1425,6 +1454,7 @@ __device__ __forceinline__ void tsid_tick_env(const DevModel<T> &m, TickLds<T> &
       T acc = 0, acc1 = 0;
 #pragma unroll
       for (int r = 0; r < 12; r++) {
+        if (SKIP0 && !((TSID_FRAME_DOFS[r / 6] >> j) & 1u)) continue;
         if (r & 1) acc1 += wjt[r] * L.k.Jf[r * LDF + j];
         else acc += wjt[r] * L.k.Jf[r * LDF + j];
       }

@@ -505,12 +505,29 @@ def assemble_blob(ts, sim, out: Path):
     return ts, sim, c0, sections
 
 
-def emit_topology_header(mj_parent, path: Path, nj=None, na=None, has_sim=True, ng=None, condim=3, eulerdamp=False, npair=0):
+def frame_dof_masks(pin_parent, frame_parent):
+    """Bitmask, per contact frame, of the TSID dofs on the frame's root path: the six base dofs and dof 5 + j of every
+    joint j >= 1 that is the frame's parent joint or one of its ancestors.  Every other column of the frame's Jacobian
+    is an exact zero (rbd_terms writes it so)."""
+    masks = []
+    for f in frame_parent:
+        m, j = 0x3F, int(f)
+        while j > 0:
+            m |= 1 << (5 + j)
+            j = int(pin_parent[j])
+        masks.append(m)
+    return masks
+
+
+def emit_topology_header(mj_parent, path: Path, nj=None, na=None, has_sim=True, ng=None, condim=3, eulerdamp=False, npair=0,
+                         pin_parent=None, frame_parent=None):
     """Compile-time facts of ONE robot for libtsidb: the dimensions (TSID joints incl. the free-flyer, nq, nv,
     actuated joints, sim bodies) and the sim tree's dof ancestry for the register Cholesky (tree-sparse elimination
     without run-time branches).  One library is built per robot (`-DTSIDB_TOPOLOGY_HEADER=...`); tsidb_create refuses
     a blob whose dimensions or tree differ.  has_sim=False: a TSID-only robot (no MJCF compiled): the sim tree is a
-    placeholder and the library is built without the sim stage."""
+    placeholder and the library is built without the sim stage.  pin_parent, frame_parent: the TSID tree and the two
+    contact frames' parent joints, for TSID_FRAME_DOFS (frame_dof_masks): k_tick's Hessian assembly skips the products
+    with the Jacobian columns that are structurally zero."""
     nb = len(mj_parent)
     nv = 6 + nb - 1
     nj = nb if nj is None else nj
@@ -546,6 +563,9 @@ def emit_topology_header(mj_parent, path: Path, nj=None, na=None, has_sim=True, 
            f"TOPO_MAXPAIR = {max(64, (npair + 63) // 64 * 64)};\n"
            "constexpr int TOPO_PARENT[] = {" + ", ".join(str(int(x)) for x in mj_parent) + "};\n"
            "constexpr unsigned MJ_DOFANC[] = {" + ", ".join(hex(x) + "u" for x in dofanc) + "};\n"
+           "// TSID side, TSID dof order: TSID_FRAME_DOFS[f] is the bitmask of the dofs on contact frame f's root path (the six\n"
+           "// base dofs and the frame's joint chain); every other column of the frame's Jacobian is an exact zero\n"
+           "constexpr unsigned TSID_FRAME_DOFS[] = {" + ", ".join(hex(x) + "u" for x in frame_dof_masks(pin_parent, frame_parent)) + "};\n"
            "} // namespace tsidb\n")
     path.write_text(txt)
 
@@ -703,12 +723,27 @@ def build_sim_model_mjcf(mjcf: Path, mesh_dir: Path):
     )
 
 
+def regenerate_headers():
+    """Both robots' topology headers from the committed blobs under assets/ (no robot description needed)."""
+    from .model import ModelBlob
+    here = Path(__file__).parent
+    for blob, hdr in (("op3_v1.tsidb", "tsidb_topology.hpp"), ("op3_v0.tsidb", "tsidb_topology_v0.hpp")):
+        sec = ModelBlob(here / "assets" / blob)
+        emit_topology_header(sec["mj_parent"], here / "csrc" / hdr, ng=len(sec["mj_geom_body"]), condim=int(sec["mj_contact"][8]),
+                             eulerdamp=bool(sec["mj_damping"].any()), npair=len(sec["mj_pairs"]) // 2,
+                             pin_parent=sec["pin_parent"], frame_parent=sec["pin_frame_parent"])
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--headers"]:
+        regenerate_headers()
+        sys.exit(0)
     ref = Path(sys.argv[1] if len(sys.argv) > 1 else "/root/reference")
     out = Path(sys.argv[2] if len(sys.argv) > 2 else Path(__file__).parent / "assets" / "op3_v1.tsidb")
     ts, sim, c0, sec = compile_model(ref, out)
     emit_topology_header(sec["mj_parent"], Path(__file__).parent / "csrc" / "tsidb_topology.hpp",
-                         ng=len(sec["mj_geom_body"]), npair=len(sec["mj_pairs"]))
+                         ng=len(sec["mj_geom_body"]), npair=len(sec["mj_pairs"]),
+                         pin_parent=sec["pin_parent"], frame_parent=sec["pin_frame_parent"])
     # the v0 robot (legacy/op3_conf.py:53-62): robot/v0/robot.urdf + robot.srdf, robot/v0/robot.xml + meshes/*.stl
     v0 = ref / "robot" / "v0"
     ts0 = build_tsid_model(v0 / "robot.urdf", v0 / "robot.srdf", ["leg_left_sole_joint_fixed", "leg_right_sole_joint_fixed"])
@@ -716,7 +751,7 @@ if __name__ == "__main__":
     _, _, _, sec0 = assemble_blob(ts0, sim0, out.parent / "op3_v0.tsidb")
     emit_topology_header(sec0["mj_parent"], Path(__file__).parent / "csrc" / "tsidb_topology_v0.hpp",
                          ng=len(sec0["mj_geom_body"]), condim=int(sec0["mj_contact"][8]), eulerdamp=bool(sec0["mj_damping"].any()),
-                         npair=len(sec0["mj_pairs"]))
+                         npair=len(sec0["mj_pairs"]), pin_parent=sec0["pin_parent"], frame_parent=sec0["pin_frame_parent"])
     print("v0 joints:", ts0["names"], "mass", ts0["inertia"][:, 0].sum(), "geoms", len(sec0["mj_geom_body"]), "pairs", len(sec0["mj_pairs"]))
     print("joints:", ts["names"])
     print("total mass (TSID):", ts["inertia"][:, 0].sum(), " (sim):", sum(b["inertia"].mass for b in sim["bodies"]))
