@@ -484,7 +484,8 @@ int tsidb_policy_perturb(tsidb_handle h, const tsidb_policy_bufs *bufs, void *st
  * reset_joint_vel noise, qvel[0:3] and qvel[3:6] += their component's noise, qpos[0:2] += reset_xy noise, qpos[2] += reset_lift,
  * and the base quaternion (wxyz) becomes (c, 0, 0, s) * quat, c = cos(t / 2), s = sin(t / 2) of t = reset_yaw (2 U - 1) formed
  * in float64 and cast - a rotation about world z - divided by its norm.  A group whose amplitude is 0 adds nothing.  The TSID
- * state q, v is left as the reset wrote it: the policy environment runs no tick, and a caller that does must copy the state over.
+ * state q, v is left as the reset wrote it: without TSID in the loop (below) the policy environment runs no tick, and with it the
+ * closed-loop tick reads the sim state itself.
  * Launches nothing and succeeds while every reset_* value is 0. */
 int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, void *qpos,
                              void *qvel, void *stream);
@@ -496,6 +497,60 @@ int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
  * cmd_lo != cmd_hi are redrawn and the others stay as they are.  Noise: columns 0-2 += noise_ang_vel, 3-5 += noise_gravity,
  * 9 .. 9 + NA - 1 += noise_joint_pos, 9 + NA .. 9 + 2 NA - 1 += noise_joint_vel draws (stream 7, column = the observation column);
  * command, last action, contact flags and the privileged tail stay exact, and qpos / qvel are not touched. */
+
+/* ---- TSID in the loop of the policy environment: the policy steps the closed-loop tsidb_step (params[CLOSED_LOOP]; tick on the
+ * sim state, then sim) in place of tsidb_sim_ctrl, and two more launches score it against the controller and show it the
+ * controller's references.  One policy step is then tsidb_policy_act, decimation closed-loop env steps (tsidb_walk_update +
+ * tsidb_step when a walking plan runs), tsidb_policy_reward, tsidb_policy_teacher, tsidb_reset_done (+ tsidb_walk_plan for the
+ * done envs), tsidb_policy_obs, tsidb_policy_teacher_obs.  What ctrl means is tsidb_set_ctrl's mode: TSIDB_CTRL_RESIDUAL = the
+ * policy adds a torque to TSID's tau; TSIDB_CTRL_MOTOR / _POSITION = the policy alone drives the sim and TSID is the teacher.
+ * Both launches are plain asynchronous launches that can be captured.  Both fail (message via tsidb_last_error) in a library
+ * built without the sim stage, while no ctrl buffer is registered, before tsidb_policy_config and before
+ * tsidb_policy_teacher_config, and without the reference buffers (tsidb_set_refs).
+ *
+ * Teacher terms, unweighted, in the order of teacher_terms [N, TSIDB_POL_TEACH_NT] and of the weights; com, LF, RF are the
+ * columns of the tick's row (tsidb_tick obs: q v com cop LF RF), com_ref / foot_ref / contact_active the registered references:
+ *   track_com      exp(-|com - com_ref.pos|^2 / sigma_com^2)
+ *   track_feet     exp(-(|LF - foot_ref[0].p|^2 + |RF - foot_ref[1].p|^2) / sigma_foot^2)
+ *   contact_match  the number of feet (0 .. 2) whose sim contact flag c_f (tsidb_policy_reward) equals contact_active[f]
+ *   deviation      sum_a ctrl_a^2 in TSIDB_CTRL_RESIDUAL mode, sum_a (ctrl_a - tau[mj_ctrl_qidx[a] - 7])^2 in TSIDB_CTRL_MOTOR mode
+ *                  (tau in the actuator order), 0 in TSIDB_CTRL_POSITION mode */
+enum { TSIDB_POL_TEACH_NT = 4, TSIDB_POL_TEACH_NOBS = 34 /* 14 + NA: the v1 robot's; 32 for robot/v0 */ };
+
+/* tsidb_policy_teacher_config's parameter vector (float64, host) */
+enum {
+  TSIDB_POL_TEACH_SIGMA_COM = 0 /* m, > 0 */, TSIDB_POL_TEACH_SIGMA_FOOT /* m, > 0 */, TSIDB_POL_TEACH_WEIGHTS /*TSIDB_POL_TEACH_NT*/,
+  TSIDB_POL_TEACH_NPARAMS = TSIDB_POL_TEACH_WEIGHTS + TSIDB_POL_TEACH_NT
+};
+
+/* Copies teach_params [TSIDB_POL_TEACH_NPARAMS] into the handle; first waits for the kernels in flight, as tsidb_policy_config
+ * does.  Rejects a wrong n_params, non-finite values and a sigma <= 0; nothing of a rejected vector is taken. */
+int tsidb_policy_teacher_config(tsidb_handle h, const double *teach_params, int n_params);
+
+/* after tsidb_policy_reward, before tsidb_reset_done.  rows [N, rows_ld >= TSIDB_NROW] as the last tick of tsidb_step wrote them,
+ * with reward and done in columns TSIDB_NOBS and TSIDB_NOBS + 1 as tsidb_policy_reward left them; q [N, NQ] the TSID state that
+ * tick ended on, tau [N, NA] and status [N] its outputs, ncon / con_pairs the last sim step's.  Writes teacher_terms and
+ * reward += sum_k weights[k] teacher_terms[k].  An env whose status != 0 (TSID's QP failed) becomes terminated: done = 1,
+ * timeout = 0, the termination term of tsidb_policy_bufs.terms set to 1, and reward += the termination weight of
+ * tsidb_policy_config unless tsidb_policy_reward had terminated the env already.  Writes teacher_action [N, NA], the action
+ * that reproduces TSID's command through tsidb_policy_act's map (no delay, no filter), clipped to +-clip and 0 where
+ * scale[a] = 0: (tau[mj_ctrl_qidx[a] - 7] - default[a]) / scale[a] in TSIDB_CTRL_MOTOR mode, (q[mj_ctrl_qidx[a]] - default[a]) /
+ * scale[a] in TSIDB_CTRL_POSITION mode, 0 in TSIDB_CTRL_RESIDUAL mode.  All of this launch's arithmetic runs in float64 on the
+ * path's buffers, with scale, default, clip and the weights as the two config calls were given them, and is cast once when it is
+ * stored - as the randomisation forms its draws. */
+int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *rows, int rows_ld, const void *q, const void *tau,
+                         const int32_t *status, const int32_t *ncon, const int32_t *con_pairs, void *teacher_terms,
+                         void *teacher_action, void *stream);
+
+/* after tsidb_policy_obs.  Writes teacher_obs [N, obs_ld >= 14 + NA]; R is the rotation of the sim base (qpos, wxyz), so R^T v
+ * is v in the base frame, as the observation's velocities:
+ *   0-1 contact_active of the two feet   2-4 R^T (com_ref.pos - com)   5-7 R^T com_ref.vel   8-10 R^T (foot_ref[0].p - LF)
+ *   11-13 R^T (foot_ref[1].p - RF)   14.. TSID's tau in the actuator order (NA: tau[mj_ctrl_qidx[a] - 7])
+ * For an env the step just restarted (done flag in column TSIDB_NOBS + 1 of rows) the three error groups and tau are 0 - the
+ * tick's row is the fallen robot's, and a reset robot stands on its references - while contact_active and com_ref.vel are what
+ * the reset wrote.  No noise is ever added to these columns. */
+int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *rows, int rows_ld, const void *qpos,
+                             const void *tau, void *teacher_obs, int obs_ld, void *stream);
 
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */

@@ -12,7 +12,12 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
     python tools/policy_env.py --trace ENVS STEPS  (a short run of (c) alone, for rocprofv3 --kernel-trace --stats)
     python tools/policy_env.py --randomize [out.json]   (c) with every group of the randomisation on (PolicyRandomization: reset
               noise, observation noise, pushes of at most 1 N, command resampling) against (c) with it off, in alternating
-              windows, at 4096 and 512 envs, decimation 4 and 10; default profiles/policy_dr.json"""
+              windows, at 4096 and 512 envs, decimation 4 and 10; default profiles/policy_dr.json
+    python tools/policy_env.py --tsid stand|walk [--mode residual|motor|position] [out.json]   TSID in the loop (PolicyEnv(tsid=...),
+              default mode residual) against the hand-driven closed loop over the same number of sim steps (wc.step, in "walk" behind
+              sched.apply on a device clock), against the same env with the two teacher launches left out, and against the bare
+              tsid=None env, in alternating windows, at 4096 and 512 envs, decimation 4; default profiles/policy_tsid.json (the file
+              keeps one entry per (tsid, mode): a run replaces its own and leaves the others)"""
 import json
 import sys
 import time
@@ -189,7 +194,93 @@ def measure_randomize(n, decimation, window=300, windows=4, preroll=60):
                 standing_height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
 
 
+TEACH = dict(track_com=1.0, track_feet=1.0, contact_match=0.25, deviation=-0.01)
+
+
+class NoTeacher(PolicyEnv):
+    """the tsid env without its two teacher launches: what they add is the difference to the full env"""
+
+    def _teacher(self):
+        pass
+
+    def _teacher_obs(self):
+        pass
+
+
+def measure_tsid(n, tsid, mode, decimation=4, window=100, windows=4, preroll=20):
+    """policy-steps/s of hand (the closed loop alone), tsid (PolicyEnv with TSID in the loop), noteacher (that without the two
+    new launches) and bare (tsid=None, position mode: tsidb_sim_ctrl only), in alternating windows of one process"""
+    from tsid_control_amd.walk_planner import WalkSchedule, op3_closed_loop_walking_conf, op3_walking_posture
+    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+
+    def conf():
+        c = op3_closed_loop_walking_conf(RobotConfig()) if tsid == "walk" else RobotConfig()
+        c.closed_loop, c.reference_quirks = True, False
+        return c
+
+    kw = dict(KW, action_scale=dict(residual=0.05, motor=0.3, position=0.25)[mode])
+    make = lambda cls: cls(conf(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, tsid=tsid, mode=mode, teacher_weights=TEACH, **kw)
+    envs = dict(tsid=make(PolicyEnv), noteacher=make(NoTeacher),
+                bare=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW))
+    hand = WalkController(conf(), num_envs=n, device="cuda:0")
+    dt = hand.conf.dt
+    if tsid == "walk":
+        hand.set_posture_bias(op3_walking_posture())
+        clock = torch.zeros(1, dtype=torch.float64, device=hand.device)
+        sched = WalkSchedule.on_device(hand, foot_press=0.0)
+        sched.enable_touchdown_feedback()
+
+        def hand_step():
+            for _ in range(decimation):
+                sched.apply(hand, 0.0, t_device=clock)
+                hand.step(1)
+                clock.add_(dt)
+    else:
+        hand_step = lambda: hand.step(decimation)
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, hand.NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    run = dict(hand=lambda k: [hand_step() for _ in range(k)])
+    for name, env in envs.items():
+        run[name] = lambda k, env=env: [env.step(actions[i & 15]) for i in range(k)]
+    for fn in run.values():
+        fn(preroll)
+    torch.cuda.synchronize()
+    res = {k: [] for k in run}
+    order = list(run)
+    for w in range(windows):
+        for name in order[w % 4:] + order[:w % 4]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run[name](window)
+            torch.cuda.synchronize()
+            res[name].append(window / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    us = {k: 1e6 / v for k, v in med.items()}
+    return dict(envs=n, tsid=tsid, mode=mode, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med,
+                all=res, us_per_policy_step=us, tsid_over_hand=med["tsid"] / med["hand"], tsid_over_bare=med["tsid"] / med["bare"],
+                policy_layer_us_per_policy_step=us["tsid"] - us["hand"], teacher_launches_us_per_policy_step=us["tsid"] - us["noteacher"],
+                restarts={k: int(e.episode.sum()) - n for k, e in envs.items()}, failed_qp_hand=int((hand.status != 0).sum()),
+                height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--tsid":
+        import os
+        tsid, rest = sys.argv[2], sys.argv[3:]
+        mode = "residual"
+        if rest and rest[0] == "--mode":
+            mode, rest = rest[1], rest[2:]
+        out_path = rest[0] if rest else "profiles/policy_tsid.json"
+        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", runs={})
+        if os.path.exists(out_path):
+            with open(out_path) as f:
+                out["runs"] = json.load(f).get("runs", {})
+        out["runs"][f"{tsid}/{mode}"] = [measure_tsid(n, tsid, mode) for n in (4096, 512)]
+        text = json.dumps(out, indent=1)
+        print(text)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--randomize":
         out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_dr.json"
         out = dict(device=torch.cuda.get_device_name(0), dtype="f64", randomization=RANDOMIZATION,

@@ -14,7 +14,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_reset_done", "tsidb_set_posture_bias", "tsidb_walk_plan", "tsidb_set_option", "tsidb_tick_walk", "tsidb_sim_batch", "tsidb_stream_create", "tsidb_stream_destroy", "tsidb_get_option",
            "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl",
            "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs",
-           "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise"]
+           "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise",
+           "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -40,6 +41,17 @@ POL_DR_SEED, POL_DR_ENV_OFFSET, POL_DR_RESET_JOINT_POS, POL_DR_RESET_JOINT_VEL, 
     POL_DR_RESET_YAW, POL_DR_RESET_XY, POL_DR_RESET_LIFT, POL_DR_NOISE_ANG_VEL, POL_DR_NOISE_GRAVITY, POL_DR_NOISE_JOINT_POS, \
     POL_DR_NOISE_JOINT_VEL, POL_DR_PUSH_INTERVAL, POL_DR_PUSH_DURATION, POL_DR_PUSH_FORCE_LO, POL_DR_PUSH_FORCE_HI, \
     POL_DR_COMMAND_INTERVAL, POL_DR_COMMAND_ZERO_PROB, POL_DR_NPARAMS = 0, 1, 2, 3, 4, 7, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23
+
+# TSID in the loop of the policy environment (include/tsidb.h TSIDB_POL_TEACH_*): the teacher terms in the order of the
+# teacher_terms row and of the weights, and the layout of tsidb_policy_teacher_config's parameter vector
+POL_TEACH_TERMS = ("track_com", "track_feet", "contact_match", "deviation")
+POL_TEACH_NT = 4
+POL_TEACH_SIGMA_COM, POL_TEACH_SIGMA_FOOT, POL_TEACH_WEIGHTS, POL_TEACH_NPARAMS = 0, 1, 2, 6
+
+
+def pol_teach_nobs(na):
+    """columns of the teacher observation for a robot with na actuators (TSIDB_POL_TEACH_NOBS is the v1 robot's)"""
+    return 14 + na
 
 
 def pol_nobs(na):
@@ -134,6 +146,9 @@ def load(path=None):
     L.tsidb_policy_randomize.argtypes = [vp, vp, C.c_int]
     L.tsidb_policy_perturb.argtypes = [vp, vp, vp]
     L.tsidb_policy_reset_noise.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    L.tsidb_policy_teacher_config.argtypes = [vp, vp, C.c_int]
+    L.tsidb_policy_teacher.argtypes = [vp, vp, vp, C.c_int, vp, vp, i32p, i32p, i32p, vp, vp, vp]
+    L.tsidb_policy_teacher_obs.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -678,6 +678,8 @@ static_assert((int)CTRL_POSITION == TSIDB_CTRL_POSITION && (int)CTRL_MOTOR == TS
               "include/tsidb.h and the kernels agree on the ctrl modes");
 static_assert(POL_NT == TSIDB_POL_NT && POL_HIST == TSIDB_POL_HIST && POL_NPRIV == TSIDB_POL_NPRIV && (NA != 20 || POL_NOBS == TSIDB_POL_NOBS),
               "include/tsidb.h and the kernels agree on the policy environment's rows");
+static_assert(POL_TEACH_NT == TSIDB_POL_TEACH_NT && (NA != 20 || POL_TEACH_NOBS == TSIDB_POL_TEACH_NOBS),
+              "include/tsidb.h and the kernels agree on the teacher's rows");
 
 // Batches up to this many envs default to two wavefronts per env in k_sim and to CU-split streams (tsidb_stream_create):
 // measured, DESIGN.md section 5 "Streams"
@@ -721,6 +723,8 @@ struct tsidb_ctx {
   double pol[TSIDB_POL_NPARAMS] = {}, pol_scale[NA] = {}, pol_def[NA] = {};
   unsigned pol_mask = 0;
   double pol_dr[TSIDB_POL_DR_NPARAMS] = {}; // tsidb_policy_randomize's vector; all 0 = every group off
+  bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
+  double teach[TSIDB_POL_TEACH_NPARAMS] = {};
   std::string err;
 };
 
@@ -1210,6 +1214,14 @@ static bool dr_obs_on(const tsidb_ctx *h) {
          h->pol_dr[TSIDB_POL_DR_ENV_OFFSET] != 0;
 }
 
+// what both teacher launches need on top of policy_bufs: the teacher's configuration and the registered references
+template <typename T>
+static PolicyRefs<T> policy_teacher_refs(const tsidb_ctx *h, const char *who) {
+  if (!h->teach_set) throw std::string(who) + "not configured (call tsidb_policy_teacher_config first)";
+  if (!h->com_ref || !h->foot_ref || !h->contact_active) throw std::string(who) + "reference buffers not registered (call tsidb_set_refs first)";
+  return PolicyRefs<T>{(const T *)h->com_ref, (const T *)h->foot_ref, h->contact_active};
+}
+
 static dim3 policy_grid(const tsidb_ctx *h) { return dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK); }
 
 extern "C" {
@@ -1342,6 +1354,66 @@ int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
     h->note_stream(s);
     hipLaunchKernelGGL(k_policy_reset_noise<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, b,
                        policy_dr(h), (const T *)done_rows, rows_ld, (T *)qpos, (T *)qvel);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_teacher_config(tsidb_handle h, const double *teach_params, int n_params) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_teacher_config: ";
+  if (lacks_sim(h, true, who)) throw h->err;
+  if (!teach_params || n_params != TSIDB_POL_TEACH_NPARAMS) throw std::string(who) + "needs TSIDB_POL_TEACH_NPARAMS parameters";
+  for (int i = 0; i < n_params; i++) if (!std::isfinite(teach_params[i])) throw std::string(who) + "non-finite parameter";
+  if (!(teach_params[TSIDB_POL_TEACH_SIGMA_COM] > 0) || !(teach_params[TSIDB_POL_TEACH_SIGMA_FOOT] > 0)) throw std::string(who) + "sigma_com and sigma_foot must be positive";
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->teach, teach_params, sizeof h->teach);
+  h->teach_set = true;
+  GUARD_END
+}
+
+int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *rows, int rows_ld, const void *q, const void *tau,
+                         const int32_t *status, const int32_t *ncon, const int32_t *con_pairs, void *teacher_terms, void *teacher_action,
+                         void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const char *who = "tsidb_policy_teacher: ";
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
+    const PolicyRefs<T> r = policy_teacher_refs<T>(h, who);
+    if (!rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows of the last tick (reward and done in columns TSIDB_NOBS, TSIDB_NOBS + 1)";
+    if (!q || !tau || !status || !ncon || !con_pairs || !teacher_terms || !teacher_action) throw std::string(who) + "null buffer";
+    PolicyTeach tc;
+    tc.sigma_com = h->teach[TSIDB_POL_TEACH_SIGMA_COM]; tc.sigma_foot = h->teach[TSIDB_POL_TEACH_SIGMA_FOOT];
+    for (int k = 0; k < POL_TEACH_NT; k++) tc.w[k] = h->teach[TSIDB_POL_TEACH_WEIGHTS + k];
+    tc.w_termination = h->pol[TSIDB_POL_P_WEIGHTS + POL_T_TERMINATION]; tc.clip = h->pol[TSIDB_POL_P_CLIP];
+    for (int a = 0; a < NA; a++) { tc.scale[a] = h->pol_scale[a]; tc.def[a] = h->pol_def[a]; }
+    tc.ctrl_mode = h->ctrl_mode;
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_teacher<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
+                       policy_cfg<T>(h), tc, b, r, (T *)rows, rows_ld, (const T *)q, (const T *)tau, status, ncon, con_pairs, (const T *)h->ctrl,
+                       (T *)teacher_terms, (T *)teacher_action);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *rows, int rows_ld, const void *qpos, const void *tau,
+                             void *teacher_obs, int obs_ld, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const char *who = "tsidb_policy_teacher_obs: ";
+    policy_bufs<T>(h, bufs, who);
+    const PolicyRefs<T> r = policy_teacher_refs<T>(h, who);
+    if (!rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)";
+    if (!qpos || !tau || !teacher_obs) throw std::string(who) + "null buffer";
+    if (obs_ld < POL_TEACH_NOBS) throw std::string(who) + "teacher_obs row stride must be at least 14 + NA";
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_teacher_obs<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, r,
+                       (const T *)rows, rows_ld, (const T *)qpos, (const T *)tau, (T *)teacher_obs, obs_ld);
   });
   HIP_OK(hipGetLastError());
   GUARD_END

@@ -11,6 +11,7 @@
 // and a wavefront per env keeps every load of a row one transaction.
 #pragma once
 #include "tsidb_common.hpp"
+#include "tsidb_sim.hpp" // CTRL_*
 
 namespace tsidb {
 
@@ -332,6 +333,117 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_reset_nois
     else if (d.reset_lift != 0) qp[2] += (T)d.reset_lift;
   }
   if (d.reset_yaw != 0 && lane >= 3 && lane < 7) qp[lane] = lane == 3 ? w : lane == 4 ? x : lane == 5 ? y : z;
+}
+
+// ---------------------------------------------------------------------------- TSID in the loop: the teacher
+constexpr int POL_TEACH_NT = 4;           // teacher terms (TSIDB_POL_TEACH_NT)
+constexpr int POL_TEACH_NOBS = 14 + NA;   // columns of the teacher observation (TSIDB_POL_TEACH_NOBS for the v1 robot)
+constexpr int ROW_COM = NQ + NV, ROW_LF = NQ + NV + 6, ROW_RF = NQ + NV + 9;   // the tick's row: q v com cop LF RF
+enum { POL_TT_TRACK_COM = 0, POL_TT_TRACK_FEET, POL_TT_CONTACT_MATCH, POL_TT_DEVIATION };
+
+// tsidb_policy_teacher_config's values and what the teacher needs of tsidb_policy_config's; ctrl_mode is tsidb_set_ctrl's.
+// float64 whatever the path's type: the teacher's arithmetic runs in float64 on the path's buffers and is cast once when it is
+// stored (include/tsidb.h) - a dozen scalar operations per env, and the float32 path's reward is rounded once instead of six times
+struct PolicyTeach {
+  double sigma_com, sigma_foot, w[POL_TEACH_NT], w_termination, clip, scale[NA], def[NA];
+  int ctrl_mode;
+};
+
+// the registered references the two kernels read (tsidb_set_refs)
+template <typename T>
+struct PolicyRefs {
+  const T *com_ref, *foot_ref;
+  const uint8_t *contact_active;
+};
+
+// after k_policy_reward, before k_reset: the teacher terms into the reward, a failed QP into done, TSID's command as an action.
+// Lanes 0 .. 8 hold one component each of com - com_ref, LF - foot_ref[0].p, RF - foot_ref[1].p; lane a < NA actuator a.
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_teacher(const DevModel<T> *__restrict__ mp, int n, PolicyCfg<T> c, PolicyTeach tc,
+                                                                              PolicyBufs<T> b, PolicyRefs<T> r, T *rows, int rows_ld,
+                                                                              const T *__restrict__ q, const T *__restrict__ tau,
+                                                                              const int *__restrict__ status, const int *__restrict__ ncon,
+                                                                              const int *__restrict__ con_pairs, const T *__restrict__ ctrl,
+                                                                              T *teacher_terms, T *teacher_action) {
+  const DevModel<T> &m = *mp;
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  T *row = rows + E * rows_ld;
+  double ec = 0, ef = 0, dev = 0;
+  if (lane < 9) {
+    const int g = lane / 3, k = lane - 3 * g;
+    const double have = row[g == 0 ? ROW_COM + k : g == 1 ? ROW_LF + k : ROW_RF + k];
+    const double want = g == 0 ? r.com_ref[E * 9 + k] : r.foot_ref[(E * 2 + (g - 1)) * 24 + k];
+    const double d = have - want;
+    if (g == 0) ec = d * d; else ef = d * d;
+  }
+  if (lane < NA) {
+    const int qi = m.mj_ctrl_qidx[lane];
+    const double u = ctrl[E * NA + lane], ta = tau[E * NA + qi - 7];
+    const double x = tc.ctrl_mode == CTRL_RESIDUAL ? u : tc.ctrl_mode == CTRL_MOTOR ? u - ta : 0.0;
+    dev = x * x;
+    double act = 0;
+    if (tc.ctrl_mode != CTRL_RESIDUAL && tc.scale[lane] != 0) {
+      const double cmd = tc.ctrl_mode == CTRL_MOTOR ? ta : (double)q[E * NQ + qi];
+      const double a = (cmd - tc.def[lane]) / tc.scale[lane];
+      act = a > tc.clip ? tc.clip : a < -tc.clip ? -tc.clip : a;
+    }
+    teacher_action[E * NA + lane] = (T)act;
+  }
+  wave_sum3(ec, ef, dev);
+  const int con = pol_contacts(m, c, ncon, con_pairs, E, lane);
+  const int a0 = r.contact_active[E * 2] != 0, a1 = r.contact_active[E * 2 + 1] != 0;
+  double t[POL_TEACH_NT];
+  t[POL_TT_TRACK_COM] = exp(-ec / (tc.sigma_com * tc.sigma_com));
+  t[POL_TT_TRACK_FEET] = exp(-ef / (tc.sigma_foot * tc.sigma_foot));
+  t[POL_TT_CONTACT_MATCH] = (double)(((con & 1) == a0) + (((con >> 1) & 1) == a1));
+  t[POL_TT_DEVIATION] = dev;
+  double add = 0, mine = 0;
+#pragma unroll
+  for (int k = 0; k < POL_TEACH_NT; k++) {
+    add += tc.w[k] * t[k];
+    mine = lane == k ? t[k] : mine;
+  }
+  if (lane < POL_TEACH_NT) teacher_terms[E * POL_TEACH_NT + lane] = (T)mine;
+  if (lane == 0) {
+    double rew = (double)row[NROW - 2] + add;
+    if (status[E] != 0) {   // TSID's QP failed: terminated, whatever k_policy_reward decided
+      if (b.terms[E * POL_NT + POL_T_TERMINATION] == T(0)) rew += tc.w_termination;
+      b.terms[E * POL_NT + POL_T_TERMINATION] = 1;
+      b.timeout[E] = 0;
+      row[NROW - 1] = 1;
+    }
+    row[NROW - 2] = (T)rew;
+  }
+}
+
+// after k_policy_obs: the controller's references as the policy sees them, in the base frame of the sim state.  Lanes 0 .. 11
+// hold one component each of the four vectors; lane a < NA the actuator's tau
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_teacher_obs(const DevModel<T> *__restrict__ mp, int n, PolicyRefs<T> r,
+                                                                                  const T *__restrict__ rows, int rows_ld, const T *__restrict__ qpos,
+                                                                                  const T *__restrict__ tau, T *out, int out_ld) {
+  const DevModel<T> &m = *mp;
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  const T *row = rows + E * rows_ld, *qp = qpos + E * NQ;
+  const bool fresh = row[NROW - 1] != T(0);
+  T *o = out + E * out_ld;
+  if (lane < 2) o[lane] = r.contact_active[E * 2 + lane] ? T(1) : T(0);
+  if (lane < 12) {
+    const int g = lane / 3, k = lane - 3 * g;   // 0 com error, 1 com velocity, 2 LF error, 3 RF error
+    T R[9], w[3];
+    quat_to_R(qp[4], qp[5], qp[6], qp[3], R);   // wxyz storage
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+      w[j] = g == 0 ? r.com_ref[E * 9 + j] - row[ROW_COM + j] : g == 1 ? r.com_ref[E * 9 + 3 + j]
+           : g == 2 ? r.foot_ref[E * 48 + j] - row[ROW_LF + j] : r.foot_ref[E * 48 + 24 + j] - row[ROW_RF + j];
+    const T v = R[k] * w[0] + R[3 + k] * w[1] + R[6 + k] * w[2];   // R^T w
+    o[2 + lane] = fresh && g != 1 ? T(0) : v;
+  }
+  if (lane < NA) o[14 + lane] = fresh ? T(0) : tau[E * NA + m.mj_ctrl_qidx[lane] - 7];
 }
 
 } // namespace tsidb

@@ -13,6 +13,12 @@ With a PolicyRandomization two more launches join them, each only while its grou
 force before the sim steps (tsidb_policy_perturb), noise on the state of the envs just reset before the observation
 (tsidb_policy_reset_noise) - and the obs launch resamples commands and adds observation noise.  Every draw is a hash of
 (seed, stream, column, env, episode, ep_len): no random state, so a captured step replays and a split batch draws alike.
+
+With tsid = "stand" or "walk" the batched TSID controller is in the loop: the sim stage of a step is `decimation` closed-loop env
+steps (tick on the sim state, then sim; in "walk" each behind the walking reference update on a device clock) and two more
+launches join the step - after the reward the teacher terms, TSID's failed QPs and its command as an action
+(tsidb_policy_teacher), after the observation the controller's references in the base frame (tsidb_policy_teacher_obs).
+mode = "residual" adds the policy's torque to TSID's tau; "position" / "motor" leave the sim to the policy and TSID beside it.
 """
 import copy
 import ctypes as C
@@ -119,26 +125,62 @@ class PolicyEnv:
 
     Tensors, all used in place: obs [N, NOBS], priv [N, 4] (base linear velocity in the body frame, base height), reward [N],
     done [N] (views of wc.rows), command [N, 3], delay [N], terms [N, 12], timeout [N], ep_len [N], episode [N], last_action,
-    prev_action [N, NA], air_time [N, 2], act_hist [8, N, NA]; wc is the WalkController underneath."""
+    prev_action [N, NA], air_time [N, 2], act_hist [8, N, NA]; wc is the WalkController underneath.
+
+    tsid: None (no tick: the environment above), "stand" or "walk" - TSID in the loop; conf must then have closed_loop = True
+    (walk_planner.op3_closed_loop_walking_conf for walking).  "stand": one wc.step(decimation) per policy step.  "walk": per sim
+    step the walking reference update at the device clock self.clock (float64 [1]), one closed-loop env step, clock += dt;
+    self.sched is the WalkSchedule.on_device(wc, **walk) the env builds - walk: its keyword arguments (default foot_press = 0)
+    plus touchdown_feedback (fraction of the swing, default 0.6; None = off) and posture_bias ([NA] added to the posture
+    reference, default walk_planner.op3_walking_posture() for the 20-actuator robot); the envs a step or reset() restarts are
+    replanned on a new path with their clocks at self.clock.  mode "residual" (only with tsid): ctrl = default_joint_pos
+    (default 0) + action_scale * action is a torque [N m] added to TSID's tau.  teacher_weights: {term: weight} over
+    _lib.POL_TEACH_TERMS added to the reward, sigma_com / sigma_foot [m] the widths of the two tracking terms (a reset leaves
+    the foot references at the identity placement and only a walking schedule writes them: track_feet and the foot errors of
+    teacher_obs mean something with tsid = "walk").  Reset noise
+    that moves the base (reset_xy, reset_yaw, reset_lift) is rejected with tsid: the plan and the contact references start
+    where the reset put the robot.  More tensors: teacher_terms [N, 4], teacher_action [N, NA], teacher_obs [N, 14 + NA]
+    (include/tsidb.h tsidb_policy_teacher / _teacher_obs), all three in step()'s info."""
 
     # the randomisation's launches a step makes; class-level so that an instance built without __init__ steps unrandomised
     randomization = None
     _dr_push = _dr_reset = False
+    # TSID in the loop: None = no tick; sched = the walking schedule of tsid = "walk", clock its device time
+    tsid = sched = clock = None
 
     def __init__(self, conf=None, num_envs=None, device=None, decimation=10, mode="position", action_scale=0.25,
                  default_joint_pos=None, action_clip=100.0, delay=None, filter_alpha=1.0, command_range=((0.0, 0.0),) * 3,
                  max_episode_steps=0, reward_weights=None, term_bodies=None, sigma=0.25, h_target=None, t_air=0.25, deadband=0.1,
-                 seed=0, randomization=None):
+                 seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05):
         from .conf import RobotConfig
         conf = copy.copy(conf) if conf is not None else RobotConfig()
         conf.reference_quirks = False
         conf.sim_enabled = True
-        if mode not in ("position", "motor"):
-            raise _lib.TsidbError(f"PolicyEnv: mode must be 'position' or 'motor', got {mode!r}")
+        if tsid not in (None, "stand", "walk"):
+            raise _lib.TsidbError(f"PolicyEnv: tsid must be None, 'stand' or 'walk', got {tsid!r}")
+        if mode not in ("position", "motor") and not (mode == "residual" and tsid is not None):
+            raise _lib.TsidbError(f"PolicyEnv: mode must be 'position' or 'motor', or 'residual' with tsid = 'stand' / 'walk' "
+                                  f"(a residual needs TSID's tau to add to), got {mode!r}")
         dr = None
         if randomization is not None:
             self.randomization = PolicyRandomization.of(randomization)
             dr = self.randomization.params(seed)      # (checked before anything is built)
+        teach = None
+        if tsid is None:
+            if walk is not None or teacher_weights:
+                raise _lib.TsidbError("PolicyEnv: walk and teacher_weights need tsid = 'stand' or 'walk'")
+        else:
+            if not getattr(conf, "closed_loop", False):
+                raise _lib.TsidbError("PolicyEnv: tsid needs a closed-loop conf (conf.closed_loop = True; for walking "
+                                      "walk_planner.op3_closed_loop_walking_conf): the tick must read the sim state the policy moves")
+            if walk is not None and tsid != "walk":
+                raise _lib.TsidbError("PolicyEnv: walk is the schedule's arguments of tsid = 'walk'")
+            teach = self._teacher_params(teacher_weights, sigma_com, sigma_foot)
+            moved = [k for k in ("reset_xy", "reset_yaw", "reset_lift") if dr is not None and dr[getattr(_lib, "POL_DR_" + k.upper())] != 0]
+            if moved:
+                raise _lib.TsidbError(f"PolicyEnv: {', '.join(moved)} cannot be used with tsid: the walking plan and the contact "
+                                      "references start from the base pose the reset captured (joint and velocity noise are fine: "
+                                      "the closed-loop tick reads the sim state)")
         self.wc = wc = WalkController(conf, num_envs=num_envs, device=device)
         self.num_envs, self.device, self.dtype, self.NA = wc.num_envs, wc.device, wc.dtype, wc.NA
         N, NA = wc.num_envs, wc.NA
@@ -193,7 +235,46 @@ class PolicyEnv:
             self._dr_reset = bool(dr[_lib.POL_DR_RESET_JOINT_POS:_lib.POL_DR_RESET_LIFT + 1].any())
             if self._dr_push and wc.xfrc is None:
                 wc.set_xfrc(z(N, wc.NB, 6))
+        if tsid is not None:
+            self.tsid = tsid
+            self.teach_params = teach
+            wc._call("tsidb_policy_teacher_config", teach.ctypes.data_as(vp), _lib.POL_TEACH_NPARAMS)
+            self.teacher_terms, self.teacher_action = z(N, _lib.POL_TEACH_NT), z(N, NA)
+            self.teacher_obs = z(N, _lib.pol_teach_nobs(NA))
+            if tsid == "walk":
+                self._build_schedule(dict(walk or {}))
         self.reset()   # (episode 1 starts)
+
+    @staticmethod
+    def _teacher_params(teacher_weights, sigma_com, sigma_foot):
+        """the float64 vector tsidb_policy_teacher_config takes, checked as the library checks it"""
+        weights = dict(teacher_weights or {})
+        unknown = sorted(set(weights) - set(_lib.POL_TEACH_TERMS))
+        if unknown:
+            raise _lib.TsidbError(f"PolicyEnv: unknown teacher terms {unknown} (known: {_lib.POL_TEACH_TERMS})")
+        p = np.zeros(_lib.POL_TEACH_NPARAMS)
+        p[_lib.POL_TEACH_SIGMA_COM], p[_lib.POL_TEACH_SIGMA_FOOT] = sigma_com, sigma_foot
+        for k, w in weights.items():
+            p[_lib.POL_TEACH_WEIGHTS + _lib.POL_TEACH_TERMS.index(k)] = w
+        if not np.isfinite(p).all():
+            raise _lib.TsidbError("PolicyEnv: non-finite teacher weight or sigma")
+        if not (p[_lib.POL_TEACH_SIGMA_COM] > 0 and p[_lib.POL_TEACH_SIGMA_FOOT] > 0):
+            raise _lib.TsidbError(f"PolicyEnv: sigma_com and sigma_foot must be positive, got {sigma_com}, {sigma_foot}")
+        return p
+
+    def _build_schedule(self, walk):
+        """tsid = "walk": the device clock and the schedule"""
+        from .walk_planner import WalkSchedule, op3_walking_posture
+        wc = self.wc
+        fraction = walk.pop("touchdown_feedback", 0.6)
+        bias = walk.pop("posture_bias", op3_walking_posture() if wc.NA == 20 else None)
+        walk.setdefault("foot_press", 0.0)
+        if bias is not None:
+            wc.set_posture_bias(bias)
+        self.clock = torch.zeros(1, dtype=torch.float64, device=wc.device)   # float64 whatever the path's dtype
+        self.sched = WalkSchedule.on_device(wc, plan=False, **walk)
+        if fraction is not None:
+            self.sched.enable_touchdown_feedback(fraction)     # (reset() plans: every env is restarted before the first step)
 
     def written(self):
         """Every tensor a step() writes: what a caller that captures steps in a graph rewinds after its warm-up and keeps
@@ -203,6 +284,11 @@ class PolicyEnv:
                     self.ep_len, self.episode, self.timeout, self._rows)
         if self.wc.xfrc is not None:
             yield self.wc.xfrc
+        if self.tsid is not None:
+            yield from (self.teacher_terms, self.teacher_action, self.teacher_obs)
+        if self.sched is not None:
+            s = self.sched
+            yield from (self.clock, s.td_latch, s.coef, s.rest, s.com, s.side, s.nsteps, s.steps, s.flags, s.episode, s.t_offset)
 
     def _act(self, action):
         self.wc._call("tsidb_policy_act", C.byref(self._bufs), _ptr(action), self.wc._stream())
@@ -224,6 +310,32 @@ class PolicyEnv:
         wc = self.wc
         wc._call("tsidb_policy_reset_noise", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(wc.qvel), wc._stream())
 
+    def _tsid_steps(self):
+        """`decimation` closed-loop env steps: tick on the sim state, then sim - in "walk" each behind its reference update"""
+        wc = self.wc
+        if self.sched is None:
+            wc.step(self.decimation)
+            return
+        dt = wc.conf.dt
+        for _ in range(self.decimation):
+            self.sched.apply(wc, 0.0, t_device=self.clock)
+            wc.step(1)
+            self.clock += dt
+
+    def _replan(self):
+        """the envs reset_done just restarted get a new path, and their plans start at the clock"""
+        self.sched.plan(self.wc, done_only=True, new_paths=True, t_device=self.clock)
+
+    def _teacher(self):
+        wc = self.wc
+        wc._call("tsidb_policy_teacher", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.q), _ptr(wc.tau), _ptr(wc.status),
+                 _ptr(wc.ncon), _ptr(wc.con_pairs), _ptr(self.teacher_terms), _ptr(self.teacher_action), wc._stream())
+
+    def _teacher_obs(self):
+        wc = self.wc
+        wc._call("tsidb_policy_teacher_obs", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(wc.tau),
+                 _ptr(self.teacher_obs), self.teacher_obs.shape[1], wc._stream())
+
     def reset(self, env_ids=None):
         """Restart the envs env_ids (None = all) as a done flag would: standing state, zeroed action history and air times, ctrl
         at the default pose (position mode), episode + 1, a new command where a range is set.  reward and done are cleared.
@@ -237,9 +349,15 @@ class PolicyEnv:
             ids = torch.as_tensor(env_ids, device=wc.device).long().reshape(-1)
             wc.done[ids] = 1
         wc.reset_done()
+        if self.sched is not None:
+            if env_ids is None:
+                self.clock.zero_()
+            self._replan()
         if self._dr_reset:
             self._reset_noise()
         self._obs()
+        if self.tsid is not None:
+            self._teacher_obs()
         wc.done.zero_()
         self.timeout.zero_()
         return self.obs
@@ -250,7 +368,8 @@ class PolicyEnv:
         length alone, terms [N, 12]: the unweighted reward terms, episode_length [N] int32: policy steps into the running
         episode, 0 for an env this step restarted).  obs is the FIRST observation of the new episode for a done env; reward,
         done and terms belong to the step that ended the old one.  With pushes on, info["push"] [N, 3] is the torso force the
-        step applied (0 for an env it restarted: the reset clears the wrenches)."""
+        step applied (0 for an env it restarted: the reset clears the wrenches).  With tsid set, info also holds teacher_terms
+        [N, 4] (unweighted; already in reward with teacher_weights), teacher_action [N, NA] and teacher_obs [N, 14 + NA]."""
         wc = self.wc
         if action is None:
             raise _lib.TsidbError("PolicyEnv.step: action is None")
@@ -258,13 +377,23 @@ class PolicyEnv:
         self._act(action)
         if self._dr_push:
             self._perturb()
-        wc.sim_steps(self.decimation)
-        self._reward()
+        if self.tsid is None:
+            wc.sim_steps(self.decimation)
+            self._reward()
+        else:
+            self._tsid_steps()
+            self._reward()
+            self._teacher()
         wc.reset_done()
+        if self.sched is not None:
+            self._replan()
         if self._dr_reset:
             self._reset_noise()
         self._obs()
         info = dict(timeout=self.timeout, terms=self.terms, episode_length=self.ep_len)
+        if self.tsid is not None:
+            self._teacher_obs()
+            info.update(teacher_terms=self.teacher_terms, teacher_action=self.teacher_action, teacher_obs=self.teacher_obs)
         if self._dr_push:
             info["push"] = wc.xfrc[:, 0, :3]
         return self.obs, self.reward, self.done, info
