@@ -498,6 +498,73 @@ int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
  * 9 .. 9 + NA - 1 += noise_joint_pos, 9 + NA .. 9 + 2 NA - 1 += noise_joint_vel draws (stream 7, column = the observation column);
  * command, last action, contact flags and the privileged tail stay exact, and qpos / qvel are not touched. */
 
+/* ---- per-episode terrain and dynamics of the policy environment, and the height scan a policy sees the ground through.  The
+ * sim reads its per-env mass scale, friction, floor plane and stepped terrain from the two tables registered with
+ * tsidb_set_env_params (env_params [N,8], terrain [N,20]); tsidb_policy_terrain_reset rewrites the rows of the envs a step
+ * restarted, on the device, and tsidb_policy_height_scan samples the surface the sim collides against around the base.  No
+ * kernel of the sim or the tick changes.  Draws are those of the randomisation above - same hash, same key layout, U in float64,
+ * every value formed in float64 and cast once to the path's type - with a seed and an env_offset of their own
+ * (TSIDB_POL_TER_SEED, _ENV_OFFSET: env index = env_offset + env) and streams that continue the table:
+ *   stream  draw                                               column        counter
+ *   12      mass scale = lo + (hi - lo) U -> env_params[0]     -             the episode about to start (episode + 1 when the kernel runs)
+ *   13      friction, likewise -> env_params[1]                -             same
+ *   14      tilt t = tilt_max U                                -             same
+ *   15      tilt azimuth a = 2 pi U                            -             same
+ *   16      strip direction g = 2 pi U                         -             same
+ *   17      strip length L = lo + (hi - lo) U                  -             same
+ *   18      strip c is raised iff U < step_prob                c = 0 .. 15   same
+ *   19      step height H = (lo + (hi - lo) U) (lvl + 1) / num_levels   -    same
+ *   20      height scan noise                                  point & 255   episode * 2^32 + ep_len (as stream 7)
+ * What a restart writes, with (x_b, y_b) = qpos[0:2] of the restarted env as the reset and its noise left it:
+ *   env_params = (mass scale, friction, n_x, n_y, n_z, d, 0, 0), n = (sin t cos a, sin t sin a, cos t), d = n_x x_b + n_y y_b
+ *                (the plane passes through the point under the robot);
+ *   terrain    = (cos g, sin g, phase, 1 / L, heights[16]), phase = (cos g) x_b + (sin g) y_b - L / 2 (cell 0 is centred under
+ *                the robot), heights[c] = H where strip c is raised, else 0, and 0 for c <= flat_cells and c >= 16 - flat_cells
+ *                (the start strip and flat_cells strips on each side of it; flat_cells = 0 keeps only cell 0 level).
+ * lvl = level[e] clamped to 0 .. num_levels - 1, or num_levels - 1 where level is NULL: the hook of a terrain curriculum, the
+ * caller's to write.  A degenerate range (lo == hi) writes that value. */
+enum { TSIDB_POL_TER_SEED = 0, TSIDB_POL_TER_ENV_OFFSET, TSIDB_POL_TER_MASS_LO, TSIDB_POL_TER_MASS_HI,
+       TSIDB_POL_TER_FRICTION_LO, TSIDB_POL_TER_FRICTION_HI, TSIDB_POL_TER_TILT_MAX /* rad, < pi/4 */,
+       TSIDB_POL_TER_STEP_HEIGHT_LO, TSIDB_POL_TER_STEP_HEIGHT_HI /* m, >= 0 */,
+       TSIDB_POL_TER_STEP_LENGTH_LO, TSIDB_POL_TER_STEP_LENGTH_HI /* m, > 0 */,
+       TSIDB_POL_TER_STEP_PROB /* [0, 1] */, TSIDB_POL_TER_FLAT_CELLS /* integer 0 .. 7 */,
+       TSIDB_POL_TER_NUM_LEVELS /* integer >= 1 */,
+       TSIDB_POL_TER_SCAN_NX, TSIDB_POL_TER_SCAN_NY /* integers >= 0, nx * ny <= TSIDB_POL_MAXSCAN */,
+       TSIDB_POL_TER_SCAN_X0, TSIDB_POL_TER_SCAN_X1, TSIDB_POL_TER_SCAN_Y0, TSIDB_POL_TER_SCAN_Y1,
+       TSIDB_POL_TER_SCAN_CLIP_LO, TSIDB_POL_TER_SCAN_CLIP_HI, TSIDB_POL_TER_SCAN_NOISE, TSIDB_POL_TER_NPARAMS };
+enum { TSIDB_POL_MAXSCAN = 256 };
+
+/* Copies ter_params [TSIDB_POL_TER_NPARAMS] (host, float64) into the handle; NULL with n_params 0 switches everything off again
+ * (the state of a new handle: tsidb_policy_terrain_reset fails, tsidb_policy_height_scan launches nothing).  First waits for the
+ * kernels in flight, as tsidb_policy_config does.  Rejects a wrong n_params, non-finite values, any lo > hi, a mass or friction
+ * lo <= 0, a tilt outside [0, pi/4), a negative height, a step length lo <= 0, a probability outside [0, 1], a non-integer where
+ * an integer is named (seed, env_offset, flat_cells, num_levels, nx, ny) or one outside its range, a seed >= 2^32, an offset
+ * >= 2^31, num_levels >= 2^31, nx * ny > TSIDB_POL_MAXSCAN, exactly one of nx, ny equal to 0, a negative scan_noise and
+ * clip_lo > clip_hi; nothing of a rejected vector is taken. */
+int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_params);
+
+/* after tsidb_reset_done(done_rows, ...) and tsidb_policy_reset_noise, before tsidb_policy_obs.  For every env whose done flag is
+ * set (column TSIDB_NOBS + 1 of done_rows [N, rows_ld >= TSIDB_NROW]) rewrites the env's row of BOTH tables registered with
+ * tsidb_set_env_params as described above, from qpos [N, NQ] and level [N] (int32, device; may be NULL); the rows of the other
+ * envs stay bit for bit.  A plain asynchronous launch that can be captured.  Fails (message via tsidb_last_error) while either
+ * table is unregistered, before tsidb_policy_terrain_config and in a library built without the sim stage. */
+int tsidb_policy_terrain_reset(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld,
+                               const void *qpos, const int32_t *level, void *stream);
+
+/* after tsidb_policy_obs.  Writes scan [N, scan_ld >= nx * ny] (the path's type; columns from nx * ny on are not touched): the
+ * height of the base above the floor surface at nx * ny points of a grid that turns with the base's heading.  Point
+ * p = ix * ny + iy has the offset (px, py) in the heading frame, px = x0 + (x1 - x0) ix / (nx - 1) (x0 when nx = 1), py likewise
+ * from y0, y1, iy, ny, both formed in float64 and cast.  Heading h = (1 - 2 (q_y^2 + q_z^2), 2 (q_w q_z + q_x q_y)) of the base
+ * quaternion qpos[3:7] (wxyz) divided by its norm, (1, 0) where |h|^2 < 1e-12: the world x, y of the base's x axis, the same
+ * under any roll and pitch; no trigonometric call.  World point (X, Y) = (x_b, y_b) + (h_x px - h_y py, h_y px + h_x py), surface
+ * height z_s = (d + heights[cell(X, Y) & 15] - n_x X - n_y Y) / n_z with cell = floor((direction . (X, Y) - phase) / L) of
+ * tsidb_set_env_params: the surface the sim collides against (distance of x = n . x - d - heights).  The value is
+ * qpos[2] - z_s clipped to [clip_lo, clip_hi] (NaN passes), then + scan_noise (2 U - 1) of stream 20 where scan_noise != 0.  An
+ * unregistered table is the nominal one (n = +z, d = 0; flat), so the scan needs no randomisation.  A plain asynchronous launch
+ * that can be captured; launches nothing and succeeds while nx * ny = 0. */
+int tsidb_policy_height_scan(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, void *scan, int scan_ld,
+                             void *stream);
+
 /* ---- TSID in the loop of the policy environment: the policy steps the closed-loop tsidb_step (params[CLOSED_LOOP]; tick on the
  * sim state, then sim) in place of tsidb_sim_ctrl, and two more launches score it against the controller and show it the
  * controller's references.  One policy step is then tsidb_policy_act, decimation closed-loop env steps (tsidb_walk_update +

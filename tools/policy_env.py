@@ -17,7 +17,12 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               default mode residual) against the hand-driven closed loop over the same number of sim steps (wc.step, in "walk" behind
               sched.apply on a device clock), against the same env with the two teacher launches left out, and against the bare
               tsid=None env, in alternating windows, at 4096 and 512 envs, decimation 4; default profiles/policy_tsid.json (the file
-              keeps one entry per (tsid, mode): a run replaces its own and leaves the others)"""
+              keeps one entry per (tsid, mode): a run replaces its own and leaves the others)
+    python tools/policy_env.py --terrain [out.json]   per-episode terrain and dynamics and the height scan (PolicyEnv(terrain=...): a
+              4 % mass range, friction 0.4 - 1, 5 degrees of tilt, steps of 0 - 1 cm, an 11 x 7 scan) against the env without them on
+              tables drawn once on the host (wc.randomize(): the same sim path, no per-episode redraw, no scan), in alternating
+              windows, at 4096 and 512 envs, decimation 4 and 10; default profiles/policy_terrain.json.  The two kernels' times come
+              from a run of their own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --terrain --trace ENVS STEPS"""
 import json
 import sys
 import time
@@ -194,6 +199,43 @@ def measure_randomize(n, decimation, window=300, windows=4, preroll=60):
                 standing_height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
 
 
+TERRAIN = dict(seed=1, mass=(0.98, 1.02), friction=(0.4, 1.0), tilt_deg=5.0, step_height=(0.0, 0.01), step_length=(0.04, 0.12), step_prob=0.5,
+               flat_cells=1, num_levels=1, scan_x=(-0.5, 0.5, 11), scan_y=(-0.3, 0.3, 7), scan_clip=(-0.2, 0.6), scan_noise=0.01)
+
+
+def measure_terrain(n, decimation, window=300, windows=4, preroll=60):
+    """host: tables drawn once with wc.randomize() (what the library offered before); device: PolicyEnv(terrain=TERRAIN).
+    Policy-steps/s in alternating windows of one process"""
+    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    envs = dict(host=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW),
+                device=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, terrain=TERRAIN, **KW))
+    envs["host"].wc.randomize(seed=1, mass=TERRAIN["mass"], friction=TERRAIN["friction"], tilt_deg=TERRAIN["tilt_deg"],
+                              step_height=TERRAIN["step_height"][1], step_length=TERRAIN["step_length"])
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, envs["device"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    for env in envs.values():
+        for i in range(preroll):
+            env.step(actions[i & 15])
+    torch.cuda.synchronize()
+    res = {k: [] for k in envs}
+    for w in range(windows):
+        for mode in (("host", "device"), ("device", "host"))[w & 1]:
+            env = envs[mode]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(window):
+                env.step(actions[i & 15])
+            torch.cuda.synchronize()
+            res[mode].append(window / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    us = {k: 1e6 / v for k, v in med.items()}
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
+                us_per_policy_step=us, device_over_host=med["device"] / med["host"], terrain_us_per_policy_step=us["device"] - us["host"],
+                restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
+                height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()},
+                scan_min_max=[float(envs["device"].height_scan.min()), float(envs["device"].height_scan.max())])
+
+
 TEACH = dict(track_com=1.0, track_feet=1.0, contact_match=0.25, deviation=-0.01)
 
 
@@ -276,6 +318,23 @@ if __name__ == "__main__":
             with open(out_path) as f:
                 out["runs"] = json.load(f).get("runs", {})
         out["runs"][f"{tsid}/{mode}"] = [measure_tsid(n, tsid, mode) for n in (4096, 512)]
+        text = json.dumps(out, indent=1)
+        print(text)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--terrain":
+        if len(sys.argv) > 2 and sys.argv[2] == "--trace":
+            n, k = int(sys.argv[3]), int(sys.argv[4])
+            env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=4, terrain=TERRAIN, **KW)
+            a = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
+            for _ in range(k):
+                env.step(a)
+            torch.cuda.synchronize()
+            sys.exit(0)
+        out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_terrain.json"
+        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", terrain=TERRAIN,
+                   runs=[measure_terrain(n, d) for n in (4096, 512) for d in (4, 10)])
         text = json.dumps(out, indent=1)
         print(text)
         with open(out_path, "w") as f:

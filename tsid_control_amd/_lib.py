@@ -15,7 +15,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_set_xfrc", "tsidb_set_sim_readouts", "tsidb_set_sensors", "tsidb_set_ctrl", "tsidb_sim_ctrl",
            "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs",
            "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise",
-           "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs"]
+           "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs",
+           "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -41,6 +42,20 @@ POL_DR_SEED, POL_DR_ENV_OFFSET, POL_DR_RESET_JOINT_POS, POL_DR_RESET_JOINT_VEL, 
     POL_DR_RESET_YAW, POL_DR_RESET_XY, POL_DR_RESET_LIFT, POL_DR_NOISE_ANG_VEL, POL_DR_NOISE_GRAVITY, POL_DR_NOISE_JOINT_POS, \
     POL_DR_NOISE_JOINT_VEL, POL_DR_PUSH_INTERVAL, POL_DR_PUSH_DURATION, POL_DR_PUSH_FORCE_LO, POL_DR_PUSH_FORCE_HI, \
     POL_DR_COMMAND_INTERVAL, POL_DR_COMMAND_ZERO_PROB, POL_DR_NPARAMS = 0, 1, 2, 3, 4, 7, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23
+
+# tsidb_policy_terrain_config's parameter vector (include/tsidb.h TSIDB_POL_TER_*), in its order, and the most points of a
+# height scan (TSIDB_POL_MAXSCAN)
+POL_TER_NAMES = ("seed", "env_offset", "mass_lo", "mass_hi", "friction_lo", "friction_hi", "tilt_max", "step_height_lo", "step_height_hi",
+                 "step_length_lo", "step_length_hi", "step_prob", "flat_cells", "num_levels", "scan_nx", "scan_ny", "scan_x0", "scan_x1",
+                 "scan_y0", "scan_y1", "scan_clip_lo", "scan_clip_hi", "scan_noise")
+POL_TER_SEED, POL_TER_ENV_OFFSET, POL_TER_MASS_LO, POL_TER_MASS_HI, POL_TER_FRICTION_LO, POL_TER_FRICTION_HI, POL_TER_TILT_MAX, \
+    POL_TER_STEP_HEIGHT_LO, POL_TER_STEP_HEIGHT_HI, POL_TER_STEP_LENGTH_LO, POL_TER_STEP_LENGTH_HI, POL_TER_STEP_PROB, POL_TER_FLAT_CELLS, \
+    POL_TER_NUM_LEVELS, POL_TER_SCAN_NX, POL_TER_SCAN_NY, POL_TER_SCAN_X0, POL_TER_SCAN_X1, POL_TER_SCAN_Y0, POL_TER_SCAN_Y1, \
+    POL_TER_SCAN_CLIP_LO, POL_TER_SCAN_CLIP_HI, POL_TER_SCAN_NOISE, POL_TER_NPARAMS = range(24)
+POL_MAXSCAN = 256
+# PolicyTerrain's fields (policy_env.py): ranges are (lo, hi) pairs, the scan axes (first, last, points)
+POL_TER_FIELDS = ("seed", "env_offset", "mass", "friction", "tilt_deg", "step_height", "step_length", "step_prob", "flat_cells", "num_levels",
+                  "scan_x", "scan_y", "scan_clip", "scan_noise")
 
 # TSID in the loop of the policy environment (include/tsidb.h TSIDB_POL_TEACH_*): the teacher terms in the order of the
 # teacher_terms row and of the weights, and the layout of tsidb_policy_teacher_config's parameter vector
@@ -149,6 +164,9 @@ def load(path=None):
     L.tsidb_policy_teacher_config.argtypes = [vp, vp, C.c_int]
     L.tsidb_policy_teacher.argtypes = [vp, vp, vp, C.c_int, vp, vp, i32p, i32p, i32p, vp, vp, vp]
     L.tsidb_policy_teacher_obs.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.tsidb_policy_terrain_config.argtypes = [vp, vp, C.c_int]
+    L.tsidb_policy_terrain_reset.argtypes = [vp, vp, vp, C.c_int, vp, i32p, vp]
+    L.tsidb_policy_height_scan.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

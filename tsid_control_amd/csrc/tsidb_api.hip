@@ -678,6 +678,7 @@ static_assert((int)CTRL_POSITION == TSIDB_CTRL_POSITION && (int)CTRL_MOTOR == TS
               "include/tsidb.h and the kernels agree on the ctrl modes");
 static_assert(POL_NT == TSIDB_POL_NT && POL_HIST == TSIDB_POL_HIST && POL_NPRIV == TSIDB_POL_NPRIV && (NA != 20 || POL_NOBS == TSIDB_POL_NOBS),
               "include/tsidb.h and the kernels agree on the policy environment's rows");
+static_assert(POL_MAXSCAN == TSIDB_POL_MAXSCAN, "include/tsidb.h and the kernels agree on the height scan's size");
 static_assert(POL_TEACH_NT == TSIDB_POL_TEACH_NT && (NA != 20 || POL_TEACH_NOBS == TSIDB_POL_TEACH_NOBS),
               "include/tsidb.h and the kernels agree on the teacher's rows");
 
@@ -723,6 +724,8 @@ struct tsidb_ctx {
   double pol[TSIDB_POL_NPARAMS] = {}, pol_scale[NA] = {}, pol_def[NA] = {};
   unsigned pol_mask = 0;
   double pol_dr[TSIDB_POL_DR_NPARAMS] = {}; // tsidb_policy_randomize's vector; all 0 = every group off
+  bool ter_set = false;                      // tsidb_policy_terrain_config: per-episode terrain and dynamics, the height scan
+  double pol_ter[TSIDB_POL_TER_NPARAMS] = {};
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
   std::string err;
@@ -1214,6 +1217,20 @@ static bool dr_obs_on(const tsidb_ctx *h) {
          h->pol_dr[TSIDB_POL_DR_ENV_OFFSET] != 0;
 }
 
+static PolicyTer policy_ter(const tsidb_ctx *h) {
+  const double *p = h->pol_ter;
+  PolicyTer d;
+  d.seed = (unsigned long long)p[TSIDB_POL_TER_SEED]; d.env_offset = (unsigned long long)p[TSIDB_POL_TER_ENV_OFFSET];
+  d.mass_lo = p[TSIDB_POL_TER_MASS_LO]; d.mass_hi = p[TSIDB_POL_TER_MASS_HI]; d.fric_lo = p[TSIDB_POL_TER_FRICTION_LO]; d.fric_hi = p[TSIDB_POL_TER_FRICTION_HI];
+  d.tilt_max = p[TSIDB_POL_TER_TILT_MAX]; d.height_lo = p[TSIDB_POL_TER_STEP_HEIGHT_LO]; d.height_hi = p[TSIDB_POL_TER_STEP_HEIGHT_HI];
+  d.length_lo = p[TSIDB_POL_TER_STEP_LENGTH_LO]; d.length_hi = p[TSIDB_POL_TER_STEP_LENGTH_HI]; d.step_prob = p[TSIDB_POL_TER_STEP_PROB];
+  d.flat_cells = (int)p[TSIDB_POL_TER_FLAT_CELLS]; d.num_levels = (int)p[TSIDB_POL_TER_NUM_LEVELS];
+  d.nx = (int)p[TSIDB_POL_TER_SCAN_NX]; d.ny = (int)p[TSIDB_POL_TER_SCAN_NY];
+  d.x0 = p[TSIDB_POL_TER_SCAN_X0]; d.x1 = p[TSIDB_POL_TER_SCAN_X1]; d.y0 = p[TSIDB_POL_TER_SCAN_Y0]; d.y1 = p[TSIDB_POL_TER_SCAN_Y1];
+  d.clip_lo = p[TSIDB_POL_TER_SCAN_CLIP_LO]; d.clip_hi = p[TSIDB_POL_TER_SCAN_CLIP_HI]; d.noise = p[TSIDB_POL_TER_SCAN_NOISE];
+  return d;
+}
+
 // what both teacher launches need on top of policy_bufs: the teacher's configuration and the registered references
 template <typename T>
 static PolicyRefs<T> policy_teacher_refs(const tsidb_ctx *h, const char *who) {
@@ -1354,6 +1371,85 @@ int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
     h->note_stream(s);
     hipLaunchKernelGGL(k_policy_reset_noise<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, b,
                        policy_dr(h), (const T *)done_rows, rows_ld, (T *)qpos, (T *)qvel);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_params) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_terrain_config: ";
+  if (lacks_sim(h, true, who)) throw h->err;
+  double p[TSIDB_POL_TER_NPARAMS] = {};
+  const bool on = ter_params || n_params;
+  if (on) {
+    if (!ter_params || n_params != TSIDB_POL_TER_NPARAMS) throw std::string(who) + "needs TSIDB_POL_TER_NPARAMS parameters (or NULL, 0: everything off)";
+    for (int i = 0; i < n_params; i++) {
+      if (!std::isfinite(ter_params[i])) throw std::string(who) + "non-finite parameter";
+      p[i] = ter_params[i];
+    }
+    for (int i : {(int)TSIDB_POL_TER_SEED, (int)TSIDB_POL_TER_ENV_OFFSET, (int)TSIDB_POL_TER_FLAT_CELLS, (int)TSIDB_POL_TER_NUM_LEVELS, (int)TSIDB_POL_TER_SCAN_NX,
+                  (int)TSIDB_POL_TER_SCAN_NY})
+      if (p[i] != std::floor(p[i]) || p[i] < 0) throw std::string(who) + "seed, env_offset, flat_cells, num_levels, scan_nx and scan_ny must be whole numbers >= 0";
+    if (p[TSIDB_POL_TER_SEED] >= 4294967296.0) throw std::string(who) + "seed must be below 2^32";
+    if (p[TSIDB_POL_TER_ENV_OFFSET] >= 2147483648.0) throw std::string(who) + "env_offset must be below 2^31";
+    for (int i : {(int)TSIDB_POL_TER_MASS_LO, (int)TSIDB_POL_TER_FRICTION_LO, (int)TSIDB_POL_TER_STEP_HEIGHT_LO, (int)TSIDB_POL_TER_STEP_LENGTH_LO})
+      if (p[i] > p[i + 1]) throw std::string(who) + "range: lo > hi (mass, friction, step_height, step_length)";
+    if (!(p[TSIDB_POL_TER_MASS_LO] > 0) || !(p[TSIDB_POL_TER_FRICTION_LO] > 0)) throw std::string(who) + "mass and friction must be positive";
+    if (p[TSIDB_POL_TER_TILT_MAX] < 0 || !(p[TSIDB_POL_TER_TILT_MAX] < 0.7853981633974483)) throw std::string(who) + "tilt_max must be in [0, pi/4)";
+    if (p[TSIDB_POL_TER_STEP_HEIGHT_LO] < 0) throw std::string(who) + "step heights must be >= 0";
+    if (!(p[TSIDB_POL_TER_STEP_LENGTH_LO] > 0)) throw std::string(who) + "step lengths must be positive";
+    if (p[TSIDB_POL_TER_STEP_PROB] < 0 || p[TSIDB_POL_TER_STEP_PROB] > 1) throw std::string(who) + "step_prob must be in [0, 1]";
+    if (p[TSIDB_POL_TER_FLAT_CELLS] > 7) throw std::string(who) + "flat_cells must be 0 .. 7";
+    if (p[TSIDB_POL_TER_NUM_LEVELS] < 1 || p[TSIDB_POL_TER_NUM_LEVELS] >= 2147483648.0) throw std::string(who) + "num_levels must be 1 .. 2^31 - 1";
+    const double nx = p[TSIDB_POL_TER_SCAN_NX], ny = p[TSIDB_POL_TER_SCAN_NY];
+    if (nx > TSIDB_POL_MAXSCAN || ny > TSIDB_POL_MAXSCAN || nx * ny > TSIDB_POL_MAXSCAN) throw std::string(who) + "scan_nx * scan_ny must be at most TSIDB_POL_MAXSCAN";
+    if ((nx == 0) != (ny == 0)) throw std::string(who) + "scan_nx and scan_ny must both be 0 (no scan) or both positive";
+    if (p[TSIDB_POL_TER_SCAN_CLIP_LO] > p[TSIDB_POL_TER_SCAN_CLIP_HI]) throw std::string(who) + "scan clip_lo > clip_hi";
+    if (p[TSIDB_POL_TER_SCAN_NOISE] < 0) throw std::string(who) + "scan_noise must be >= 0";
+  }
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->pol_ter, p, sizeof h->pol_ter);
+  h->ter_set = on;
+  GUARD_END
+}
+
+int tsidb_policy_terrain_reset(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
+                               const int32_t *level, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const char *who = "tsidb_policy_terrain_reset: ";
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
+    if (!h->ter_set) throw std::string(who) + "not configured (call tsidb_policy_terrain_config first)";
+    if (!h->env_params || !h->terrain) throw std::string(who) + "needs both the env_params and the terrain table registered (call tsidb_set_env_params first)";
+    if (!done_rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)";
+    if (!qpos) throw std::string(who) + "null buffer";
+    h->note_stream(s);
+    // (the tables are the caller's device buffers, registered read-only for the sim: this launch is their one writer)
+    hipLaunchKernelGGL(k_policy_terrain_reset<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, policy_ter(h),
+                       (const T *)done_rows, rows_ld, (const T *)qpos, level, (T *)const_cast<void *>(h->env_params),
+                       (T *)const_cast<void *>(h->terrain));
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_height_scan(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, void *scan, int scan_ld, void *stream) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    const char *who = "tsidb_policy_height_scan: ";
+    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
+    const PolicyTer d = policy_ter(h);
+    if (d.nx * d.ny == 0) return;   // (also before tsidb_policy_terrain_config)
+    if (!qpos || !scan) throw std::string(who) + "null buffer";
+    if (scan_ld < d.nx * d.ny) throw std::string(who) + "scan row stride must be at least scan_nx * scan_ny";
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_height_scan<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, d, (const T *)qpos,
+                       (const T *)h->env_params, (const T *)h->terrain, (T *)scan, scan_ld);
   });
   HIP_OK(hipGetLastError());
   GUARD_END

@@ -2,8 +2,9 @@
 // before the sim steps, reward / termination after them, bookkeeping of the restarted envs and the observation row after the
 // reset; with a randomisation configured (tsidb_policy_randomize) also the push of the step before the sim steps, noise on the
 // state of the envs just reset, command resampling and observation noise - every draw a hash of (seed, stream, column, env,
-// episode, ep_len), no random state anywhere.  No reference counterpart: the reference runs one TSID-driven episode
-// (main.py:113-124).
+// episode, ep_len), no random state anywhere; with a terrain configured (tsidb_policy_terrain_config) the sim's per-env mass
+// scale, friction, floor plane and stepped terrain are redrawn for the envs just reset, and a height scan of that floor is
+// written beside the observation.  No reference counterpart: the reference runs one TSID-driven episode (main.py:113-124).
 //
 // Shape of all the kernels, as k_reset: one wavefront per env, lane = column of the env's rows (coalesced row loads and
 // stores), wave reductions (DPP) for the sums over actuators and wave votes for the flags over contacts; four envs per
@@ -63,8 +64,11 @@ __device__ __forceinline__ double pol_uniform(unsigned long long key, unsigned l
   return (double)(plan_hash(key, env, counter) >> 11) * (1.0 / 9007199254740992.0);
 }
 // the draw of (stream, column): key = seed + ((stream * 256 + column) << 32)
+__device__ __forceinline__ double pol_draw(unsigned long long seed, int stream, int column, unsigned long long env, unsigned long long counter) {
+  return pol_uniform(seed + ((unsigned long long)(stream * 256 + column) << 32), env, counter);
+}
 __device__ __forceinline__ double pol_draw(const PolicyDR &d, int stream, int column, unsigned long long env, unsigned long long counter) {
-  return pol_uniform(d.seed + ((unsigned long long)(stream * 256 + column) << 32), env, counter);
+  return pol_draw(d.seed, stream, column, env, counter);
 }
 // amp (2 U - 1) in float64, cast
 template <typename T>
@@ -333,6 +337,89 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_reset_nois
     else if (d.reset_lift != 0) qp[2] += (T)d.reset_lift;
   }
   if (d.reset_yaw != 0 && lane >= 3 && lane < 7) qp[lane] = lane == 3 ? w : lane == 4 ? x : lane == 5 ? y : z;
+}
+
+// ---------------------------------------------------------------------------- per-episode terrain and dynamics, height scan
+// tsidb_policy_terrain_config's values, passed to the kernels by value.  float64 whatever the path's type, as PolicyDR
+struct PolicyTer {
+  unsigned long long seed, env_offset;
+  double mass_lo, mass_hi, fric_lo, fric_hi, tilt_max, height_lo, height_hi, length_lo, length_hi, step_prob;
+  int flat_cells, num_levels, nx, ny;
+  double x0, x1, y0, y1, clip_lo, clip_hi, noise;
+};
+enum { TER_S_MASS = 12, TER_S_FRICTION, TER_S_TILT, TER_S_AZIMUTH, TER_S_DIRECTION, TER_S_LENGTH, TER_S_RAISED, TER_S_HEIGHT, TER_S_SCAN };
+constexpr int POL_MAXSCAN = 256;   // TSIDB_POL_MAXSCAN
+
+// after the reset and its noise, before k_policy_obs: the rows of the two sim tables (tsidb_set_env_params) of the envs just
+// reset.  lane = column of the row: lanes 0 .. 7 store env_params[e], lanes 0 .. 19 terrain[e].  The seven draws every column
+// needs one or two of are formed on every lane (a hash each) - no cross-lane traffic; everything in float64, cast when stored
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_terrain_reset(int n, PolicyBufs<T> b, PolicyTer d, const T *__restrict__ done_rows,
+                                                                                    int rows_ld, const T *__restrict__ qpos,
+                                                                                    const int *__restrict__ level, T *env_params, T *terrain) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= 20) return;
+  const size_t E = (size_t)e;
+  if (done_rows[E * rows_ld + NROW - 1] == T(0)) return;
+  const unsigned long long ge = d.env_offset + (unsigned long long)e, ep = (unsigned long long)(b.episode[E] + 1);   // (the episode about to start)
+  const double xb = (double)qpos[E * NQ], yb = (double)qpos[E * NQ + 1];
+  int lvl = level ? level[E] : d.num_levels - 1;
+  lvl = lvl < 0 ? 0 : lvl > d.num_levels - 1 ? d.num_levels - 1 : lvl;
+  const double two_pi = 6.283185307179586;
+  const double mass = d.mass_lo + (d.mass_hi - d.mass_lo) * pol_draw(d.seed, TER_S_MASS, 0, ge, ep);
+  const double fric = d.fric_lo + (d.fric_hi - d.fric_lo) * pol_draw(d.seed, TER_S_FRICTION, 0, ge, ep);
+  const double t = d.tilt_max * pol_draw(d.seed, TER_S_TILT, 0, ge, ep), a = two_pi * pol_draw(d.seed, TER_S_AZIMUTH, 0, ge, ep);
+  const double g = two_pi * pol_draw(d.seed, TER_S_DIRECTION, 0, ge, ep);
+  const double len = d.length_lo + (d.length_hi - d.length_lo) * pol_draw(d.seed, TER_S_LENGTH, 0, ge, ep);
+  const double H = (d.height_lo + (d.height_hi - d.height_lo) * pol_draw(d.seed, TER_S_HEIGHT, 0, ge, ep)) * (double)(lvl + 1) / (double)d.num_levels;
+  const double st = sin(t), nx = st * cos(a), ny = st * sin(a), nz = cos(t), cg = cos(g), sg = sin(g);
+  if (lane < 8) {
+    const double v = lane == 0 ? mass : lane == 1 ? fric : lane == 2 ? nx : lane == 3 ? ny : lane == 4 ? nz : lane == 5 ? nx * xb + ny * yb : 0.0;
+    env_params[E * 8 + lane] = (T)v;
+  }
+  double v;
+  if (lane < 4) v = lane == 0 ? cg : lane == 1 ? sg : lane == 2 ? cg * xb + sg * yb - 0.5 * len : 1.0 / len;
+  else {
+    const int c = lane - 4;
+    const bool raised = pol_draw(d.seed, TER_S_RAISED, c, ge, ep) < d.step_prob;
+    v = raised && c > d.flat_cells && c < 16 - d.flat_cells ? H : 0.0;
+  }
+  terrain[E * 20 + lane] = (T)v;
+}
+
+// after k_policy_obs: the height of the base above the floor surface at the nx * ny points of a grid in the heading frame.
+// lane = point (points 64 apart share a lane: a row store is coalesced); the env's rows of the two tables sit behind
+// wave-uniform addresses that nothing in this kernel writes: scalar loads.  envp / terr NULL = the nominal floor
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_height_scan(int n, PolicyBufs<T> b, PolicyTer d, const T *__restrict__ qpos,
+                                                                                  const T *__restrict__ envp_g, const T *__restrict__ terr_g, T *scan,
+                                                                                  int scan_ld) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0) return;
+  const size_t E = (size_t)e;
+  const int np = d.nx * d.ny;
+  const T *qp = qpos + E * NQ, *envp = envp_g ? envp_g + E * 8 : nullptr, *terr = terr_g ? terr_g + E * 20 : nullptr;
+  const T fnx = envp ? envp[2] : T(0), fny = envp ? envp[3] : T(0), fnz = envp ? envp[4] : T(1), fd = envp ? envp[5] : T(0);
+  const T xb = qp[0], yb = qp[1], zb = qp[2], qw = qp[3], qx = qp[4], qy = qp[5], qz = qp[6];
+  T hx = 1 - 2 * (qy * qy + qz * qz), hy = 2 * (qw * qz + qx * qy);
+  const T h2 = hx * hx + hy * hy;
+  if (h2 < T(1e-12)) { hx = 1; hy = 0; }
+  else { const T hn = sqrt(h2); hx /= hn; hy /= hn; }
+  const T lo = (T)d.clip_lo, hi = (T)d.clip_hi;
+  const unsigned long long ge = d.env_offset + (unsigned long long)e;
+  const unsigned long long ctr = ((unsigned long long)b.episode[E] << 32) | (unsigned long long)b.ep_len[E];
+  for (int p = lane; p < np; p += WAVE) {
+    const int ix = p / d.ny, iy = p - ix * d.ny;
+    const T px = (T)(d.nx > 1 ? d.x0 + (d.x1 - d.x0) * (double)ix / (double)(d.nx - 1) : d.x0);
+    const T py = (T)(d.ny > 1 ? d.y0 + (d.y1 - d.y0) * (double)iy / (double)(d.ny - 1) : d.y0);
+    const T X = xb + (hx * px - hy * py), Y = yb + (hy * px + hx * py);
+    const T hs = terr ? terrain_h(terr, X, Y) : T(0);
+    const T zs = (fd + hs - fnx * X - fny * Y) / fnz;
+    T v = zb - zs;
+    v = v < lo ? lo : v > hi ? hi : v;   // (NaN passes)
+    if (d.noise != 0) v += (T)(d.noise * (2.0 * pol_draw(d.seed, TER_S_SCAN, p & 255, ge, ctr) - 1.0));
+    scan[E * scan_ld + p] = v;
+  }
 }
 
 // ---------------------------------------------------------------------------- TSID in the loop: the teacher

@@ -14,6 +14,11 @@ force before the sim steps (tsidb_policy_perturb), noise on the state of the env
 (tsidb_policy_reset_noise) - and the obs launch resamples commands and adds observation noise.  Every draw is a hash of
 (seed, stream, column, env, episode, ep_len): no random state, so a captured step replays and a split batch draws alike.
 
+With a PolicyTerrain two more launches join them: after the reset and its noise the sim's per-env tables - mass scale, contact
+friction, floor plane, stepped terrain (WalkController.set_env_params) - are redrawn on the device for the envs just restarted
+(tsidb_policy_terrain_reset), and after the observation a height scan of that floor around the base is written
+(tsidb_policy_height_scan).  The same hash draws them, on streams of their own.
+
 With tsid = "stand" or "walk" the batched TSID controller is in the loop: the sim stage of a step is `decimation` closed-loop env
 steps (tick on the sim state, then sim; in "walk" each behind the walking reference update on a device clock) and two more
 launches join the step - after the reward the teacher terms, TSID's failed QPs and its command as an action
@@ -109,6 +114,115 @@ class PolicyRandomization:
         return p
 
 
+@dataclasses.dataclass
+class PolicyTerrain:
+    """Per-episode dynamics and terrain of a PolicyEnv and its height scan (include/tsidb.h TSIDB_POL_TER_*).  seed: of these
+    draws (None = the env's seed; below 2^32).  env_offset: added to the env index in every draw (None = the randomization's,
+    else 0).  Ranges are (lo, hi), drawn uniformly at every restart, lo == hi = that value: mass (scale of every sim body's mass
+    and inertia, > 0), friction (floor contacts, > 0), step_height [m] (of the raised strips, scaled by (level + 1) / num_levels
+    with level = PolicyEnv.terrain_level of the env), step_length [m] (width of a strip, > 0).  tilt_deg: the floor is a plane
+    through the point under the restarted robot, tilted by at most this much (< 45) about a random azimuth.  step_prob: each
+    of the 16 strips of the stepped floor, which repeat along a random direction, is raised with this probability; the strip
+    under the restarted robot and flat_cells (0 .. 7) strips on each side of it stay level.  scan_x, scan_y: (first, last,
+    points) of the height scan's grid along the base's heading and to its left [m], None = no scan (both or neither; at most 256
+    points); scan_clip: (lo, hi) the base's height above the surface is clipped to; scan_noise [m]: uniform in +-scan_noise, added
+    after the clip."""
+    seed: int = None
+    env_offset: int = None
+    mass: object = (1.0, 1.0)
+    friction: object = (1.0, 1.0)
+    tilt_deg: float = 0.0
+    step_height: object = (0.0, 0.0)
+    step_length: object = (0.08, 0.08)
+    step_prob: float = 0.5
+    flat_cells: int = 1
+    num_levels: int = 1
+    scan_x: object = None
+    scan_y: object = None
+    scan_clip: object = (-1.0, 1.0)
+    scan_noise: float = 0.0
+
+    @classmethod
+    def of(cls, t):
+        """t as a PolicyTerrain: one, or a dict of its fields"""
+        if isinstance(t, cls):
+            return t
+        if not isinstance(t, dict):
+            raise _lib.TsidbError(f"PolicyEnv: terrain must be a PolicyTerrain or a dict, got {type(t).__name__}")
+        unknown = sorted(set(t) - set(_lib.POL_TER_FIELDS))
+        if unknown:
+            raise _lib.TsidbError(f"PolicyEnv: unknown terrain fields {unknown} (known: {_lib.POL_TER_FIELDS})")
+        return cls(**t)
+
+    def params(self, default_seed=0, default_env_offset=0):
+        """the float64 vector tsidb_policy_terrain_config takes, checked as the library checks it"""
+        bad = lambda msg: _lib.TsidbError("PolicyTerrain: " + msg)
+
+        def numbers(k, count):
+            v = getattr(self, k)
+            try:
+                a = np.asarray(v, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError) as err:
+                raise bad(f"{k} = {v!r} is not {count} numbers") from err
+            if a.shape != (count,):
+                raise bad(f"{k} = {v!r} is not {count} numbers")
+            return a
+
+        p = np.zeros(_lib.POL_TER_NPARAMS)
+        seed = default_seed if self.seed is None else self.seed
+        offset = default_env_offset if self.env_offset is None else self.env_offset
+        scalars = dict(seed=seed, env_offset=offset, tilt_deg=self.tilt_deg, step_prob=self.step_prob, flat_cells=self.flat_cells,
+                       num_levels=self.num_levels, scan_noise=self.scan_noise)
+        for k, v in scalars.items():
+            try:
+                scalars[k] = float(v)
+            except (TypeError, ValueError) as err:
+                raise bad(f"{k} = {v!r} is not a number") from err
+        p[_lib.POL_TER_SEED], p[_lib.POL_TER_ENV_OFFSET] = scalars["seed"], scalars["env_offset"]
+        p[_lib.POL_TER_TILT_MAX] = math.radians(scalars["tilt_deg"])
+        p[_lib.POL_TER_STEP_PROB], p[_lib.POL_TER_SCAN_NOISE] = scalars["step_prob"], scalars["scan_noise"]
+        p[_lib.POL_TER_FLAT_CELLS], p[_lib.POL_TER_NUM_LEVELS] = scalars["flat_cells"], scalars["num_levels"]
+        for k, i in (("mass", _lib.POL_TER_MASS_LO), ("friction", _lib.POL_TER_FRICTION_LO), ("step_height", _lib.POL_TER_STEP_HEIGHT_LO),
+                     ("step_length", _lib.POL_TER_STEP_LENGTH_LO), ("scan_clip", _lib.POL_TER_SCAN_CLIP_LO)):
+            p[i:i + 2] = numbers(k, 2)
+        for k, i, j in (("scan_x", _lib.POL_TER_SCAN_X0, _lib.POL_TER_SCAN_NX), ("scan_y", _lib.POL_TER_SCAN_Y0, _lib.POL_TER_SCAN_NY)):
+            if getattr(self, k) is not None:
+                p[i], p[i + 1], p[j] = numbers(k, 3)
+        if not np.isfinite(p).all():
+            raise bad("non-finite value")
+        for k in ("seed", "env_offset", "flat_cells", "num_levels", "scan_nx", "scan_ny"):
+            v = p[getattr(_lib, "POL_TER_" + k.upper())]
+            if v != math.floor(v) or v < 0:
+                raise bad(f"{k} must be a whole number >= 0, got {v}")
+        if p[_lib.POL_TER_SEED] >= 2.0 ** 32 or p[_lib.POL_TER_ENV_OFFSET] >= 2.0 ** 31:
+            raise bad("seed must be below 2^32 and env_offset below 2^31")
+        for k, i in (("mass", _lib.POL_TER_MASS_LO), ("friction", _lib.POL_TER_FRICTION_LO), ("step_height", _lib.POL_TER_STEP_HEIGHT_LO),
+                     ("step_length", _lib.POL_TER_STEP_LENGTH_LO), ("scan_clip", _lib.POL_TER_SCAN_CLIP_LO)):
+            if p[i] > p[i + 1]:
+                raise bad(f"{k}: lo > hi")
+        for k, i in (("mass", _lib.POL_TER_MASS_LO), ("friction", _lib.POL_TER_FRICTION_LO), ("step_length", _lib.POL_TER_STEP_LENGTH_LO)):
+            if not p[i] > 0:
+                raise bad(f"{k} must be positive")
+        if not 0 <= p[_lib.POL_TER_TILT_MAX] < math.pi / 4:
+            raise bad("tilt_deg must be in [0, 45)")
+        if p[_lib.POL_TER_STEP_HEIGHT_LO] < 0:
+            raise bad("step_height must be >= 0")
+        if not 0 <= p[_lib.POL_TER_STEP_PROB] <= 1:
+            raise bad("step_prob must be in [0, 1]")
+        if p[_lib.POL_TER_FLAT_CELLS] > 7:
+            raise bad("flat_cells must be 0 .. 7")
+        if not 1 <= p[_lib.POL_TER_NUM_LEVELS] < 2.0 ** 31:
+            raise bad("num_levels must be a whole number >= 1 (below 2^31)")
+        nx, ny = p[_lib.POL_TER_SCAN_NX], p[_lib.POL_TER_SCAN_NY]
+        if (nx == 0) != (ny == 0):
+            raise bad("scan_x and scan_y must both be given, with at least one point each, or neither")
+        if nx * ny > _lib.POL_MAXSCAN:
+            raise bad(f"the scan has {int(nx * ny)} points, at most {_lib.POL_MAXSCAN}")
+        if p[_lib.POL_TER_SCAN_NOISE] < 0:
+            raise bad("scan_noise must be >= 0")
+        return p
+
+
 class PolicyEnv:
     """conf: a RobotConfig (used as a copy with reference_quirks = False, sim_enabled = True: a reset then writes a proper wxyz
     qpos).  decimation: sim steps per policy step.  mode: "position" (ctrl = joint targets [rad] = default_joint_pos +
@@ -140,18 +254,28 @@ class PolicyEnv:
     teacher_obs mean something with tsid = "walk").  Reset noise
     that moves the base (reset_xy, reset_yaw, reset_lift) is rejected with tsid: the plan and the contact references start
     where the reset put the robot.  More tensors: teacher_terms [N, 4], teacher_action [N, NA], teacher_obs [N, 14 + NA]
-    (include/tsidb.h tsidb_policy_teacher / _teacher_obs), all three in step()'s info."""
+    (include/tsidb.h tsidb_policy_teacher / _teacher_obs), all three in step()'s info.
+
+    terrain: a PolicyTerrain or a dict of its fields (None = none: the launches and every result are those of an env built
+    without the argument).  The env registers nominal tables once (wc.set_env_params(mass_scale=1, terrain="flat")) and the
+    kernels rewrite wc.env_params [N, 8] and wc.terrain [N, 20] in place, for the envs a step or reset() restarts.  terrain_level
+    [N] int32, zero at first, is the caller's to write: the level of the env's NEXT episodes (the hook of a terrain curriculum;
+    no promotion rule is built in).  height_scan [N, nx * ny]: point ix * ny + iy.  All three are in step()'s info (env_params
+    under that name).  Accepted with tsid = "stand" / "walk", but the controller is NOT told about the floor: its references,
+    contact frames and plan assume the level floor z = 0, so a tilt or steps are a disturbance TSID has to absorb."""
 
     # the randomisation's launches a step makes; class-level so that an instance built without __init__ steps unrandomised
     randomization = None
     _dr_push = _dr_reset = False
+    # per-episode terrain and dynamics, the height scan: class-level for the same reason
+    terrain = terrain_level = height_scan = None
     # TSID in the loop: None = no tick; sched = the walking schedule of tsid = "walk", clock its device time
     tsid = sched = clock = None
 
     def __init__(self, conf=None, num_envs=None, device=None, decimation=10, mode="position", action_scale=0.25,
                  default_joint_pos=None, action_clip=100.0, delay=None, filter_alpha=1.0, command_range=((0.0, 0.0),) * 3,
                  max_episode_steps=0, reward_weights=None, term_bodies=None, sigma=0.25, h_target=None, t_air=0.25, deadband=0.1,
-                 seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05):
+                 seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05, terrain=None):
         from .conf import RobotConfig
         conf = copy.copy(conf) if conf is not None else RobotConfig()
         conf.reference_quirks = False
@@ -165,6 +289,10 @@ class PolicyEnv:
         if randomization is not None:
             self.randomization = PolicyRandomization.of(randomization)
             dr = self.randomization.params(seed)      # (checked before anything is built)
+        ter = None
+        if terrain is not None:
+            self.terrain = PolicyTerrain.of(terrain)
+            ter = self.terrain.params(seed, 0 if dr is None else int(dr[_lib.POL_DR_ENV_OFFSET]))
         teach = None
         if tsid is None:
             if walk is not None or teacher_weights:
@@ -235,6 +363,12 @@ class PolicyEnv:
             self._dr_reset = bool(dr[_lib.POL_DR_RESET_JOINT_POS:_lib.POL_DR_RESET_LIFT + 1].any())
             if self._dr_push and wc.xfrc is None:
                 wc.set_xfrc(z(N, wc.NB, 6))
+        if ter is not None:
+            self.ter_params = ter
+            wc.set_env_params(mass_scale=1.0, terrain="flat")      # nominal rows; the kernels rewrite the two tensors in place
+            wc._call("tsidb_policy_terrain_config", ter.ctypes.data_as(vp), _lib.POL_TER_NPARAMS)
+            self.terrain_level = z(N, dt=torch.int32)
+            self.height_scan = z(N, int(ter[_lib.POL_TER_SCAN_NX] * ter[_lib.POL_TER_SCAN_NY]))
         if tsid is not None:
             self.tsid = tsid
             self.teach_params = teach
@@ -284,6 +418,8 @@ class PolicyEnv:
                     self.ep_len, self.episode, self.timeout, self._rows)
         if self.wc.xfrc is not None:
             yield self.wc.xfrc
+        if self.terrain is not None:
+            yield from (self.wc.env_params, self.wc.terrain, self.height_scan)
         if self.tsid is not None:
             yield from (self.teacher_terms, self.teacher_action, self.teacher_obs)
         if self.sched is not None:
@@ -309,6 +445,16 @@ class PolicyEnv:
     def _reset_noise(self):
         wc = self.wc
         wc._call("tsidb_policy_reset_noise", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(wc.qvel), wc._stream())
+
+    def _terrain_reset(self):
+        wc = self.wc
+        wc._call("tsidb_policy_terrain_reset", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(self.terrain_level),
+                 wc._stream())
+
+    def _height_scan(self):
+        wc = self.wc
+        wc._call("tsidb_policy_height_scan", C.byref(self._bufs), _ptr(wc.qpos), _ptr(self.height_scan), self.height_scan.shape[1],
+                 wc._stream())
 
     def _tsid_steps(self):
         """`decimation` closed-loop env steps: tick on the sim state, then sim - in "walk" each behind its reference update"""
@@ -355,7 +501,11 @@ class PolicyEnv:
             self._replan()
         if self._dr_reset:
             self._reset_noise()
+        if self.terrain is not None:
+            self._terrain_reset()
         self._obs()
+        if self.terrain is not None:
+            self._height_scan()
         if self.tsid is not None:
             self._teacher_obs()
         wc.done.zero_()
@@ -369,7 +519,8 @@ class PolicyEnv:
         episode, 0 for an env this step restarted).  obs is the FIRST observation of the new episode for a done env; reward,
         done and terms belong to the step that ended the old one.  With pushes on, info["push"] [N, 3] is the torso force the
         step applied (0 for an env it restarted: the reset clears the wrenches).  With tsid set, info also holds teacher_terms
-        [N, 4] (unweighted; already in reward with teacher_weights), teacher_action [N, NA] and teacher_obs [N, 14 + NA]."""
+        [N, 4] (unweighted; already in reward with teacher_weights), teacher_action [N, NA] and teacher_obs [N, 14 + NA].  With
+        terrain set, height_scan [N, nx * ny], env_params [N, 8] (the sim's table, as the restarts left it) and terrain_level."""
         wc = self.wc
         if action is None:
             raise _lib.TsidbError("PolicyEnv.step: action is None")
@@ -389,8 +540,13 @@ class PolicyEnv:
             self._replan()
         if self._dr_reset:
             self._reset_noise()
+        if self.terrain is not None:
+            self._terrain_reset()
         self._obs()
         info = dict(timeout=self.timeout, terms=self.terms, episode_length=self.ep_len)
+        if self.terrain is not None:
+            self._height_scan()
+            info.update(height_scan=self.height_scan, env_params=wc.env_params, terrain_level=self.terrain_level)
         if self.tsid is not None:
             self._teacher_obs()
             info.update(teacher_terms=self.teacher_terms, teacher_action=self.teacher_action, teacher_obs=self.teacher_obs)

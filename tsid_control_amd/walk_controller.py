@@ -187,7 +187,8 @@ class WalkController:
         of mass_scale [N], friction [N] (floor contacts), floor_normal [N,3] (normalised here), floor_offset [N],
         terrain = dict(direction [N,2], phase [N], step_length [N] or float, heights [N,16]): a stepped floor -
         the surface is raised along its normal by heights[cell & 15], cell = floor((direction . x_world_xy - phase)
-        / step_length).  Calling with no argument restores the nominal model."""
+        / step_length); terrain = "flat" registers the table of a level floor (zeros, 1 / step_length = 1), for a caller or a
+        kernel (PolicyEnv(terrain=...)) to rewrite self.terrain in place.  Calling with no argument restores the nominal model."""
         self.sync_sim()  # a sim stage left in flight by step_pipelined() may still read the old table
         N = self.num_envs
         if mass_scale is None and friction is None and floor_normal is None and floor_offset is None:
@@ -207,6 +208,11 @@ class WalkController:
             self.env_params = ep
         if terrain is None:
             self.terrain = None
+        elif isinstance(terrain, str):
+            if terrain != "flat":
+                raise _lib.TsidbError(f"set_env_params: terrain must be a dict, 'flat' or None, got {terrain!r}")
+            self.terrain = torch.zeros(N, 20, dtype=self.dtype, device=self.device)
+            self.terrain[:, 3] = 1.0
         else:
             tr = torch.zeros(N, 20, dtype=torch.float64)
             d = torch.as_tensor(terrain["direction"], dtype=torch.float64).reshape(N, 2)
