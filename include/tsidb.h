@@ -619,6 +619,73 @@ int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *ro
 int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *rows, int rows_ld, const void *qpos,
                              const void *tau, void *teacher_obs, int obs_ld, void *stream);
 
+/* ---- the policy's side of a rollout: a dense actor and an optional critic evaluated on the env's own rows, the Gaussian sample
+ * with its log-probability, and the advantages of a recorded rollout.  Both calls are plain asynchronous launches on the given
+ * stream: no allocation, no host synchronisation, no state of their own - T policy steps with their actor calls can be captured
+ * as one graph.  Hot path: f32-input MFMA (v_mfma_f32_16x16x4_f32), exact float32 products and sums whatever the path's type.
+ *
+ * A network is 1 .. TSIDB_POL_NET_MAXLAYERS dense layers, y = weight x + bias, each at most TSIDB_POL_NET_MAXWIDTH wide, with
+ * the hidden activation after every layer but the last (ELU with alpha = 1, tanh or ReLU); the last layer is linear.  weight
+ * [width, fan-in] row-major and bias [width] (NULL = none) are float32 device pointers in torch.nn.Linear's own layout, READ IN
+ * PLACE AT EVERY LAUNCH: nothing is packed or cached, so an optimiser step on the tensors behind them is seen by the next launch.
+ * The input row of env e is the concatenation of 1 .. TSIDB_POL_NET_MAXBLOCKS column blocks, block[i][e * block_ld[i] + c] for
+ * c < block_cols[i], in the path's type (cast to float32 on load; any [N, k] view with a row stride, such as obs inside its
+ * TSIDB_POL_NOBS + TSIDB_POL_NPRIV row); at most TSIDB_POL_NET_MAXWIDTH columns in total = the fan-in of layer 0.  The struct is
+ * copied into the launch; the handle keeps nothing of it. */
+enum { TSIDB_POL_NET_MAXLAYERS = 4, TSIDB_POL_NET_MAXBLOCKS = 4, TSIDB_POL_NET_MAXWIDTH = 512 };
+enum { TSIDB_POL_ACT_ELU = 0, TSIDB_POL_ACT_TANH = 1, TSIDB_POL_ACT_RELU = 2 };
+enum { TSIDB_POL_ACTOR_SAMPLE = 1 /* flags bit 0 */ };
+typedef struct tsidb_policy_net {
+  int n_layers;
+  int width[4];           /* outputs of each layer */
+  int activation;         /* TSIDB_POL_ACT_* */
+  const float *weight[4];
+  const float *bias[4];
+  int n_blocks;
+  const void *block[4];
+  int block_ld[4];        /* row stride in elements, >= block_cols */
+  int block_cols[4];
+} tsidb_policy_net;
+
+/* what tsidb_policy_actor writes; every pointer is optional (NULL = not written), rows at or beyond N are never touched */
+typedef struct tsidb_policy_actor_out {
+  void *action;           /* [N, NA] the path's type: action32 cast, ready for tsidb_policy_act */
+  float *action32;        /* [N, NA] */
+  float *mean;            /* [N, NA] the actor's output */
+  float *logp;            /* [N] */
+  float *value;           /* [N] the critic's output */
+  float *actor_input;     /* [N, K_actor] the assembled float32 input rows */
+  float *critic_input;    /* [N, K_critic] */
+} tsidb_policy_actor_out;
+
+/* Evaluates the actor (last width = NA) and, unless critic is NULL, the critic (last width = 1) for every env, in one launch; actor
+ * may be NULL in a call with a critic (the value alone: the last row of a rollout, no draw whatever the flags).  flags bit 0
+ * (TSIDB_POL_ACTOR_SAMPLE) clear: action = mean, no draw.  Set: log_std [NA] float32 (device, read in place) and
+ *   eps_a = sqrt(-2 ln(1 - U1)) cos(2 pi U2), formed in float64 and cast to float32 once;   action_a = mean_a + exp(log_std_a) eps_a
+ * with U1, U2 two more streams of the randomisation's key layout (key = seed + ((stream * 256 + column) * 2^32), the same hash):
+ *   stream  draw                     column              counter
+ *   21      action noise, U1         actuator            episode * 2^32 + ep_len, as the observation noise (stream 7)
+ *   22      action noise, U2         actuator            same
+ * for the env index env_offset + env; episode and ep_len are read from bufs.  TWO CALLS ON THE SAME (env, episode, ep_len) DRAW
+ * THE SAME NOISE: the sample belongs to the observation, not to the call, and a batch split over ranks draws what the unsplit
+ * batch draws.  logp = -sum_a (eps_a^2 / 2 + log_std_a) - NA ln(2 pi) / 2, the log-probability of the unclipped sample (eps = 0
+ * without the flag; log_std = 0 where it is NULL); the clip stays tsidb_policy_act's.  bufs may be NULL without the flag.
+ * Rejects (message via tsidb_last_error, nothing launched): a NULL out, both networks NULL, n_layers outside 1 .. 4, n_blocks outside
+ * 1 .. 4, a width or an input total of 0 or above 512, block_cols < 1, block_ld < block_cols, a NULL block or weight, an unknown
+ * activation, an actor whose last width is not NA, a critic whose last width is not 1, the flag without bufs (episode, ep_len)
+ * or log_std, a seed >= 2^32 or an env_offset >= 2^31. */
+int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                       void *stream);
+
+/* Generalised advantage estimation over T recorded policy steps, float32, one lane per env, backwards from A_T = 0:
+ *   r'_t = r_t + gamma V_t timeout_t;   delta_t = r'_t + gamma V_{t+1} (1 - done_t) - V_t;
+ *   A_t = delta_t + gamma lam (1 - done_t) A_{t+1};   returns_t = A_t + V_t
+ * reward, done [T, N] in the path's type, timeout [T, N] int32, value [T + 1, N] float32 (the last row: the critic on the
+ * observation after the last step); advantage, returns [T, N] float32.  Rejects T < 1 and a NULL buffer. */
+int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done, const int32_t *timeout, const float *value,
+                     float gamma, float lam, float *advantage, float *returns, void *stream);
+
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */
 int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void *hbias, void *Jcom, void *Jf,

@@ -22,7 +22,14 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               4 % mass range, friction 0.4 - 1, 5 degrees of tilt, steps of 0 - 1 cm, an 11 x 7 scan) against the env without them on
               tables drawn once on the host (wc.randomize(): the same sim path, no per-episode redraw, no scan), in alternating
               windows, at 4096 and 512 envs, decimation 4 and 10; default profiles/policy_terrain.json.  The two kernels' times come
-              from a run of their own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --terrain --trace ENVS STEPS"""
+              from a run of their own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --terrain --trace ENVS STEPS
+    python tools/policy_env.py --actor [out.json]   the policy in the loop: PolicyEnv.rollout with a PolicyActor (one fused launch per
+              step: networks, sample, log-probability, value, written into the rollout storage) against TorchActor below - the same
+              networks as nn.Sequential in float32 with cat, cast, torch.randn, log-prob, value, cast back and copies into the same
+              storage - each eager and captured in a graph, in alternating windows of 16-step rollouts (a process per case), at 4096 and 512 envs,
+              decimation 4; actor obs -> 256 -> 128 -> NA (ELU), critic obs | priv -> 256 -> 128 -> 1, and the same with obs |
+              height_scan (77) as the actor's input; default profiles/policy_actor.json.  The kernel's time comes from a run of its
+              own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --actor --trace ENVS STEPS"""
 import json
 import sys
 import time
@@ -305,7 +312,125 @@ def measure_tsid(n, tsid, mode, decimation=4, window=100, windows=4, preroll=20)
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
 
 
+def actor_nets(env, scan, seed=1):
+    """(actor, critic, actor_inputs, critic_inputs, log_std) of the --actor measurement, float32 on the env's device"""
+    torch.manual_seed(seed)
+    k = env.NOBS + (77 if scan else 0)
+    mlp = lambda i, o: torch.nn.Sequential(torch.nn.Linear(i, 256), torch.nn.ELU(), torch.nn.Linear(256, 128), torch.nn.ELU(),
+                                           torch.nn.Linear(128, o)).to(env.device)
+    return (mlp(k, env.NA), mlp(env.NOBS + 4, 1), ("obs", "height_scan") if scan else ("obs",), ("obs", "priv"),
+            torch.full((env.NA,), -2.0, dtype=torch.float32, device=env.device))
+
+
+class TorchActor:
+    """PolicyActor and PolicyEnv.rollout with torch ops in place of the fused launch, into the same RolloutStorage"""
+
+    def __init__(self, env, actor, critic, actor_inputs, critic_inputs, log_std):
+        self.env, self.actor, self.critic, self.log_std = env, actor, critic, log_std
+        self.ai, self.ci = [getattr(env, k) for k in actor_inputs], [getattr(env, k) for k in critic_inputs]
+
+    @torch.no_grad()
+    def rollout(self, steps, st):
+        env, ls = self.env, self.log_std
+        for t in range(steps):
+            x, xc = torch.cat(self.ai, dim=1).float(), torch.cat(self.ci, dim=1).float()
+            mean = self.actor(x)
+            eps = torch.randn_like(mean)
+            a = mean + ls.exp() * eps
+            st.logp[t].copy_(-(0.5 * eps * eps + ls).sum(1) - 0.5 * env.NA * 1.8378770664093453)
+            st.value[t].copy_(self.critic(xc).squeeze(1))
+            st.actor_input[t].copy_(x); st.critic_input[t].copy_(xc); st.action[t].copy_(a); st.mean[t].copy_(mean)
+            env.step(a.to(env.dtype))
+            st.reward[t].copy_(env.reward); st.done[t].copy_(env.done); st.timeout[t].copy_(env.timeout)
+        st.value[steps].copy_(self.critic(torch.cat(self.ci, dim=1).float()).squeeze(1))
+        return st
+
+
+def captured(fn):
+    """fn captured in a graph after a warm-up on a side stream; returns the replay.  The replay keeps fn alive, and with it every
+    tensor the captured launches read and write (the actor's parameters and outputs, the storage: rollout_written()) - a graph
+    holds addresses, not references"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return lambda keep=fn: g.replay()
+
+
+def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll=3):
+    """policy-steps/s of 16-step rollouts: fused / torch, each eager and graph-captured, in alternating windows of one process"""
+    from tsid_control_amd import PolicyActor, RolloutStorage
+    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    kw = dict(KW, action_scale=0.05, terrain=TERRAIN) if scan else dict(KW, action_scale=0.05)
+    run, envs = {}, {}
+    for name in ("fused", "fused_graph", "torch", "torch_graph"):
+        env = envs[name] = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **kw)
+        actor, critic, ai, ci, ls = actor_nets(env, scan)
+        pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls)
+        st = RolloutStorage(env, pa, steps)
+        if name.startswith("fused"):
+            fn = lambda env=env, pa=pa, st=st: env.rollout(pa, steps, st)
+        else:
+            ta = TorchActor(env, actor, critic, ai, ci, ls)
+            fn = lambda ta=ta, st=st: ta.rollout(steps, st)
+        run[name] = captured(fn) if name.endswith("graph") else fn
+    for fn in run.values():
+        for _ in range(preroll):
+            fn()
+    torch.cuda.synchronize()
+    res = {k: [] for k in run}
+    order = list(run)
+    for w in range(windows):
+        for name in order[w % 4:] + order[:w % 4]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(window):
+                run[name]()
+            torch.cuda.synchronize()
+            res[name].append(window * steps / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    us = {k: 1e6 / v for k, v in med.items()}
+    return dict(envs=n, actor_input="obs | height_scan" if scan else "obs", decimation=decimation, rollout_steps=steps, window_rollouts=window,
+                windows=windows, policy_steps_per_s_median=med, all=res, us_per_policy_step=us,
+                fused_over_torch=med["fused"] / med["torch"], fused_graph_over_torch_graph=med["fused_graph"] / med["torch_graph"],
+                fused_over_torch_graph=med["fused"] / med["torch_graph"],
+                restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
+                height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--actor":
+        from tsid_control_amd import PolicyActor
+        if len(sys.argv) > 2 and sys.argv[2] == "--trace":
+            n, k = int(sys.argv[3]), int(sys.argv[4])
+            env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=4, terrain=TERRAIN, **dict(KW, action_scale=0.05))
+            for scan in (False, True):
+                actor, critic, ai, ci, ls = actor_nets(env, scan)
+                env.rollout(PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls), k).gae(0.99, 0.95)
+            torch.cuda.synchronize()
+            sys.exit(0)
+        if len(sys.argv) > 2 and sys.argv[2] == "--case":           # one (envs, actor input) case, as a JSON line
+            print(json.dumps(measure_actor(int(sys.argv[3]), sys.argv[4] == "scan")))
+            sys.exit(0)
+        import subprocess
+        out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_actor.json"
+        runs = []
+        for n in (4096, 512):                                       # a process per case: four envs and two captured graphs each
+            for scan in ("obs", "scan"):
+                r = subprocess.run([sys.executable, sys.argv[0], "--actor", "--case", str(n), scan], capture_output=True, text=True, check=True)
+                runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", actor="K -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU",
+                   runs=runs)
+        text = json.dumps(out, indent=1)
+        print(text)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--tsid":
         import os
         tsid, rest = sys.argv[2], sys.argv[3:]

@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("PolicyEnv", "PolicyRandomization", "PolicyTerrain"):
         from . import policy_env
         return getattr(policy_env, name)
+    if name in ("PolicyActor", "RolloutStorage", "rollout_written"):
+        from . import policy_actor
+        return getattr(policy_actor, name)
     if name in ("Footstep", "Support", "FootstepPlanner"):
         from . import footstep_planner
         return getattr(footstep_planner, name)

@@ -16,7 +16,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs",
            "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise",
            "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs",
-           "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan"]
+           "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan",
+           "tsidb_policy_actor", "tsidb_policy_gae"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -64,6 +65,14 @@ POL_TEACH_NT = 4
 POL_TEACH_SIGMA_COM, POL_TEACH_SIGMA_FOOT, POL_TEACH_WEIGHTS, POL_TEACH_NPARAMS = 0, 1, 2, 6
 
 
+# the policy actor (include/tsidb.h tsidb_policy_net): the most layers, input blocks and columns of a layer or of the input row,
+# the hidden activations, tsidb_policy_actor's flag, and the two streams of the action noise
+POL_NET_MAXLAYERS, POL_NET_MAXBLOCKS, POL_NET_MAXWIDTH = 4, 4, 512
+POL_ACTIVATIONS = ("elu", "tanh", "relu")
+POL_ACTOR_SAMPLE = 1
+POL_ACTOR_STREAMS = (21, 22)
+
+
 def pol_teach_nobs(na):
     """columns of the teacher observation for a robot with na actuators (TSIDB_POL_TEACH_NOBS is the v1 robot's)"""
     return 14 + na
@@ -94,6 +103,19 @@ class PolicyBufs(C.Structure):
     _fields_ = [("act_hist", C.c_void_p), ("last_action", C.c_void_p), ("prev_action", C.c_void_p), ("command", C.c_void_p),
                 ("air_time", C.c_void_p), ("ep_len", C.c_void_p), ("episode", C.c_void_p), ("delay", C.c_void_p),
                 ("terms", C.c_void_p), ("timeout", C.c_void_p), ("obs", C.c_void_p), ("obs_ld", C.c_int)]
+
+
+class PolicyNet(C.Structure):
+    """tsidb_policy_net (include/tsidb.h): a dense network, its parameters in place, and the column blocks of its input row"""
+    _fields_ = [("n_layers", C.c_int), ("width", C.c_int * 4), ("activation", C.c_int), ("weight", C.c_void_p * 4),
+                ("bias", C.c_void_p * 4), ("n_blocks", C.c_int), ("block", C.c_void_p * 4), ("block_ld", C.c_int * 4),
+                ("block_cols", C.c_int * 4)]
+
+
+class PolicyActorOut(C.Structure):
+    """tsidb_policy_actor_out (include/tsidb.h): what tsidb_policy_actor writes, every pointer optional"""
+    _fields_ = [("action", C.c_void_p), ("action32", C.c_void_p), ("mean", C.c_void_p), ("logp", C.c_void_p), ("value", C.c_void_p),
+                ("actor_input", C.c_void_p), ("critic_input", C.c_void_p)]
 
 
 def dims9(L):
@@ -167,6 +189,8 @@ def load(path=None):
     L.tsidb_policy_terrain_config.argtypes = [vp, vp, C.c_int]
     L.tsidb_policy_terrain_reset.argtypes = [vp, vp, vp, C.c_int, vp, i32p, vp]
     L.tsidb_policy_height_scan.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+    L.tsidb_policy_actor.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
+    L.tsidb_policy_gae.argtypes = [vp, C.c_int, vp, vp, i32p, vp, C.c_float, C.c_float, vp, vp, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

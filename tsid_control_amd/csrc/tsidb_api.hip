@@ -4,6 +4,7 @@
 #include "tsidb_sim.hpp"
 #include "tsidb_tick.hpp"
 #include "tsidb_policy.hpp"
+#include "tsidb_actor.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -728,6 +729,7 @@ struct tsidb_ctx {
   double pol_ter[TSIDB_POL_TER_NPARAMS] = {};
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
+  bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
   std::string err;
 };
 
@@ -1510,6 +1512,97 @@ int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
     h->note_stream(s);
     hipLaunchKernelGGL(k_policy_teacher_obs<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, r,
                        (const T *)rows, rows_ld, (const T *)qpos, (const T *)tau, (T *)teacher_obs, obs_ld);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+} // extern "C"
+
+// tsidb_policy_net as the kernel takes it, checked; `name` = "actor" / "critic", last = the width its last layer must have
+static ActorNet actor_net(const tsidb_policy_net *p, const char *who, const char *name, int last, const char *last_name, float *input) {
+  const std::string pre = std::string(who) + name + ": ";
+  if (p->n_layers < 1 || p->n_layers > ACT_MAXL) throw pre + "n_layers must be 1 .. 4";
+  if (p->n_blocks < 1 || p->n_blocks > ACT_MAXB) throw pre + "n_blocks must be 1 .. 4";
+  if (p->activation != ACT_ELU && p->activation != ACT_TANH && p->activation != ACT_RELU)
+    throw pre + "unknown activation (TSIDB_POL_ACT_ELU, _TANH or _RELU)";
+  ActorNet n = {};
+  n.n_layers = p->n_layers; n.n_blocks = p->n_blocks; n.activation = p->activation; n.input = input;
+  long total = 0;
+  for (int i = 0; i < p->n_blocks; i++) {
+    if (!p->block[i]) throw pre + "null input block";
+    if (p->block_cols[i] < 1 || p->block_cols[i] > ACT_MAXW) throw pre + "block_cols must be 1 .. 512";
+    if (p->block_ld[i] < p->block_cols[i]) throw pre + "block_ld < block_cols";
+    n.blk[i] = p->block[i]; n.blk_ld[i] = p->block_ld[i]; n.blk_cols[i] = p->block_cols[i];
+    total += p->block_cols[i];
+  }
+  if (total < 1 || total > ACT_MAXW) throw pre + "the input blocks must hold 1 .. 512 columns in total";
+  n.K = (int)total;
+  for (int l = 0; l < p->n_layers; l++) {
+    if (p->width[l] < 1 || p->width[l] > ACT_MAXW) throw pre + "width must be 1 .. 512";
+    if (!p->weight[l]) throw pre + "null weight";
+    n.width[l] = p->width[l]; n.W[l] = p->weight[l]; n.b[l] = p->bias[l];
+  }
+  if (p->width[p->n_layers - 1] != last) throw pre + "the last width must be " + last_name;
+  return n;
+}
+
+extern "C" {
+
+int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                       void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_actor: ";
+  hipStream_t s = (hipStream_t)stream;
+  if (!actor && !critic) throw std::string(who) + "null actor (only a call with a critic may leave it out)";
+  if (!out) throw std::string(who) + "null out";
+  ActorArgs a = {};
+  if (actor) a.net[0] = actor_net(actor, who, "actor", NA, "NA", out->actor_input);
+  if (critic) a.net[1] = actor_net(critic, who, "critic", 1, "1", out->critic_input);
+  if (seed >= (1ull << 32) || env_offset >= (1ull << 31)) throw std::string(who) + "seed must be below 2^32 and env_offset below 2^31";
+  a.sample = actor ? flags & TSIDB_POL_ACTOR_SAMPLE : 0;
+  a.first = actor ? 0 : 1;
+  if (a.sample) {
+    if (!bufs || !bufs->episode || !bufs->ep_len) throw std::string(who) + "sampling needs bufs (episode, ep_len)";
+    if (!log_std) throw std::string(who) + "sampling needs log_std";
+    a.episode = bufs->episode; a.ep_len = bufs->ep_len;
+  }
+  int widest = 0;
+  for (int y = 0; y < 2; y++) {
+    if (a.net[y].K > widest) widest = a.net[y].K;
+    for (int l = 0; l < a.net[y].n_layers; l++) if (a.net[y].width[l] > widest) widest = a.net[y].width[l];
+  }
+  a.n = h->num_envs; a.LD = act_ld(widest);
+  a.action = out->action; a.action32 = out->action32; a.mean = out->mean; a.logp = out->logp; a.value = out->value;
+  a.log_std = (const float *)log_std; a.seed = seed; a.env_offset = env_offset;
+  const size_t lds = act_lds_bytes(a.LD);
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    if (lds > 65536 && !h->actor_big_lds) {   // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle)
+      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_actor<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)act_lds_bytes(act_ld(ACT_MAXW))));
+      h->actor_big_lds = true;
+    }
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_actor<T>, dim3((h->num_envs + ACT_TILE - 1) / ACT_TILE, actor && critic ? 2 : 1), dim3(WAVE * ACT_WAVES), lds, s, a);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done, const int32_t *timeout, const float *value,
+                     float gamma, float lam, float *advantage, float *returns, void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_gae: ";
+  hipStream_t s = (hipStream_t)stream;
+  if (T < 1) throw std::string(who) + "T must be >= 1";
+  if (!reward || !done || !timeout || !value || !advantage || !returns) throw std::string(who) + "null buffer";
+  h->note_stream(s);
+  with_dtype(h->dtype, [&](auto t) {
+    using F = decltype(t);
+    hipLaunchKernelGGL(k_policy_gae<F>, dim3((h->num_envs + 255) / 256), dim3(256), 0, s, h->num_envs, T, (const F *)reward, (const F *)done,
+                       timeout, value, gamma, lam, advantage, returns);
   });
   HIP_OK(hipGetLastError());
   GUARD_END

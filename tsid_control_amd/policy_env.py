@@ -553,3 +553,31 @@ class PolicyEnv:
         if self._dr_push:
             info["push"] = wc.xfrc[:, 0, :3]
         return self.obs, self.reward, self.done, info
+
+    def rollout(self, actor, steps, storage=None):
+        """`steps` policy steps with `actor` (a PolicyActor on this env) in the loop: per step one actor launch - networks, sample,
+        log-probability and value on the current observation, written straight into slot t of the storage - then step(action) and
+        three device copies of reward, done and timeout; last, one critic-only launch on the final observation into value[steps].
+        storage: a RolloutStorage of this env, actor and length to reuse (None = a new one); returned.  Everything stays on the
+        current stream with no host synchronisation, so a whole rollout can be captured in a graph (policy_actor.rollout_written
+        lists what it writes beyond written()).  storage.gae(gamma, lam) then gives the advantages and returns."""
+        from .policy_actor import PolicyActor, RolloutStorage
+        if not isinstance(actor, PolicyActor) or actor.env is not self:
+            raise _lib.TsidbError("PolicyEnv.rollout: actor must be a PolicyActor built on this env")
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise _lib.TsidbError(f"PolicyEnv.rollout: steps must be a whole number >= 1, got {steps!r}")
+        if storage is None:
+            storage = RolloutStorage(self, actor, steps)
+        elif not isinstance(storage, RolloutStorage) or storage.env is not self or storage.actor is not actor or storage.steps != steps:
+            raise _lib.TsidbError("PolicyEnv.rollout: storage must be a RolloutStorage of this env, this actor and this many steps")
+        st = storage
+        for t in range(steps):
+            actor._launch(True, action=actor.action, action32=st.action[t], mean=st.mean[t], logp=st.logp[t], value=st.value[t],
+                          actor_input=st.actor_input[t], critic_input=st.critic_input[t] if st.critic_input is not None else None)
+            self.step(actor.action)
+            st.reward[t].copy_(self.reward)
+            st.done[t].copy_(self.done)
+            st.timeout[t].copy_(self.timeout)
+        if actor.critic_net is not None:
+            actor._launch(False, actor=False, value=st.value[steps])
+        return storage
