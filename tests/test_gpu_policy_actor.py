@@ -11,9 +11,9 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import policy_actor_reference as R  # noqa: E402
-from test_gpu_policy_dr import CMD, DR, driven, same  # noqa: E402
-from test_gpu_policy_env import ALL_WEIGHTS, host, make_env  # noqa: E402
-from test_gpu_policy_tsid import make_env as make_tsid_env, standing_conf  # noqa: E402
+from policy_testlib import capture, conf_of, host, make_env, same  # noqa: E402
+from test_gpu_policy_dr import CMD, DR, driven  # noqa: E402
+from test_gpu_policy_env import ALL_WEIGHTS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -73,9 +73,9 @@ def test_kernel_matches_the_numpy_restatement(dtype, v0):
     from tsid_control_amd import PolicyActor
     worst = dict(mean=0.0, value=0.0, action32=0.0, logp=0.0)
     for n in (1, 17, 33):
-        env = make_tsid_env(n, standing_conf(dtype, v0), tsid="stand", mode="position", decimation=2, action_scale=0.25, seed=11,
-                            reward_weights=dict(alive=1.0), randomization=dict(seed=7, env_offset=5, noise_joint_vel=0.5, noise_ang_vel=0.1),
-                            terrain=dict(tilt_deg=3.0, step_height=(0.0, 0.01), **SCAN))
+        env = make_env(n, conf_of(dtype, v0, closed_loop=True), tsid="stand", mode="position", decimation=2, action_scale=0.25, seed=11,
+                       reward_weights=dict(alive=1.0), randomization=dict(seed=7, env_offset=5, noise_joint_vel=0.5, noise_ang_vel=0.1),
+                       terrain=dict(tilt_deg=3.0, step_height=(0.0, 0.01), **SCAN))
         NA = env.NA
         assert env.NOBS == (65 if v0 else 71) and env.height_scan.shape == (n, 77)
         for t in range(5):
@@ -270,23 +270,7 @@ def test_captured_rollout_replays_bit_identically():
     from tsid_control_amd.policy_actor import RolloutStorage
     st = RolloutStorage(env, pa, T)
     written = list(env.written()) + list(rollout_written(st))
-    saved = [x.clone() for x in written]
-
-    def rewind():
-        for x, s in zip(written, saved):
-            x.copy_(s)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.rollout(pa, T, st)                              # warm-up (lazy kernel loads), then rewind
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    rewind()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        env.rollout(pa, T, st)
-    for x, s in zip(written, saved):
-        assert same(x, s)
+    g, rewind = capture(lambda: env.rollout(pa, T, st), written)
     g.replay()
     torch.cuda.synchronize()
     replayed = [x.clone() for x in written]

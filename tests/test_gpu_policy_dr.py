@@ -16,7 +16,8 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 from policy_dr_reference import PolicyDRReference  # noqa: E402
-from test_gpu_policy_env import ALL_WEIGHTS, host, make_env, rand, rel  # noqa: E402
+from policy_testlib import conf_of, host, make_env, rel, replay_against_eager, same  # noqa: E402
+from test_gpu_policy_env import ALL_WEIGHTS, rand  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,10 +59,6 @@ def driven(n, na, seed, env, hard=1.0, soft=0.05, step=None):
         e = torch.arange(n, device=a.device)
         a[(e >= n // 2) & ((7 * step + e) % 23 == 0), 0] = float("nan")
     return a.contiguous()
-
-
-def same(a, b):
-    return torch.equal(a, b) or bool((torch.isnan(a) == torch.isnan(b)).all()) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
 
 
 # ---------------------------------------------------------------------------- (1) the kernels against the restatement
@@ -178,7 +175,6 @@ def test_pushed_sim_state_is_that_of_the_hand_driven_loop():
     xfrc copied in each step: bit-identical qpos, qvel, ncon and con_pairs.  Forces of at most 1 N; identity is asserted, not
     survival (how the position-servo robot takes a push has not been measured)."""
     from tsid_control_amd import WalkController
-    from test_gpu_policy_env import conf_of
     n, steps = 16, 40
     dr = dict(seed=5, push_interval=6, push_duration=2, push_force_lo=0.2, push_force_hi=1.0, noise_joint_vel=0.5, command_interval=4)
     env = make_env(n, decimation=5, action_scale=0.5, filter_alpha=0.6, max_episode_steps=15, command_range=CMD, randomization=dr)
@@ -253,34 +249,12 @@ def test_captured_randomised_step_replays_bit_identically():
               randomization=DR)
     eager, env = make_env(n, **kw), make_env(n, **kw)
     actions = [driven(n, env.NA, 900 + t, env, 0.5, step=t) for t in range(steps)]
-    buf = torch.zeros_like(actions[0])
-    written = list(env.written())
-    assert any(x is env.wc.xfrc for x in written)
-    saved = [x.clone() for x in written]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.step(buf)                                      # warm-up (lazy kernel loads), then rewind
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for x, s in zip(written, saved):
-        x.copy_(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        env.step(buf)
-    for x, s in zip(written, saved):
-        assert same(x, s)
+    assert any(x is env.wc.xfrc for x in env.written())
     restarts = pushed = 0
-    for t in range(steps):
-        buf.copy_(actions[t])
-        g.replay()
-        eager.step(actions[t])
-        torch.cuda.synchronize()
+    for t in replay_against_eager(env, eager, actions):
         restarts += int(env.done.sum())
         pushed += int((env.wc.xfrc[:, 0, :3] != 0).any(1).sum())
-        for a, b in zip(env.written(), eager.written()):
-            assert same(a, b), t
-    assert restarts >= 2 * n and pushed >= 2 * n
+    assert t == steps - 1 and restarts >= 2 * n and pushed >= 2 * n
 
 
 # ---------------------------------------------------------------------------- (6) lifecycle

@@ -17,29 +17,12 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 from policy_reference import PolicyReference  # noqa: E402
+from policy_testlib import conf_of, host, make_env, rel, replay_against_eager, staged_step  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ALL_WEIGHTS = dict(track_lin_vel=1.0, track_ang_vel=0.5, lin_vel_z=-2.0, ang_vel_xy=-0.05, orientation=-1.0, base_height=-10.0,
                    torques=-1e-4, action_rate=-0.01, joint_vel=-1e-3, feet_air_time=1.0, alive=0.2, termination=-5.0)
-
-
-def conf_of(dtype="f64", v0=False):
-    from tsid_control_amd import RobotConfig, op3_v0_conf
-    conf = op3_v0_conf() if v0 else RobotConfig()
-    conf.dtype = dtype
-    if v0:
-        conf.done_base_height = 0.12    # (the v0 robot stands lower than the v1 robot's default fall height)
-    return conf
-
-
-def make_env(n, dtype="f64", v0=False, **kw):
-    from tsid_control_amd import PolicyEnv
-    return PolicyEnv(conf_of(dtype, v0), num_envs=n, device="cuda:0", **kw)
-
-
-def host(t):
-    return t.detach().cpu().numpy().copy()
 
 
 def rand(shape, seed, env, scale=1.0):
@@ -71,31 +54,7 @@ def reference_of(env, dtype=np.float64):
     return r
 
 
-def staged_step(env, action, after_act=None, after_reward=None):
-    """PolicyEnv.step() stage by stage, with hooks where a test reads what the next stage overwrites"""
-    wc = env.wc
-    env._act(action)
-    if after_act:
-        after_act()
-    wc.sim_steps(env.decimation)
-    env._reward()
-    if after_reward:
-        after_reward()
-    wc.reset_done()
-    env._obs()
-
-
 # ---------------------------------------------------------------------------- (1) the kernels against the numpy reference
-def rel(a, b):
-    """largest |a - b| / max(1, |b|); NaN only where both are"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    if a.size == 0:
-        return 0.0
-    with np.errstate(invalid="ignore"):
-        return float(np.nanmax(np.concatenate([[0.0], (np.abs(a - b) / np.maximum(1.0, np.abs(b))).reshape(-1)])))
-
-
 @pytest.mark.parametrize("dtype,v0", [("f64", False), ("f64", True), ("f32", False), ("f32", True)])
 def test_kernels_match_the_numpy_reference(dtype, v0):
     """60 policy steps of 32 envs under random actions, every term weighted, delays 0 .. 7, a filter, a clip that bites,
@@ -267,35 +226,36 @@ def test_captured_step_replays_bit_identically():
     actions = [rand((n, env.NA), 900 + t, env, 0.5) for t in range(steps)]
     for a in actions:
         a[: n // 2] *= 0.1
-    buf = torch.zeros_like(actions[0])
-    written = list(env.written())
-    saved = [x.clone() for x in written]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.step(buf)                                      # warm-up (lazy kernel loads), then rewind
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for x, s in zip(written, saved):
-        x.copy_(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        env.step(buf)
-    for x, s in zip(written, saved):                       # (a capture runs nothing; rewind anyway: nothing may have moved)
-        assert torch.equal(x, s)
     restarts = 0
-    for t in range(steps):
-        buf.copy_(actions[t])
-        g.replay()
-        eager.step(actions[t])
-        torch.cuda.synchronize()
+    for t in replay_against_eager(env, eager, actions):
         restarts += int(env.done.sum())
-        for a, b in zip(env.written(), eager.written()):
-            assert torch.equal(a, b) or (torch.isnan(a) == torch.isnan(b)).all() and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)), t
-    assert restarts >= 2 * n
+    assert t == steps - 1 and restarts >= 2 * n
 
 
-# ---------------------------------------------------------------------------- (6) errors
+# ---------------------------------------------------------------------------- (6) a group that is off launches nothing
+def test_launches_of_a_group_that_is_off_return_without_launching():
+    """no randomisation, no terrain: tsidb_policy_perturb (before it looks for an xfrc buffer), tsidb_policy_reset_noise and
+    tsidb_policy_height_scan return 0 (wc._call raises on anything else) and leave every written tensor as it was, bit for
+    bit - with every env flagged done, so that a launch would have had work"""
+    n = 4
+    env = make_env(n)
+    wc, vp = env.wc, C.c_void_p
+    assert wc.xfrc is None and env.terrain is None
+    wc.done.fill_(1)
+    scan = torch.full((n, 4), -7.0, dtype=wc.dtype, device=wc.device)
+    torch.cuda.synchronize()
+    saved = [x.clone() for x in env.written()]
+    wc._call("tsidb_policy_perturb", C.byref(env._bufs), wc._stream())
+    wc._call("tsidb_policy_reset_noise", C.byref(env._bufs), vp(wc.rows.data_ptr()), wc.NROW, vp(wc.qpos.data_ptr()), vp(wc.qvel.data_ptr()),
+             wc._stream())
+    wc._call("tsidb_policy_height_scan", C.byref(env._bufs), vp(wc.qpos.data_ptr()), vp(scan.data_ptr()), 4, wc._stream())
+    torch.cuda.synchronize()
+    for x, s in zip(env.written(), saved):
+        assert torch.equal(x, s)
+    assert (scan == -7.0).all()
+
+
+# ---------------------------------------------------------------------------- (7) errors
 def test_calls_are_rejected_with_a_message():
     from tsid_control_amd import WalkController, _lib
     n = 4

@@ -20,8 +20,9 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 from policy_terrain_reference import PolicyTerrainReference  # noqa: E402
-from test_gpu_policy_dr import CMD, DR, driven, same  # noqa: E402
-from test_gpu_policy_env import ALL_WEIGHTS, host, make_env, rel  # noqa: E402
+from policy_testlib import conf_of, host, make_env, rel, replay_against_eager, same  # noqa: E402
+from test_gpu_policy_dr import CMD, DR, driven  # noqa: E402
+from test_gpu_policy_env import ALL_WEIGHTS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -222,13 +223,12 @@ def test_sim_steps_on_the_rewritten_tables():
 def test_terrain_with_tsid_in_the_loop_steps_the_rewritten_tables():
     """tsid = "stand", residual mode: the closed-loop tick + sim reads the rewritten tables as the plain sim does - the same twin
     identity over 16 steps with restarts; the controller itself is not told about the floor"""
-    from test_gpu_policy_tsid import TEACH, standing_conf
-    from tsid_control_amd import PolicyEnv
+    from test_gpu_policy_tsid import TEACH
     n, steps = 16, 16
-    kw = dict(num_envs=n, device="cuda:0", decimation=4, mode="residual", action_scale=0.05, max_episode_steps=5, tsid="stand", teacher_weights=TEACH,
+    kw = dict(decimation=4, mode="residual", action_scale=0.05, max_episode_steps=5, tsid="stand", teacher_weights=TEACH,
               randomization=dict(seed=5, reset_joint_pos=0.05))
     ter = dict(TER, tilt_deg=2.0, step_height=(0.0, 0.005))
-    env, twin = PolicyEnv(standing_conf(), terrain=ter, **kw), PolicyEnv(standing_conf(), **kw)
+    env, twin = make_env(n, conf_of(closed_loop=True), terrain=ter, **kw), make_env(n, conf_of(closed_loop=True), **kw)
     twin.wc.set_env_params(mass_scale=1.0, terrain="flat")
     mirror = lambda: (twin.wc.env_params.copy_(env.wc.env_params), twin.wc.terrain.copy_(env.wc.terrain))
     mirror()
@@ -308,32 +308,10 @@ def test_captured_step_with_a_terrain_replays_bit_identically():
     for e in (eager, env):
         e.terrain_level.copy_(torch.arange(n, dtype=torch.int32, device=e.device) % 3)
     actions = [driven(n, env.NA, 900 + t, env, 0.5, step=t) for t in range(steps)]
-    buf = torch.zeros_like(actions[0])
-    written = list(env.written())
-    saved = [x.clone() for x in written]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.step(buf)                                      # warm-up (lazy kernel loads), then rewind
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for x, s in zip(written, saved):
-        x.copy_(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        env.step(buf)
-    for x, s in zip(written, saved):
-        assert same(x, s)
     restarts = 0
-    for t in range(steps):
-        buf.copy_(actions[t])
-        g.replay()
-        eager.step(actions[t])
-        torch.cuda.synchronize()
+    for t in replay_against_eager(env, eager, actions):
         restarts += int(env.done.sum())
-        for a, b in zip(env.written(), eager.written()):
-            assert same(a, b), t
-    assert restarts >= 2 * n
+    assert t == steps - 1 and restarts >= 2 * n
 
 
 # ---------------------------------------------------------------------------- (6) degenerate ranges

@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 from policy_teacher_reference import TeacherReference  # noqa: E402
+from policy_testlib import conf_of, host, make_env, rel, replay_against_eager, staged_step  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,29 +28,13 @@ TEACH = dict(track_com=1.5, track_feet=0.75, contact_match=0.25, deviation=-0.02
 
 
 def standing_conf(dtype="f64", v0=False):
-    from tsid_control_amd import RobotConfig, op3_v0_conf
-    conf = op3_v0_conf() if v0 else RobotConfig()
-    conf.dtype = dtype
-    conf.closed_loop = True
-    conf.reference_quirks = False
-    if v0:
-        conf.done_base_height = 0.12    # (the v0 robot stands lower than the v1 robot's default fall height)
-    return conf
+    return conf_of(dtype, v0, closed_loop=True)
 
 
 def walking_conf():
     from tsid_control_amd import RobotConfig
     from tsid_control_amd.walk_planner import op3_closed_loop_walking_conf
     return op3_closed_loop_walking_conf(RobotConfig())
-
-
-def make_env(n, conf, **kw):
-    from tsid_control_amd import PolicyEnv
-    return PolicyEnv(conf, num_envs=n, device="cuda:0", **kw)
-
-
-def host(t):
-    return t.detach().cpu().numpy().copy()
 
 
 def hashed(shape, key, env, scale=1.0):
@@ -61,38 +46,6 @@ def hashed(shape, key, env, scale=1.0):
         x = x ^ (x >> np.uint64(31))
     u = (x >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
     return torch.as_tensor(((2 * u - 1) * scale).reshape(shape)).to(env.device, env.dtype).contiguous()
-
-
-def rel(a, b):
-    """largest |a - b| / max(1, |b|); NaN only where both are"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    with np.errstate(invalid="ignore"):
-        return float(np.nanmax(np.concatenate([[0.0], (np.abs(a - b) / np.maximum(1.0, np.abs(b))).reshape(-1)])))
-
-
-def staged_step(env, action, before_reward=None, after_reward=None, after_teacher=None):
-    """PolicyEnv.step() with tsid set, stage by stage, with hooks where a test reads or writes what the next stage uses"""
-    wc = env.wc
-    env._act(action)
-    if env._dr_push:
-        env._perturb()
-    env._tsid_steps()
-    if before_reward:
-        before_reward()
-    env._reward()
-    if after_reward:
-        after_reward()
-    env._teacher()
-    if after_teacher:
-        after_teacher()
-    wc.reset_done()
-    if env.sched is not None:
-        env._replan()
-    if env._dr_reset:
-        env._reset_noise()
-    env._obs()
-    env._teacher_obs()
 
 
 def reference_of(env, dtype=np.float64):
@@ -219,15 +172,11 @@ def test_residual_mode_is_the_hand_driven_closed_loop():
     zeros = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
     moved = 0.0
     for t in range(steps):
-        env._act(hashed((n, env.NA), 300 + t, env, 1.0))
-        ctrl.copy_(env.wc.ctrl)
+        def grab():
+            ctrl.copy_(env.wc.ctrl)
+
+        staged_step(env, hashed((n, env.NA), 300 + t, env, 1.0), after_act=grab)
         moved = max(moved, float(ctrl.abs().max()))
-        env._tsid_steps()
-        env._reward()
-        env._teacher()
-        env.wc.reset_done()
-        env._obs()
-        env._teacher_obs()
         hand.step(dec)
         obs, reward, done, info = quiet.step(zeros)
         plain.step(dec)
@@ -347,34 +296,13 @@ def test_captured_walk_step_replays_bit_identically():
               delay=(torch.arange(n, dtype=torch.int32) % 4).to("cuda:0"), randomization=dr)
     eager, env = make_env(n, walking_conf(), **kw), make_env(n, walking_conf(), **kw)
     actions = [hashed((n, env.NA), 900 + t, env, 1.0) for t in range(steps)]
-    buf = torch.zeros_like(actions[0])
     written = list(env.written())
     assert any(x is env.clock for x in written) and any(x is env.sched.coef for x in written) and any(x is env.teacher_obs for x in written)
-    saved = [x.clone() for x in written]
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.step(buf)                                      # warm-up (lazy kernel loads), then rewind
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    for x, s in zip(written, saved):
-        x.copy_(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        env.step(buf)
-    for x, s in zip(written, saved):                       # (a capture runs nothing; nothing may have moved)
-        assert torch.equal(x, s)
     restarts = 0
-    for t in range(steps):
-        buf.copy_(actions[t])
-        g.replay()
-        eager.step(actions[t])
-        torch.cuda.synchronize()
+    for t in replay_against_eager(env, eager, actions):
         restarts += int(env.done.sum())
-        for a, b in zip(env.written(), eager.written()):
-            assert torch.equal(a, b) or (torch.isnan(a) == torch.isnan(b)).all() and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)), t
         assert float(env.clock) == pytest.approx((t + 1) * 4 * env.wc.conf.dt, abs=1e-12)
-    assert restarts >= n
+    assert t == steps - 1 and restarts >= n
 
 
 # ---------------------------------------------------------------------------- (5) the defaults change nothing

@@ -8,8 +8,8 @@ from pathlib import Path
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+from policy_testlib import HEADER, assert_prototypes, header_enums  # noqa: E402
 from test_policy_host import bare_env  # noqa: E402
 
 NAMES = ("tsidb_policy_actor", "tsidb_policy_gae")
@@ -39,8 +39,7 @@ def mlp(*sizes, act=torch.nn.ELU):
 
 def test_binding_matches_the_header():
     from tsid_control_amd import _lib
-    text = (ROOT / "include" / "tsidb.h").read_text()
-    en = {k: int(v) for k, v in re.findall(r"\b(TSIDB_POL_(?:NET|ACT|ACTOR)_[A-Z]+)\s*=\s*(\d+)\b", text)}
+    text, en = HEADER, header_enums("TSIDB_POL_")
     assert (_lib.POL_NET_MAXLAYERS, _lib.POL_NET_MAXBLOCKS, _lib.POL_NET_MAXWIDTH) == \
         (en["TSIDB_POL_NET_MAXLAYERS"], en["TSIDB_POL_NET_MAXBLOCKS"], en["TSIDB_POL_NET_MAXWIDTH"]) == (4, 4, 512)
     assert [en["TSIDB_POL_ACT_" + k.upper()] for k in _lib.POL_ACTIVATIONS] == [0, 1, 2]
@@ -55,16 +54,7 @@ def test_binding_matches_the_header():
         fields = re.findall(r"\b(\w+)(?:\[4\])?;", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S))
         assert fields == [f[0] for f in struct._fields_], cname
     assert C.sizeof(_lib.PolicyNet) == 4 + 16 + 4 + 32 + 32 + 4 + 4 + 32 + 16 + 16 and C.sizeof(_lib.PolicyActorOut) == 56
-    libs = sorted((ROOT / "tsid_control_amd").glob("libtsidb*.so"))
-    assert len(libs) >= 2
-    for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", text)
-        assert m, name
-        nargs = len(m.group(1).split(","))
-        for lib in libs:
-            fn = getattr(_lib.load(lib), name)
-            assert len(fn.argtypes) == nargs and fn.restype is C.c_int, (name, lib.name)
+    assert_prototypes(NAMES)
 
 
 def test_policy_actor_is_exported_and_resolves_its_inputs():

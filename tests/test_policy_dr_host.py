@@ -1,40 +1,22 @@
 """The policy randomisation (tsidb_policy_randomize / _perturb / _reset_noise, PolicyRandomization), the parts that need no
 GPU: the binding against the header, both libraries' exports, the launches a randomised PolicyEnv.step() makes, and the
 configurations the host rejects."""
-import ctypes as C
-import re
 import sys
 from pathlib import Path
 
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+from policy_testlib import HEADER, assert_prototypes, header_enums  # noqa: E402
 from test_policy_host import bare_env  # noqa: E402
 
 NAMES = ("tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise")
 
 
-def dr_enum(text):
-    """the TSIDB_POL_DR_* block of include/tsidb.h, running offsets resolved"""
-    body = re.search(r"enum \{\s*(TSIDB_POL_DR_SEED = 0.*?)\};", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    en, nxt = {}, 0
-    for item in body.split(","):
-        item = item.strip()
-        if not item:
-            continue
-        name, _, expr = (s.strip() for s in item.partition("="))
-        val = eval(expr, {}, dict(en)) if expr else nxt
-        en[name], nxt = int(val), int(val) + 1
-    return en
-
-
 def test_binding_matches_the_header():
     from tsid_control_amd import _lib
-    text = (ROOT / "include" / "tsidb.h").read_text()
-    en = dr_enum(text)
+    text, en = HEADER, header_enums("TSIDB_POL_DR_")
     assert len(en) == len(_lib.POL_DR_FIELDS) + 1
     for k in _lib.POL_DR_FIELDS:
         assert getattr(_lib, "POL_DR_" + k.upper()) == en["TSIDB_POL_DR_" + k.upper()], k
@@ -46,16 +28,7 @@ def test_binding_matches_the_header():
     # the key layout is in the header
     assert "key = seed + ((stream * 256 + column) * 2^32)" in text
     # prototypes and exports of both libraries
-    libs = sorted((ROOT / "tsid_control_amd").glob("libtsidb*.so"))
-    assert len(libs) >= 2
-    for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", text)
-        assert m, name
-        nargs = len(m.group(1).split(","))
-        for lib in libs:
-            fn = getattr(_lib.load(lib), name)
-            assert len(fn.argtypes) == nargs and fn.restype is C.c_int, (name, lib.name)
+    assert_prototypes(NAMES)
 
 
 def test_randomization_is_exported_and_defaults_to_off():

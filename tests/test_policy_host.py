@@ -7,31 +7,15 @@ from pathlib import Path
 
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+from policy_testlib import HEADER, assert_prototypes, header_enums  # noqa: E402
+
 NAMES = ("tsidb_policy_config", "tsidb_policy_act", "tsidb_policy_reward", "tsidb_policy_obs")
-
-
-def header_enums(text):
-    """every NAME = integer of include/tsidb.h's enums, the policy parameter vector's running offsets resolved"""
-    en = {k: int(v) for k, v in re.findall(r"\b(TSIDB_[A-Z0-9_]+)\s*=\s*(-?\d+)\b", text)}
-    body = re.search(r"enum \{\s*TSIDB_POL_P_CLIP = 0(.*?)\};", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    nxt = 1
-    for item in ("TSIDB_POL_P_CLIP = 0" + body).split(","):
-        item = item.strip()
-        if not item:
-            continue
-        name, _, expr = (s.strip() for s in item.partition("="))
-        val = eval(expr, {}, dict(en)) if expr else nxt
-        en[name], nxt = int(val), int(val) + 1
-    return en
 
 
 def test_binding_matches_the_header():
     from tsid_control_amd import _lib
-    text = (ROOT / "include" / "tsidb.h").read_text()
-    en = header_enums(text)
+    text, en = HEADER, header_enums()
     assert (_lib.POL_NT, _lib.POL_HIST, _lib.POL_NPRIV) == (en["TSIDB_POL_NT"], en["TSIDB_POL_HIST"], en["TSIDB_POL_NPRIV"]) == (12, 8, 4)
     assert len(_lib.POL_TERMS) == _lib.POL_NT and len(set(_lib.POL_TERMS)) == _lib.POL_NT
     assert _lib.pol_nobs(en["TSIDB_NA"]) == en["TSIDB_POL_NOBS"] == 71 and _lib.pol_nobs(18) == 65
@@ -48,16 +32,7 @@ def test_binding_matches_the_header():
     assert fields == [f[0] for f in _lib.PolicyBufs._fields_]
     assert [f[1] for f in _lib.PolicyBufs._fields_] == [C.c_void_p] * 11 + [C.c_int]
     # the prototypes: as many arguments as the header declares, and both libraries export them
-    libs = sorted((ROOT / "tsid_control_amd").glob("libtsidb*.so"))
-    assert len(libs) >= 2
-    for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", text)
-        assert m, name
-        nargs = len(m.group(1).split(","))
-        for lib in libs:
-            fn = getattr(_lib.load(lib), name)
-            assert len(fn.argtypes) == nargs and fn.restype is C.c_int, (name, lib.name)
+    assert_prototypes(NAMES)
 
 
 def test_policy_env_is_exported():

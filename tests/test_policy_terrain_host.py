@@ -1,7 +1,6 @@
 """Per-episode terrain and dynamics of the policy environment and its height scan (tsidb_policy_terrain_config / _terrain_reset /
 _height_scan, PolicyTerrain), the parts that need no GPU: the binding against the header, both libraries' exports, the
 configurations the host rejects, and the launches a PolicyEnv.step() / reset() with a terrain makes."""
-import ctypes as C
 import dataclasses
 import math
 import re
@@ -12,25 +11,16 @@ import numpy as np
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+from policy_testlib import HEADER, assert_prototypes, header_enums  # noqa: E402
 from test_policy_host import bare_env  # noqa: E402
 
 NAMES = ("tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan")
 
 
-def ter_enum(text):
-    """the TSIDB_POL_TER_* block of include/tsidb.h"""
-    body = re.search(r"enum \{\s*(TSIDB_POL_TER_SEED = 0.*?)\};", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [item.strip().partition("=")[0].strip() for item in body.split(",") if item.strip()]
-    return {name: i for i, name in enumerate(names)}
-
-
 def test_binding_matches_the_header():
     from tsid_control_amd import _lib
-    text = (ROOT / "include" / "tsidb.h").read_text()
-    en = ter_enum(text)
+    text, en = HEADER, header_enums("TSIDB_POL_TER_")
     assert len(en) == len(_lib.POL_TER_NAMES) + 1 == 24
     for k in _lib.POL_TER_NAMES:
         assert getattr(_lib, "POL_TER_" + k.upper()) == en["TSIDB_POL_TER_" + k.upper()], k
@@ -41,16 +31,7 @@ def test_binding_matches_the_header():
     # the streams continue the header's table
     for stream in range(12, 21):
         assert re.search(r"^ \*   %d  " % stream, text, re.M), stream
-    libs = sorted((ROOT / "tsid_control_amd").glob("libtsidb*.so"))
-    assert len(libs) >= 2
-    for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", text)
-        assert m, name
-        nargs = len(m.group(1).split(","))
-        for lib in libs:
-            fn = getattr(_lib.load(lib), name)
-            assert len(fn.argtypes) == nargs and fn.restype is C.c_int, (name, lib.name)
+    assert_prototypes(NAMES)
 
 
 def test_terrain_is_exported_and_its_defaults_are_the_nominal_floor():

@@ -1,7 +1,6 @@
 """TSID in the loop of the policy environment (PolicyEnv(tsid=...); tsidb_policy_teacher / _teacher_obs), the parts that need
 no GPU: the binding against the header, both libraries' exports, the launches a tsid step makes on a bare env, and the
 arguments the constructor rejects before it builds anything."""
-import ctypes as C
 import re
 import sys
 from pathlib import Path
@@ -9,33 +8,16 @@ from pathlib import Path
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+from policy_testlib import HEADER, assert_prototypes, header_enums  # noqa: E402
 from test_policy_host import bare_env  # noqa: E402
 
 NAMES = ("tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs")
 
 
-def teach_enum(text):
-    """the TSIDB_POL_TEACH_* parameter block of include/tsidb.h, running offsets resolved"""
-    sizes = {k: int(v) for k, v in re.findall(r"\b(TSIDB_POL_TEACH_N[A-Z]+)\s*=\s*(\d+)\b", text)}
-    body = re.search(r"enum \{\s*(TSIDB_POL_TEACH_SIGMA_COM = 0.*?)\};", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    en, nxt = dict(sizes), 0
-    for item in body.split(","):
-        item = item.strip()
-        if not item:
-            continue
-        name, _, expr = (s.strip() for s in item.partition("="))
-        val = eval(expr, {}, dict(en)) if expr else nxt
-        en[name], nxt = int(val), int(val) + 1
-    return en
-
-
 def test_binding_matches_the_header():
     from tsid_control_amd import _lib
-    text = (ROOT / "include" / "tsidb.h").read_text()
-    en = teach_enum(text)
+    text, en = HEADER, header_enums("TSIDB_POL_TEACH_")
     assert _lib.POL_TEACH_NT == en["TSIDB_POL_TEACH_NT"] == len(_lib.POL_TEACH_TERMS) == 4
     for k in ("SIGMA_COM", "SIGMA_FOOT", "WEIGHTS", "NPARAMS"):
         assert getattr(_lib, "POL_TEACH_" + k) == en["TSIDB_POL_TEACH_" + k], k
@@ -46,16 +28,7 @@ def test_binding_matches_the_header():
     assert tuple(table) == _lib.POL_TEACH_TERMS
     # the policy parameter vector was not renumbered
     assert (_lib.POL_P_CLIP, _lib.POL_P_WEIGHTS, _lib.POL_NPARAMS) == (0, 15, 27)
-    libs = sorted((ROOT / "tsid_control_amd").glob("libtsidb*.so"))
-    assert len(libs) >= 2
-    for name in NAMES:
-        assert name in _lib.SYMBOLS
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", text)
-        assert m, name
-        nargs = len(m.group(1).split(","))
-        for lib in libs:
-            fn = getattr(_lib.load(lib), name)
-            assert len(fn.argtypes) == nargs and fn.restype is C.c_int, (name, lib.name)
+    assert_prototypes(NAMES)
 
 
 def test_class_level_defaults_leave_a_bare_env_without_tsid():

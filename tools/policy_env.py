@@ -139,35 +139,58 @@ class TorchEnv:
         return self.obs, wc.reward, wc.done
 
 
-def measure(n, decimation, window=300, windows=4, preroll=60):
-    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
-    fused = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW)
-    eager = TorchEnv(n, decimation, delay)
-    bare_conf = RobotConfig()
-    bare_conf.reference_quirks = False
-    bare = WalkController(bare_conf, num_envs=n, device="cuda:0")
-    bare.set_ctrl(bare.ctrl_from_q(bare.q0).expand(n, -1).contiguous(), "position")
-    g = torch.Generator(device="cuda:0").manual_seed(1)
-    actions = [(torch.rand(n, fused.NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
-    run = dict(sim=lambda k: [bare.sim_steps(decimation) for _ in range(k)],
-               torch=lambda k: [eager.step(actions[i & 15]) for i in range(k)],
-               fused=lambda k: [fused.step(actions[i & 15]) for i in range(k)])
+def alternate(run, window, windows, preroll, per_call=1):
+    """run: {name: fn(k), k calls}.  `preroll` calls of each, then `windows` rounds of one timed window of `window` calls per runner,
+    the order rotating by one per round.  Returns the first keys of every result: policy-steps/s (`per_call` steps a call) as
+    medians and window by window, and the medians as microseconds per policy step"""
     for fn in run.values():
         fn(preroll)
     torch.cuda.synchronize()
     res = {k: [] for k in run}
     order = list(run)
     for w in range(windows):
-        for mode in order[w % 3:] + order[:w % 3]:
+        first = w % len(order)
+        for name in order[first:] + order[:first]:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            run[mode](window)
+            run[name](window)
             torch.cuda.synchronize()
-            res[mode].append(window / (time.perf_counter() - t0))
+            res[name].append(window * per_call / (time.perf_counter() - t0))
     med = {k: float(np.median(v)) for k, v in res.items()}
-    us = {k: 1e6 / v for k, v in med.items()}
-    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
-                us_per_policy_step=us, fused_overhead_over_sim_us=us["fused"] - us["sim"], torch_overhead_over_sim_us=us["torch"] - us["sim"],
+    return dict(policy_steps_per_s_median=med, all=res, us_per_policy_step={k: 1e6 / v for k, v in med.items()})
+
+
+def delays(n):
+    return (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+
+
+def stepper(env, n, na):
+    """fn(k): k steps of env under 16 small random actions in turn (the same 16 for every env)"""
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, na, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    return lambda k: [env.step(actions[i & 15]) for i in range(k)]
+
+
+def report(out_path, **out):
+    """the result as JSON, printed and written to out_path"""
+    text = json.dumps(dict(device=torch.cuda.get_device_name(0), dtype="f64", **out), indent=1)
+    print(text)
+    with open(out_path, "w") as f:
+        f.write(text + "\n")
+
+
+def measure(n, decimation, window=300, windows=4, preroll=60):
+    delay = delays(n)
+    fused = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW)
+    eager = TorchEnv(n, decimation, delay)
+    bare_conf = RobotConfig()
+    bare_conf.reference_quirks = False
+    bare = WalkController(bare_conf, num_envs=n, device="cuda:0")
+    bare.set_ctrl(bare.ctrl_from_q(bare.q0).expand(n, -1).contiguous(), "position")
+    r = alternate(dict(sim=lambda k: [bare.sim_steps(decimation) for _ in range(k)], torch=stepper(eager, n, fused.NA),
+                       fused=stepper(fused, n, fused.NA)), window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, **r, fused_overhead_over_sim_us=us["fused"] - us["sim"], torch_overhead_over_sim_us=us["torch"] - us["sim"],
                 fused_vs_torch=med["fused"] / med["torch"], restarts_fused=int(fused.episode.sum()) - n, restarts_torch=int(eager.episode.sum()),
                 standing_height_min=float(fused.wc.qpos[:, 2].min()))
 
@@ -179,29 +202,12 @@ RANDOMIZATION = dict(seed=1, reset_joint_pos=0.05, reset_joint_vel=0.2, reset_ba
 
 def measure_randomize(n, decimation, window=300, windows=4, preroll=60):
     """(c) with everything on against (c) with everything off: policy-steps/s in alternating windows of one process"""
-    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    delay = delays(n)
     envs = dict(off=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW),
                 on=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, randomization=RANDOMIZATION, **KW))
-    g = torch.Generator(device="cuda:0").manual_seed(1)
-    actions = [(torch.rand(n, envs["on"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
-    for env in envs.values():
-        for i in range(preroll):
-            env.step(actions[i & 15])
-    torch.cuda.synchronize()
-    res = {k: [] for k in envs}
-    for w in range(windows):
-        for mode in (("off", "on"), ("on", "off"))[w & 1]:
-            env = envs[mode]
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(window):
-                env.step(actions[i & 15])
-            torch.cuda.synchronize()
-            res[mode].append(window / (time.perf_counter() - t0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    us = {k: 1e6 / v for k, v in med.items()}
-    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
-                us_per_policy_step=us, on_over_off=med["on"] / med["off"], randomisation_us_per_policy_step=us["on"] - us["off"],
+    r = alternate({k: stepper(e, n, e.NA) for k, e in envs.items()}, window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, **r, on_over_off=med["on"] / med["off"], randomisation_us_per_policy_step=us["on"] - us["off"],
                 restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
                 standing_height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
 
@@ -213,31 +219,14 @@ TERRAIN = dict(seed=1, mass=(0.98, 1.02), friction=(0.4, 1.0), tilt_deg=5.0, ste
 def measure_terrain(n, decimation, window=300, windows=4, preroll=60):
     """host: tables drawn once with wc.randomize() (what the library offered before); device: PolicyEnv(terrain=TERRAIN).
     Policy-steps/s in alternating windows of one process"""
-    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    delay = delays(n)
     envs = dict(host=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **KW),
                 device=PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, terrain=TERRAIN, **KW))
     envs["host"].wc.randomize(seed=1, mass=TERRAIN["mass"], friction=TERRAIN["friction"], tilt_deg=TERRAIN["tilt_deg"],
                               step_height=TERRAIN["step_height"][1], step_length=TERRAIN["step_length"])
-    g = torch.Generator(device="cuda:0").manual_seed(1)
-    actions = [(torch.rand(n, envs["device"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
-    for env in envs.values():
-        for i in range(preroll):
-            env.step(actions[i & 15])
-    torch.cuda.synchronize()
-    res = {k: [] for k in envs}
-    for w in range(windows):
-        for mode in (("host", "device"), ("device", "host"))[w & 1]:
-            env = envs[mode]
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(window):
-                env.step(actions[i & 15])
-            torch.cuda.synchronize()
-            res[mode].append(window / (time.perf_counter() - t0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    us = {k: 1e6 / v for k, v in med.items()}
-    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med, all=res,
-                us_per_policy_step=us, device_over_host=med["device"] / med["host"], terrain_us_per_policy_step=us["device"] - us["host"],
+    r = alternate({k: stepper(e, n, e.NA) for k, e in envs.items()}, window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, **r, device_over_host=med["device"] / med["host"], terrain_us_per_policy_step=us["device"] - us["host"],
                 restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()},
                 scan_min_max=[float(envs["device"].height_scan.min()), float(envs["device"].height_scan.max())])
@@ -260,7 +249,7 @@ def measure_tsid(n, tsid, mode, decimation=4, window=100, windows=4, preroll=20)
     """policy-steps/s of hand (the closed loop alone), tsid (PolicyEnv with TSID in the loop), noteacher (that without the two
     new launches) and bare (tsid=None, position mode: tsidb_sim_ctrl only), in alternating windows of one process"""
     from tsid_control_amd.walk_planner import WalkSchedule, op3_closed_loop_walking_conf, op3_walking_posture
-    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    delay = delays(n)
 
     def conf():
         c = op3_closed_loop_walking_conf(RobotConfig()) if tsid == "walk" else RobotConfig()
@@ -286,27 +275,10 @@ def measure_tsid(n, tsid, mode, decimation=4, window=100, windows=4, preroll=20)
                 clock.add_(dt)
     else:
         hand_step = lambda: hand.step(decimation)
-    g = torch.Generator(device="cuda:0").manual_seed(1)
-    actions = [(torch.rand(n, hand.NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
-    run = dict(hand=lambda k: [hand_step() for _ in range(k)])
-    for name, env in envs.items():
-        run[name] = lambda k, env=env: [env.step(actions[i & 15]) for i in range(k)]
-    for fn in run.values():
-        fn(preroll)
-    torch.cuda.synchronize()
-    res = {k: [] for k in run}
-    order = list(run)
-    for w in range(windows):
-        for name in order[w % 4:] + order[:w % 4]:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            run[name](window)
-            torch.cuda.synchronize()
-            res[name].append(window / (time.perf_counter() - t0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    us = {k: 1e6 / v for k, v in med.items()}
-    return dict(envs=n, tsid=tsid, mode=mode, decimation=decimation, window_policy_steps=window, windows=windows, policy_steps_per_s_median=med,
-                all=res, us_per_policy_step=us, tsid_over_hand=med["tsid"] / med["hand"], tsid_over_bare=med["tsid"] / med["bare"],
+    r = alternate(dict(hand=lambda k: [hand_step() for _ in range(k)], **{k: stepper(e, n, hand.NA) for k, e in envs.items()}),
+                  window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    return dict(envs=n, tsid=tsid, mode=mode, decimation=decimation, window_policy_steps=window, windows=windows, **r, tsid_over_hand=med["tsid"] / med["hand"], tsid_over_bare=med["tsid"] / med["bare"],
                 policy_layer_us_per_policy_step=us["tsid"] - us["hand"], teacher_launches_us_per_policy_step=us["tsid"] - us["noteacher"],
                 restarts={k: int(e.episode.sum()) - n for k, e in envs.items()}, failed_qp_hand=int((hand.status != 0).sum()),
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
@@ -365,7 +337,7 @@ def captured(fn):
 def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll=3):
     """policy-steps/s of 16-step rollouts: fused / torch, each eager and graph-captured, in alternating windows of one process"""
     from tsid_control_amd import PolicyActor, RolloutStorage
-    delay = (torch.arange(n, dtype=torch.int32, device="cuda:0") % 3).contiguous()
+    delay = delays(n)
     kw = dict(KW, action_scale=0.05, terrain=TERRAIN) if scan else dict(KW, action_scale=0.05)
     run, envs = {}, {}
     for name in ("fused", "fused_graph", "torch", "torch_graph"):
@@ -378,26 +350,12 @@ def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll
         else:
             ta = TorchActor(env, actor, critic, ai, ci, ls)
             fn = lambda ta=ta, st=st: ta.rollout(steps, st)
-        run[name] = captured(fn) if name.endswith("graph") else fn
-    for fn in run.values():
-        for _ in range(preroll):
-            fn()
-    torch.cuda.synchronize()
-    res = {k: [] for k in run}
-    order = list(run)
-    for w in range(windows):
-        for name in order[w % 4:] + order[:w % 4]:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(window):
-                run[name]()
-            torch.cuda.synchronize()
-            res[name].append(window * steps / (time.perf_counter() - t0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    us = {k: 1e6 / v for k, v in med.items()}
+        fn = captured(fn) if name.endswith("graph") else fn
+        run[name] = lambda k, fn=fn: [fn() for _ in range(k)]
+    r = alternate(run, window, windows, preroll, per_call=steps)
+    med = r["policy_steps_per_s_median"]
     return dict(envs=n, actor_input="obs | height_scan" if scan else "obs", decimation=decimation, rollout_steps=steps, window_rollouts=window,
-                windows=windows, policy_steps_per_s_median=med, all=res, us_per_policy_step=us,
-                fused_over_torch=med["fused"] / med["torch"], fused_graph_over_torch_graph=med["fused_graph"] / med["torch_graph"],
+                windows=windows, **r, fused_over_torch=med["fused"] / med["torch"], fused_graph_over_torch_graph=med["fused_graph"] / med["torch_graph"],
                 fused_over_torch_graph=med["fused"] / med["torch_graph"],
                 restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
@@ -424,12 +382,7 @@ if __name__ == "__main__":
             for scan in ("obs", "scan"):
                 r = subprocess.run([sys.executable, sys.argv[0], "--actor", "--case", str(n), scan], capture_output=True, text=True, check=True)
                 runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
-        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", actor="K -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU",
-                   runs=runs)
-        text = json.dumps(out, indent=1)
-        print(text)
-        with open(out_path, "w") as f:
-            f.write(text + "\n")
+        report(out_path, actor="K -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU", runs=runs)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--tsid":
         import os
@@ -438,15 +391,12 @@ if __name__ == "__main__":
         if rest and rest[0] == "--mode":
             mode, rest = rest[1], rest[2:]
         out_path = rest[0] if rest else "profiles/policy_tsid.json"
-        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", runs={})
+        runs = {}
         if os.path.exists(out_path):
             with open(out_path) as f:
-                out["runs"] = json.load(f).get("runs", {})
-        out["runs"][f"{tsid}/{mode}"] = [measure_tsid(n, tsid, mode) for n in (4096, 512)]
-        text = json.dumps(out, indent=1)
-        print(text)
-        with open(out_path, "w") as f:
-            f.write(text + "\n")
+                runs = json.load(f).get("runs", {})
+        runs[f"{tsid}/{mode}"] = [measure_tsid(n, tsid, mode) for n in (4096, 512)]
+        report(out_path, runs=runs)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--terrain":
         if len(sys.argv) > 2 and sys.argv[2] == "--trace":
@@ -458,21 +408,11 @@ if __name__ == "__main__":
             torch.cuda.synchronize()
             sys.exit(0)
         out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_terrain.json"
-        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", terrain=TERRAIN,
-                   runs=[measure_terrain(n, d) for n in (4096, 512) for d in (4, 10)])
-        text = json.dumps(out, indent=1)
-        print(text)
-        with open(out_path, "w") as f:
-            f.write(text + "\n")
+        report(out_path, terrain=TERRAIN, runs=[measure_terrain(n, d) for n in (4096, 512) for d in (4, 10)])
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--randomize":
         out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_dr.json"
-        out = dict(device=torch.cuda.get_device_name(0), dtype="f64", randomization=RANDOMIZATION,
-                   runs=[measure_randomize(n, d) for n in (4096, 512) for d in (4, 10)])
-        text = json.dumps(out, indent=1)
-        print(text)
-        with open(out_path, "w") as f:
-            f.write(text + "\n")
+        report(out_path, randomization=RANDOMIZATION, runs=[measure_randomize(n, d) for n in (4096, 512) for d in (4, 10)])
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--trace":
         n, k = int(sys.argv[2]), int(sys.argv[3])
@@ -483,9 +423,4 @@ if __name__ == "__main__":
         torch.cuda.synchronize()
         sys.exit(0)
     out_path = sys.argv[1] if len(sys.argv) > 1 else "profiles/policy_env.json"
-    out = dict(device=torch.cuda.get_device_name(0), dtype="f64",
-               runs=[measure(n, d) for n in (4096, 512) for d in (4, 10)])
-    text = json.dumps(out, indent=1)
-    print(text)
-    with open(out_path, "w") as f:
-        f.write(text + "\n")
+    report(out_path, runs=[measure(n, d) for n in (4096, 512) for d in (4, 10)])

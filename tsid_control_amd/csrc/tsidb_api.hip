@@ -1241,7 +1241,44 @@ static PolicyRefs<T> policy_teacher_refs(const tsidb_ctx *h, const char *who) {
   return PolicyRefs<T>{(const T *)h->com_ref, (const T *)h->foot_ref, h->contact_active};
 }
 
-static dim3 policy_grid(const tsidb_ctx *h) { return dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK); }
+static PolicyTeach policy_teach(const tsidb_ctx *h) {
+  PolicyTeach tc;
+  tc.sigma_com = h->teach[TSIDB_POL_TEACH_SIGMA_COM]; tc.sigma_foot = h->teach[TSIDB_POL_TEACH_SIGMA_FOOT];
+  for (int k = 0; k < POL_TEACH_NT; k++) tc.w[k] = h->teach[TSIDB_POL_TEACH_WEIGHTS + k];
+  tc.w_termination = h->pol[TSIDB_POL_P_WEIGHTS + POL_T_TERMINATION]; tc.clip = h->pol[TSIDB_POL_P_CLIP];
+  for (int a = 0; a < NA; a++) { tc.scale[a] = h->pol_scale[a]; tc.def[a] = h->pol_def[a]; }
+  tc.ctrl_mode = h->ctrl_mode;
+  return tc;
+}
+
+// the controller's rows a launch reads (or, the teacher, writes): `what` says which for the message
+static void need_rows(const char *who, const void *rows, int ld, const char *what = "tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)") {
+  if (!rows || ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows " + what;
+}
+
+// true if every p[i], i in slots, is a whole number in [0, bound)
+static bool whole_below(const double *p, std::initializer_list<int> slots, double bound = INFINITY) {
+  for (int i : slots) if (!(p[i] >= 0 && p[i] == std::floor(p[i]) && p[i] < bound)) return false;
+  return true;
+}
+
+// The frame of every tsidb_policy_* launch: the guard, the path's type T, what policy_bufs checks, then body(T(), b, launch)
+// with the entry's own checks.  launch(kernel, args...) puts the kernel on the stream with the policy grid and block; a body
+// that returns without calling it launches nothing.
+template <typename Body>
+static int policy_call(tsidb_ctx *h, const tsidb_policy_bufs *bufs, const char *who, void *stream, Body body) {
+  GUARD_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    const auto b = policy_bufs<decltype(t)>(h, bufs, who);
+    body(t, b, [&](auto kernel, auto... args) {
+      h->note_stream(s);
+      hipLaunchKernelGGL(kernel, dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, args...);
+    });
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
 
 extern "C" {
 
@@ -1271,52 +1308,34 @@ int tsidb_policy_config(tsidb_handle h, const double *pol_params, int n_params, 
 }
 
 int tsidb_policy_act(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *action, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  return policy_call(h, bufs, "tsidb_policy_act: ", stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_act: ");
     if (!action) throw std::string("tsidb_policy_act: null action");
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_act<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, policy_cfg<T>(h), b, (const T *)action, (T *)h->ctrl);
+    launch(k_policy_act<T>, h->num_envs, policy_cfg<T>(h), b, (const T *)action, (T *)h->ctrl);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_reward(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, const void *qvel, const int32_t *ncon,
                         const int32_t *con_pairs, const int32_t *info, void *reward, void *done, int row_ld, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  return policy_call(h, bufs, "tsidb_policy_reward: ", stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_reward: ");
     if (!qpos || !qvel || !ncon || !con_pairs || !info || !reward || !done || row_ld < 1) throw std::string("tsidb_policy_reward: null buffer or row stride < 1");
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_reward<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
-                       policy_cfg<T>(h), b, (const T *)qpos, (const T *)qvel, ncon, con_pairs, info, (const T *)h->ro[3], (T *)reward, (T *)done, row_ld);
+    launch(k_policy_reward<T>, (const DevModel<T> *)h->d_model, h->num_envs, policy_cfg<T>(h), b, (const T *)qpos, (const T *)qvel, ncon, con_pairs,
+           info, (const T *)h->ro[3], (T *)reward, (T *)done, row_ld);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
                      const void *qvel, const int32_t *ncon, const int32_t *con_pairs, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_obs: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_obs: ");
-    if (!done_rows || rows_ld < NROW) throw std::string("tsidb_policy_obs: needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)");
-    if (!qpos || !qvel || !ncon || !con_pairs) throw std::string("tsidb_policy_obs: null buffer");
-    h->note_stream(s);
-    const auto kern = dr_obs_on(h) ? &k_policy_obs<T, true> : &k_policy_obs<T, false>;   // (off: the unrandomised kernel, bit for bit)
-    hipLaunchKernelGGL(kern, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s,
-                       (const DevModel<T> *)h->d_model, h->num_envs, policy_cfg<T>(h), b, (const T *)done_rows, rows_ld, (const T *)qpos,
-                       (const T *)qvel, ncon, con_pairs, (T *)h->ctrl, policy_dr(h));
+    need_rows(who, done_rows, rows_ld);
+    if (!qpos || !qvel || !ncon || !con_pairs) throw std::string(who) + "null buffer";
+    launch(dr_obs_on(h) ? &k_policy_obs<T, true> : &k_policy_obs<T, false>,   // (off: the unrandomised kernel, bit for bit)
+           (const DevModel<T> *)h->d_model, h->num_envs, policy_cfg<T>(h), b, (const T *)done_rows, rows_ld, (const T *)qpos, (const T *)qvel, ncon,
+           con_pairs, (T *)h->ctrl, policy_dr(h));
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params) {
@@ -1331,10 +1350,10 @@ int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params
       if (dr_params[i] < 0) throw std::string(who) + "negative parameter (amplitudes, forces, intervals, seed, offset and probability are all >= 0)";
       p[i] = dr_params[i];
     }
-    for (int i : {(int)TSIDB_POL_DR_SEED, (int)TSIDB_POL_DR_ENV_OFFSET, (int)TSIDB_POL_DR_PUSH_INTERVAL, (int)TSIDB_POL_DR_PUSH_DURATION, (int)TSIDB_POL_DR_COMMAND_INTERVAL})
-      if (p[i] != std::floor(p[i])) throw std::string(who) + "seed, env_offset and the intervals must be whole numbers";
-    if (p[TSIDB_POL_DR_SEED] >= 4294967296.0) throw std::string(who) + "seed must be below 2^32";
-    if (p[TSIDB_POL_DR_ENV_OFFSET] >= 2147483648.0 || p[TSIDB_POL_DR_PUSH_INTERVAL] >= 2147483648.0 || p[TSIDB_POL_DR_COMMAND_INTERVAL] >= 2147483648.0)
+    if (!whole_below(p, {TSIDB_POL_DR_SEED, TSIDB_POL_DR_ENV_OFFSET, TSIDB_POL_DR_PUSH_INTERVAL, TSIDB_POL_DR_PUSH_DURATION, TSIDB_POL_DR_COMMAND_INTERVAL}))
+      throw std::string(who) + "seed, env_offset and the intervals must be whole numbers";
+    if (!whole_below(p, {TSIDB_POL_DR_SEED}, 4294967296.0)) throw std::string(who) + "seed must be below 2^32";
+    if (!whole_below(p, {TSIDB_POL_DR_ENV_OFFSET, TSIDB_POL_DR_PUSH_INTERVAL, TSIDB_POL_DR_COMMAND_INTERVAL}, 2147483648.0))
       throw std::string(who) + "env_offset and the intervals must be below 2^31";
     if (p[TSIDB_POL_DR_PUSH_DURATION] > p[TSIDB_POL_DR_PUSH_INTERVAL]) throw std::string(who) + "push_duration > push_interval";
     if (p[TSIDB_POL_DR_PUSH_FORCE_LO] > p[TSIDB_POL_DR_PUSH_FORCE_HI]) throw std::string(who) + "push_force_lo > push_force_hi";
@@ -1346,36 +1365,24 @@ int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params
 }
 
 int tsidb_policy_perturb(tsidb_handle h, const tsidb_policy_bufs *bufs, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  return policy_call(h, bufs, "tsidb_policy_perturb: ", stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_perturb: ");
     if (!dr_push_on(h)) return;
     if (!h->xfrc) throw std::string("tsidb_policy_perturb: no xfrc buffer registered (call tsidb_set_xfrc first)");
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_perturb<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, policy_dr(h), (T *)h->xfrc);
+    launch(k_policy_perturb<T>, h->num_envs, b, policy_dr(h), (T *)h->xfrc);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, void *qpos, void *qvel,
                              void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_reset_noise: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, "tsidb_policy_reset_noise: ");
-    if (!done_rows || rows_ld < NROW) throw std::string("tsidb_policy_reset_noise: needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)");
-    if (!qpos || !qvel) throw std::string("tsidb_policy_reset_noise: null buffer");
+    need_rows(who, done_rows, rows_ld);
+    if (!qpos || !qvel) throw std::string(who) + "null buffer";
     if (!dr_reset_on(h)) return;
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_reset_noise<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, b,
-                       policy_dr(h), (const T *)done_rows, rows_ld, (T *)qpos, (T *)qvel);
+    launch(k_policy_reset_noise<T>, (const DevModel<T> *)h->d_model, h->num_envs, b, policy_dr(h), (const T *)done_rows, rows_ld, (T *)qpos, (T *)qvel);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_params) {
@@ -1390,11 +1397,10 @@ int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_
       if (!std::isfinite(ter_params[i])) throw std::string(who) + "non-finite parameter";
       p[i] = ter_params[i];
     }
-    for (int i : {(int)TSIDB_POL_TER_SEED, (int)TSIDB_POL_TER_ENV_OFFSET, (int)TSIDB_POL_TER_FLAT_CELLS, (int)TSIDB_POL_TER_NUM_LEVELS, (int)TSIDB_POL_TER_SCAN_NX,
-                  (int)TSIDB_POL_TER_SCAN_NY})
-      if (p[i] != std::floor(p[i]) || p[i] < 0) throw std::string(who) + "seed, env_offset, flat_cells, num_levels, scan_nx and scan_ny must be whole numbers >= 0";
-    if (p[TSIDB_POL_TER_SEED] >= 4294967296.0) throw std::string(who) + "seed must be below 2^32";
-    if (p[TSIDB_POL_TER_ENV_OFFSET] >= 2147483648.0) throw std::string(who) + "env_offset must be below 2^31";
+    if (!whole_below(p, {TSIDB_POL_TER_SEED, TSIDB_POL_TER_ENV_OFFSET, TSIDB_POL_TER_FLAT_CELLS, TSIDB_POL_TER_NUM_LEVELS, TSIDB_POL_TER_SCAN_NX, TSIDB_POL_TER_SCAN_NY}))
+      throw std::string(who) + "seed, env_offset, flat_cells, num_levels, scan_nx and scan_ny must be whole numbers >= 0";
+    if (!whole_below(p, {TSIDB_POL_TER_SEED}, 4294967296.0)) throw std::string(who) + "seed must be below 2^32";
+    if (!whole_below(p, {TSIDB_POL_TER_ENV_OFFSET}, 2147483648.0)) throw std::string(who) + "env_offset must be below 2^31";
     for (int i : {(int)TSIDB_POL_TER_MASS_LO, (int)TSIDB_POL_TER_FRICTION_LO, (int)TSIDB_POL_TER_STEP_HEIGHT_LO, (int)TSIDB_POL_TER_STEP_LENGTH_LO})
       if (p[i] > p[i + 1]) throw std::string(who) + "range: lo > hi (mass, friction, step_height, step_length)";
     if (!(p[TSIDB_POL_TER_MASS_LO] > 0) || !(p[TSIDB_POL_TER_FRICTION_LO] > 0)) throw std::string(who) + "mass and friction must be positive";
@@ -1418,43 +1424,29 @@ int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_
 
 int tsidb_policy_terrain_reset(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
                                const int32_t *level, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_terrain_reset: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const char *who = "tsidb_policy_terrain_reset: ";
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
     if (!h->ter_set) throw std::string(who) + "not configured (call tsidb_policy_terrain_config first)";
     if (!h->env_params || !h->terrain) throw std::string(who) + "needs both the env_params and the terrain table registered (call tsidb_set_env_params first)";
-    if (!done_rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)";
+    need_rows(who, done_rows, rows_ld);
     if (!qpos) throw std::string(who) + "null buffer";
-    h->note_stream(s);
     // (the tables are the caller's device buffers, registered read-only for the sim: this launch is their one writer)
-    hipLaunchKernelGGL(k_policy_terrain_reset<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, policy_ter(h),
-                       (const T *)done_rows, rows_ld, (const T *)qpos, level, (T *)const_cast<void *>(h->env_params),
-                       (T *)const_cast<void *>(h->terrain));
+    launch(k_policy_terrain_reset<T>, h->num_envs, b, policy_ter(h), (const T *)done_rows, rows_ld, (const T *)qpos, level,
+           (T *)const_cast<void *>(h->env_params), (T *)const_cast<void *>(h->terrain));
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_height_scan(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *qpos, void *scan, int scan_ld, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_height_scan: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const char *who = "tsidb_policy_height_scan: ";
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
     const PolicyTer d = policy_ter(h);
     if (d.nx * d.ny == 0) return;   // (also before tsidb_policy_terrain_config)
     if (!qpos || !scan) throw std::string(who) + "null buffer";
     if (scan_ld < d.nx * d.ny) throw std::string(who) + "scan row stride must be at least scan_nx * scan_ny";
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_height_scan<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, h->num_envs, b, d, (const T *)qpos,
-                       (const T *)h->env_params, (const T *)h->terrain, (T *)scan, scan_ld);
+    launch(k_policy_height_scan<T>, h->num_envs, b, d, (const T *)qpos, (const T *)h->env_params, (const T *)h->terrain, (T *)scan, scan_ld);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_teacher_config(tsidb_handle h, const double *teach_params, int n_params) {
@@ -1473,48 +1465,29 @@ int tsidb_policy_teacher_config(tsidb_handle h, const double *teach_params, int 
 int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *rows, int rows_ld, const void *q, const void *tau,
                          const int32_t *status, const int32_t *ncon, const int32_t *con_pairs, void *teacher_terms, void *teacher_action,
                          void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_teacher: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
     using T = decltype(t);
-    const char *who = "tsidb_policy_teacher: ";
-    const PolicyBufs<T> b = policy_bufs<T>(h, bufs, who);
     const PolicyRefs<T> r = policy_teacher_refs<T>(h, who);
-    if (!rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows of the last tick (reward and done in columns TSIDB_NOBS, TSIDB_NOBS + 1)";
+    need_rows(who, rows, rows_ld, "of the last tick (reward and done in columns TSIDB_NOBS, TSIDB_NOBS + 1)");
     if (!q || !tau || !status || !ncon || !con_pairs || !teacher_terms || !teacher_action) throw std::string(who) + "null buffer";
-    PolicyTeach tc;
-    tc.sigma_com = h->teach[TSIDB_POL_TEACH_SIGMA_COM]; tc.sigma_foot = h->teach[TSIDB_POL_TEACH_SIGMA_FOOT];
-    for (int k = 0; k < POL_TEACH_NT; k++) tc.w[k] = h->teach[TSIDB_POL_TEACH_WEIGHTS + k];
-    tc.w_termination = h->pol[TSIDB_POL_P_WEIGHTS + POL_T_TERMINATION]; tc.clip = h->pol[TSIDB_POL_P_CLIP];
-    for (int a = 0; a < NA; a++) { tc.scale[a] = h->pol_scale[a]; tc.def[a] = h->pol_def[a]; }
-    tc.ctrl_mode = h->ctrl_mode;
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_teacher<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs,
-                       policy_cfg<T>(h), tc, b, r, (T *)rows, rows_ld, (const T *)q, (const T *)tau, status, ncon, con_pairs, (const T *)h->ctrl,
-                       (T *)teacher_terms, (T *)teacher_action);
+    launch(k_policy_teacher<T>, (const DevModel<T> *)h->d_model, h->num_envs, policy_cfg<T>(h), policy_teach(h), b, r, (T *)rows, rows_ld, (const T *)q,
+           (const T *)tau, status, ncon, con_pairs, (const T *)h->ctrl, (T *)teacher_terms, (T *)teacher_action);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *rows, int rows_ld, const void *qpos, const void *tau,
                              void *teacher_obs, int obs_ld, void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
+  const char *who = "tsidb_policy_teacher_obs: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &, auto launch) {
     using T = decltype(t);
-    const char *who = "tsidb_policy_teacher_obs: ";
-    policy_bufs<T>(h, bufs, who);
     const PolicyRefs<T> r = policy_teacher_refs<T>(h, who);
-    if (!rows || rows_ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)";
+    need_rows(who, rows, rows_ld);
     if (!qpos || !tau || !teacher_obs) throw std::string(who) + "null buffer";
     if (obs_ld < POL_TEACH_NOBS) throw std::string(who) + "teacher_obs row stride must be at least 14 + NA";
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_teacher_obs<T>, policy_grid(h), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, (const DevModel<T> *)h->d_model, h->num_envs, r,
-                       (const T *)rows, rows_ld, (const T *)qpos, (const T *)tau, (T *)teacher_obs, obs_ld);
+    launch(k_policy_teacher_obs<T>, (const DevModel<T> *)h->d_model, h->num_envs, r, (const T *)rows, rows_ld, (const T *)qpos, (const T *)tau,
+           (T *)teacher_obs, obs_ld);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 } // extern "C"

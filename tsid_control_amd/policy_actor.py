@@ -10,11 +10,11 @@ state, a captured rollout replays, a batch split over ranks samples what the uns
 the same observation return the same sample.
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import _lib
+from .policy_env import _whole_below
 
 _INPUT_NAMES = ("obs", "priv", "height_scan", "teacher_obs", "command")
 
@@ -151,10 +151,7 @@ class PolicyActor:
         if env_offset is None:
             dr = getattr(env, "dr_params", None)
             env_offset = int(dr[_lib.POL_DR_ENV_OFFSET]) if dr is not None else 0
-        for k, v, bits in (("seed", seed, 32), ("env_offset", env_offset, 31)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != math.floor(v) or not 0 <= v < 2 ** bits:
-                raise _bad(f"{k} must be a whole number in [0, 2^{bits}), got {v!r}")
-        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.seed, self.env_offset = _whole_below("PolicyActor", "seed", seed, 32), _whole_below("PolicyActor", "env_offset", env_offset, 31)
         self.action = torch.zeros(N, NA, dtype=wc.dtype, device=wc.device)
         self.action32, self.mean, self.logp = f32(N, NA), f32(N, NA), f32(N)
         self.value = f32(N) if critic is not None else None

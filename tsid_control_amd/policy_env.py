@@ -37,6 +37,34 @@ from . import _lib
 from .walk_controller import WalkController, _ptr
 
 
+def _of(cls, r, what, fields):
+    """r as a cls: one, or a dict of its fields (`what`: the PolicyEnv argument, for the messages)"""
+    if isinstance(r, cls):
+        return r
+    if not isinstance(r, dict):
+        raise _lib.TsidbError(f"PolicyEnv: {what} must be a {cls.__name__} or a dict, got {type(r).__name__}")
+    unknown = sorted(set(r) - set(fields))
+    if unknown:
+        raise _lib.TsidbError(f"PolicyEnv: unknown {what} fields {unknown} (known: {fields})")
+    return cls(**r)
+
+
+def _weight_vector(weights, terms, what):
+    """{term: weight} as the weights in the order of `terms`, 0 for a term left out"""
+    weights = dict(weights or {})
+    unknown = sorted(set(weights) - set(terms))
+    if unknown:
+        raise _lib.TsidbError(f"PolicyEnv: unknown {what} terms {unknown} (known: {terms})")
+    return [weights.get(k, 0.0) for k in terms]
+
+
+def _whole_below(who, name, v, bits):
+    """v as an int if it is a finite whole number in [0, 2^bits) - what the library asks of seeds, offsets, intervals and counts"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v != math.floor(v) or not 0 <= v < 2 ** bits:
+        raise _lib.TsidbError(f"{who}: {name} must be a whole number in [0, 2^{bits}), got {v!r}")
+    return int(v)
+
+
 @dataclasses.dataclass
 class PolicyRandomization:
     """Per-episode and per-step randomisation of a PolicyEnv (include/tsidb.h TSIDB_POL_DR_*); every value defaults to 0 = off.
@@ -72,22 +100,13 @@ class PolicyRandomization:
     @classmethod
     def of(cls, r):
         """r as a PolicyRandomization: one, or a dict of its fields"""
-        if isinstance(r, cls):
-            return r
-        if not isinstance(r, dict):
-            raise _lib.TsidbError(f"PolicyEnv: randomization must be a PolicyRandomization or a dict, got {type(r).__name__}")
-        unknown = sorted(set(r) - set(_lib.POL_DR_FIELDS))
-        if unknown:
-            raise _lib.TsidbError(f"PolicyEnv: unknown randomization fields {unknown} (known: {_lib.POL_DR_FIELDS})")
-        return cls(**r)
+        return _of(cls, r, "randomization", _lib.POL_DR_FIELDS)
 
     def params(self, default_seed=0):
         """the float64 vector tsidb_policy_randomize takes, checked as the library checks it"""
         p = np.zeros(_lib.POL_DR_NPARAMS)
         for k in _lib.POL_DR_FIELDS:
-            v = getattr(self, k)
-            if k == "seed" and v is None:
-                v = default_seed
+            v = default_seed if k == "seed" and self.seed is None else getattr(self, k)
             i = getattr(_lib, "POL_DR_" + k.upper())
             try:
                 if k in ("reset_base_lin_vel", "reset_base_ang_vel"):
@@ -102,9 +121,7 @@ class PolicyRandomization:
         if (p < 0).any():
             raise bad("negative value: amplitudes, forces, intervals, seed, offset and probability are all >= 0")
         for k in ("seed", "env_offset", "push_interval", "push_duration", "command_interval"):
-            i = getattr(_lib, "POL_DR_" + k.upper())
-            if p[i] != math.floor(p[i]) or p[i] >= 2.0 ** (32 if k == "seed" else 31):
-                raise bad(f"{k} must be a whole number below 2^{32 if k == 'seed' else 31}, got {p[i]}")
+            _whole_below("PolicyRandomization", k, p[getattr(_lib, "POL_DR_" + k.upper())], 32 if k == "seed" else 31)
         if p[_lib.POL_DR_PUSH_DURATION] > p[_lib.POL_DR_PUSH_INTERVAL]:
             raise bad("push_duration > push_interval")
         if p[_lib.POL_DR_PUSH_FORCE_LO] > p[_lib.POL_DR_PUSH_FORCE_HI]:
@@ -145,14 +162,7 @@ class PolicyTerrain:
     @classmethod
     def of(cls, t):
         """t as a PolicyTerrain: one, or a dict of its fields"""
-        if isinstance(t, cls):
-            return t
-        if not isinstance(t, dict):
-            raise _lib.TsidbError(f"PolicyEnv: terrain must be a PolicyTerrain or a dict, got {type(t).__name__}")
-        unknown = sorted(set(t) - set(_lib.POL_TER_FIELDS))
-        if unknown:
-            raise _lib.TsidbError(f"PolicyEnv: unknown terrain fields {unknown} (known: {_lib.POL_TER_FIELDS})")
-        return cls(**t)
+        return _of(cls, t, "terrain", _lib.POL_TER_FIELDS)
 
     def params(self, default_seed=0, default_env_offset=0):
         """the float64 vector tsidb_policy_terrain_config takes, checked as the library checks it"""
@@ -191,11 +201,7 @@ class PolicyTerrain:
         if not np.isfinite(p).all():
             raise bad("non-finite value")
         for k in ("seed", "env_offset", "flat_cells", "num_levels", "scan_nx", "scan_ny"):
-            v = p[getattr(_lib, "POL_TER_" + k.upper())]
-            if v != math.floor(v) or v < 0:
-                raise bad(f"{k} must be a whole number >= 0, got {v}")
-        if p[_lib.POL_TER_SEED] >= 2.0 ** 32 or p[_lib.POL_TER_ENV_OFFSET] >= 2.0 ** 31:
-            raise bad("seed must be below 2^32 and env_offset below 2^31")
+            _whole_below("PolicyTerrain", k, p[getattr(_lib, "POL_TER_" + k.upper())], 32 if k == "seed" else 31)
         for k, i in (("mass", _lib.POL_TER_MASS_LO), ("friction", _lib.POL_TER_FRICTION_LO), ("step_height", _lib.POL_TER_STEP_HEIGHT_LO),
                      ("step_length", _lib.POL_TER_STEP_LENGTH_LO), ("scan_clip", _lib.POL_TER_SCAN_CLIP_LO)):
             if p[i] > p[i + 1]:
@@ -211,7 +217,7 @@ class PolicyTerrain:
             raise bad("step_prob must be in [0, 1]")
         if p[_lib.POL_TER_FLAT_CELLS] > 7:
             raise bad("flat_cells must be 0 .. 7")
-        if not 1 <= p[_lib.POL_TER_NUM_LEVELS] < 2.0 ** 31:
+        if p[_lib.POL_TER_NUM_LEVELS] < 1:
             raise bad("num_levels must be a whole number >= 1 (below 2^31)")
         nx, ny = p[_lib.POL_TER_SCAN_NX], p[_lib.POL_TER_SCAN_NY]
         if (nx == 0) != (ny == 0):
@@ -285,15 +291,16 @@ class PolicyEnv:
         if mode not in ("position", "motor") and not (mode == "residual" and tsid is not None):
             raise _lib.TsidbError(f"PolicyEnv: mode must be 'position' or 'motor', or 'residual' with tsid = 'stand' / 'walk' "
                                   f"(a residual needs TSID's tau to add to), got {mode!r}")
-        dr = None
+        # the four parameter vectors: checked before anything is built
+        self.params = base = self._base_params(int(decimation), action_clip, filter_alpha, sigma, t_air, deadband, max_episode_steps, seed,
+                                               command_range, reward_weights)
+        dr = ter = teach = None
         if randomization is not None:
             self.randomization = PolicyRandomization.of(randomization)
-            dr = self.randomization.params(seed)      # (checked before anything is built)
-        ter = None
+            dr = self.randomization.params(seed)
         if terrain is not None:
             self.terrain = PolicyTerrain.of(terrain)
             ter = self.terrain.params(seed, 0 if dr is None else int(dr[_lib.POL_DR_ENV_OFFSET]))
-        teach = None
         if tsid is None:
             if walk is not None or teacher_weights:
                 raise _lib.TsidbError("PolicyEnv: walk and teacher_weights need tsid = 'stand' or 'walk'")
@@ -309,56 +316,48 @@ class PolicyEnv:
                 raise _lib.TsidbError(f"PolicyEnv: {', '.join(moved)} cannot be used with tsid: the walking plan and the contact "
                                       "references start from the base pose the reset captured (joint and velocity noise are fine: "
                                       "the closed-loop tick reads the sim state)")
+        # the controller
         self.wc = wc = WalkController(conf, num_envs=num_envs, device=device)
         self.num_envs, self.device, self.dtype, self.NA = wc.num_envs, wc.device, wc.dtype, wc.NA
         N, NA = wc.num_envs, wc.NA
         self.NOBS = _lib.pol_nobs(NA)
-        self.decimation, self.mode = int(decimation), mode
-        z = lambda *s, dt=wc.dtype: torch.zeros(*s, dtype=dt, device=wc.device)
-        wc.set_ctrl(z(N, NA), mode)
-        weights = dict(reward_weights or {})
-        unknown = sorted(set(weights) - set(_lib.POL_TERMS))
-        if unknown:
-            raise _lib.TsidbError(f"PolicyEnv: unknown reward terms {unknown} (known: {_lib.POL_TERMS})")
-        if weights.get("torques", 0.0) != 0.0:     # the readout kernels cost 3-4 %: only when the term is used
-            wc.enable_sim_readouts()
+        self.decimation, self.mode, self.tsid = int(decimation), mode, tsid
+        base[_lib.POL_P_H_TARGET] = float(wc.qpos[0, 2]) if h_target is None else h_target
         if default_joint_pos is None:
             default_joint_pos = wc.ctrl_from_q(wc.q0)[0].double().cpu().numpy() if mode == "position" else 0.0
         self.action_scale = np.broadcast_to(np.asarray(action_scale, dtype=np.float64), (NA,)).copy()
         self.default_joint_pos = np.broadcast_to(np.asarray(default_joint_pos, dtype=np.float64), (NA,)).copy()
         self.term_body_mask = 1 if term_bodies is None else sum(1 << int(b) for b in set(term_bodies))
-        p = np.zeros(_lib.POL_NPARAMS)
-        p[_lib.POL_P_CLIP], p[_lib.POL_P_ALPHA], p[_lib.POL_P_SIGMA] = action_clip, filter_alpha, sigma
-        p[_lib.POL_P_H_TARGET] = float(wc.qpos[0, 2]) if h_target is None else h_target
-        p[_lib.POL_P_T_AIR], p[_lib.POL_P_DEADBAND] = t_air, deadband
-        p[_lib.POL_P_MAX_EPISODE_STEPS], p[_lib.POL_P_DECIMATION], p[_lib.POL_P_SEED] = max_episode_steps, self.decimation, seed
-        rng = np.asarray(command_range, dtype=np.float64).reshape(3, 2)
-        p[_lib.POL_P_CMD_LO:_lib.POL_P_CMD_LO + 3], p[_lib.POL_P_CMD_HI:_lib.POL_P_CMD_HI + 3] = rng[:, 0], rng[:, 1]
-        for k, w in weights.items():
-            p[_lib.POL_P_WEIGHTS + _lib.POL_TERMS.index(k)] = w
-        self.params = p
-        vp = C.c_void_p
-        wc._call("tsidb_policy_config", p.ctypes.data_as(vp), _lib.POL_NPARAMS, self.action_scale.ctypes.data_as(vp),
-                 self.default_joint_pos.ctypes.data_as(vp), self.term_body_mask)
-
+        if delay is not None and (not isinstance(delay, torch.Tensor) or tuple(delay.shape) != (N,) or delay.dtype != torch.int32
+                                  or delay.device != wc.device or not delay.is_contiguous()):
+            raise _lib.TsidbError(f"PolicyEnv: delay must be a contiguous ({N},) int32 tensor on {wc.device}")
+        self.delay = delay
+        # the tensors
+        z = lambda *s, dt=wc.dtype: torch.zeros(*s, dtype=dt, device=wc.device)
         self.act_hist, self.last_action, self.prev_action = z(_lib.POL_HIST, N, NA), z(N, NA), z(N, NA)
         self.command, self.air_time, self.terms = z(N, 3), z(N, 2), z(N, _lib.POL_NT)
         self.ep_len, self.episode, self.timeout = z(N, dt=torch.int32), z(N, dt=torch.int32), z(N, dt=torch.int32)
-        self.command[:] = torch.as_tensor(rng[:, 0], dtype=wc.dtype, device=wc.device)
-        if delay is not None:
-            if not isinstance(delay, torch.Tensor) or tuple(delay.shape) != (N,) or delay.dtype != torch.int32 \
-                    or delay.device != wc.device or not delay.is_contiguous():
-                raise _lib.TsidbError(f"PolicyEnv: delay must be a contiguous ({N},) int32 tensor on {wc.device}")
-        self.delay = delay
+        self.command[:] = torch.as_tensor(base[_lib.POL_P_CMD_LO:_lib.POL_P_CMD_LO + 3], dtype=wc.dtype, device=wc.device)
         self._rows = z(N, self.NOBS + _lib.POL_NPRIV)
         self.obs, self.priv = self._rows[:, :self.NOBS], self._rows[:, self.NOBS:]
         self.reward, self.done = wc.reward, wc.done
         self._bufs = _lib.PolicyBufs(*(t.data_ptr() if t is not None else None for t in (
             self.act_hist, self.last_action, self.prev_action, self.command, self.air_time, self.ep_len, self.episode, self.delay,
             self.terms, self.timeout, self._rows)), self.NOBS + _lib.POL_NPRIV)
+        if ter is not None:
+            self.terrain_level, self.height_scan = z(N, dt=torch.int32), z(N, int(ter[_lib.POL_TER_SCAN_NX] * ter[_lib.POL_TER_SCAN_NY]))
+        if tsid is not None:
+            self.teacher_terms, self.teacher_action, self.teacher_obs = z(N, _lib.POL_TEACH_NT), z(N, NA), z(N, _lib.pol_teach_nobs(NA))
+        # the library's configuration, group by group
+        vec = lambda p: (p.ctypes.data_as(C.c_void_p), len(p))
+        wc.set_ctrl(z(N, NA), mode)
+        if base[_lib.POL_P_WEIGHTS + _lib.POL_TERMS.index("torques")] != 0.0:     # the readout kernels cost 3-4 %: only when the term is used
+            wc.enable_sim_readouts()
+        wc._call("tsidb_policy_config", *vec(base), self.action_scale.ctypes.data_as(C.c_void_p),
+                 self.default_joint_pos.ctypes.data_as(C.c_void_p), self.term_body_mask)
         if dr is not None:
             self.dr_params = dr
-            wc._call("tsidb_policy_randomize", dr.ctypes.data_as(vp), _lib.POL_DR_NPARAMS)
+            wc._call("tsidb_policy_randomize", *vec(dr))
             self._dr_push = bool(dr[_lib.POL_DR_PUSH_INTERVAL] >= 1 and dr[_lib.POL_DR_PUSH_DURATION] >= 1)
             self._dr_reset = bool(dr[_lib.POL_DR_RESET_JOINT_POS:_lib.POL_DR_RESET_LIFT + 1].any())
             if self._dr_push and wc.xfrc is None:
@@ -366,30 +365,33 @@ class PolicyEnv:
         if ter is not None:
             self.ter_params = ter
             wc.set_env_params(mass_scale=1.0, terrain="flat")      # nominal rows; the kernels rewrite the two tensors in place
-            wc._call("tsidb_policy_terrain_config", ter.ctypes.data_as(vp), _lib.POL_TER_NPARAMS)
-            self.terrain_level = z(N, dt=torch.int32)
-            self.height_scan = z(N, int(ter[_lib.POL_TER_SCAN_NX] * ter[_lib.POL_TER_SCAN_NY]))
+            wc._call("tsidb_policy_terrain_config", *vec(ter))
         if tsid is not None:
-            self.tsid = tsid
             self.teach_params = teach
-            wc._call("tsidb_policy_teacher_config", teach.ctypes.data_as(vp), _lib.POL_TEACH_NPARAMS)
-            self.teacher_terms, self.teacher_action = z(N, _lib.POL_TEACH_NT), z(N, NA)
-            self.teacher_obs = z(N, _lib.pol_teach_nobs(NA))
+            wc._call("tsidb_policy_teacher_config", *vec(teach))
             if tsid == "walk":
                 self._build_schedule(dict(walk or {}))
         self.reset()   # (episode 1 starts)
 
     @staticmethod
+    def _base_params(decimation, action_clip, filter_alpha, sigma, t_air, deadband, max_episode_steps, seed, command_range, reward_weights):
+        """the float64 vector tsidb_policy_config takes, which checks its values; h_target is left to __init__: its default needs the
+        controller"""
+        p = np.zeros(_lib.POL_NPARAMS)
+        p[_lib.POL_P_CLIP], p[_lib.POL_P_ALPHA], p[_lib.POL_P_SIGMA] = action_clip, filter_alpha, sigma
+        p[_lib.POL_P_T_AIR], p[_lib.POL_P_DEADBAND] = t_air, deadband
+        p[_lib.POL_P_MAX_EPISODE_STEPS], p[_lib.POL_P_DECIMATION], p[_lib.POL_P_SEED] = max_episode_steps, decimation, seed
+        rng = np.asarray(command_range, dtype=np.float64).reshape(3, 2)
+        p[_lib.POL_P_CMD_LO:_lib.POL_P_CMD_LO + 3], p[_lib.POL_P_CMD_HI:_lib.POL_P_CMD_HI + 3] = rng[:, 0], rng[:, 1]
+        p[_lib.POL_P_WEIGHTS:] = _weight_vector(reward_weights, _lib.POL_TERMS, "reward")
+        return p
+
+    @staticmethod
     def _teacher_params(teacher_weights, sigma_com, sigma_foot):
         """the float64 vector tsidb_policy_teacher_config takes, checked as the library checks it"""
-        weights = dict(teacher_weights or {})
-        unknown = sorted(set(weights) - set(_lib.POL_TEACH_TERMS))
-        if unknown:
-            raise _lib.TsidbError(f"PolicyEnv: unknown teacher terms {unknown} (known: {_lib.POL_TEACH_TERMS})")
         p = np.zeros(_lib.POL_TEACH_NPARAMS)
         p[_lib.POL_TEACH_SIGMA_COM], p[_lib.POL_TEACH_SIGMA_FOOT] = sigma_com, sigma_foot
-        for k, w in weights.items():
-            p[_lib.POL_TEACH_WEIGHTS + _lib.POL_TEACH_TERMS.index(k)] = w
+        p[_lib.POL_TEACH_WEIGHTS:] = _weight_vector(teacher_weights, _lib.POL_TEACH_TERMS, "teacher")
         if not np.isfinite(p).all():
             raise _lib.TsidbError("PolicyEnv: non-finite teacher weight or sigma")
         if not (p[_lib.POL_TEACH_SIGMA_COM] > 0 and p[_lib.POL_TEACH_SIGMA_FOOT] > 0):
@@ -482,6 +484,21 @@ class PolicyEnv:
         wc._call("tsidb_policy_teacher_obs", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(wc.tau),
                  _ptr(self.teacher_obs), self.teacher_obs.shape[1], wc._stream())
 
+    def _after_reset_done(self):
+        """what reset() and step() launch behind reset_done, each only while its group is on: a new plan, reset noise and new
+        tables for the envs just restarted, then the observation, the height scan and the teacher's observation of every env"""
+        if self.sched is not None:
+            self._replan()
+        if self._dr_reset:
+            self._reset_noise()
+        if self.terrain is not None:
+            self._terrain_reset()
+        self._obs()
+        if self.terrain is not None:
+            self._height_scan()
+        if self.tsid is not None:
+            self._teacher_obs()
+
     def reset(self, env_ids=None):
         """Restart the envs env_ids (None = all) as a done flag would: standing state, zeroed action history and air times, ctrl
         at the default pose (position mode), episode + 1, a new command where a range is set.  reward and done are cleared.
@@ -495,19 +512,9 @@ class PolicyEnv:
             ids = torch.as_tensor(env_ids, device=wc.device).long().reshape(-1)
             wc.done[ids] = 1
         wc.reset_done()
-        if self.sched is not None:
-            if env_ids is None:
-                self.clock.zero_()
-            self._replan()
-        if self._dr_reset:
-            self._reset_noise()
-        if self.terrain is not None:
-            self._terrain_reset()
-        self._obs()
-        if self.terrain is not None:
-            self._height_scan()
-        if self.tsid is not None:
-            self._teacher_obs()
+        if self.sched is not None and env_ids is None:
+            self.clock.zero_()
+        self._after_reset_done()
         wc.done.zero_()
         self.timeout.zero_()
         return self.obs
@@ -536,19 +543,11 @@ class PolicyEnv:
             self._reward()
             self._teacher()
         wc.reset_done()
-        if self.sched is not None:
-            self._replan()
-        if self._dr_reset:
-            self._reset_noise()
-        if self.terrain is not None:
-            self._terrain_reset()
-        self._obs()
+        self._after_reset_done()
         info = dict(timeout=self.timeout, terms=self.terms, episode_length=self.ep_len)
         if self.terrain is not None:
-            self._height_scan()
             info.update(height_scan=self.height_scan, env_params=wc.env_params, terrain_level=self.terrain_level)
         if self.tsid is not None:
-            self._teacher_obs()
             info.update(teacher_terms=self.teacher_terms, teacher_action=self.teacher_action, teacher_obs=self.teacher_obs)
         if self._dr_push:
             info["push"] = wc.xfrc[:, 0, :3]
