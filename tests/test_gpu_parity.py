@@ -90,6 +90,32 @@ def test_rbd_terms_f64(oracle):
     assert np.abs(M - M.transpose(0, 2, 1)).max() == 0
 
 
+def large_joint_angles(n, na, seed=11):
+    """(n, na) joint angles outside the walking range: the doubles nearest k pi/2 and their +-1 ulp neighbours for k in -8 .. 8
+    and k = +-637 (sincos_t's quadrant select and its reduction's last bits), the rest uniform in +-1e3"""
+    vals = []
+    for k in list(range(-8, 9)) + [-637, 637]:
+        x = k * (np.pi / 2)
+        vals += [x, np.nextafter(x, -np.inf), np.nextafter(x, np.inf)]
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(-1e3, 1e3, n * na)
+    a[:len(vals)] = vals
+    return rng.permutation(a).reshape(n, na)
+
+
+def test_rbd_terms_large_joint_angles_f64(oracle):
+    """the product path of sincos_t beyond quadrants -1, 0, 1: tsidb_rbd_terms against the oracle's libm at the same gate"""
+    wc = make(16)
+    perturb(wc, 1, dq=0.0, dv=1.0)
+    wc.q[:, 7:] = torch.as_tensor(large_joint_angles(16, 20)).to(wc.device)
+    t = wc.rbd_terms()
+    q, v = wc.q.cpu().numpy(), wc.v.cpu().numpy()
+    ref = [oracle.terms(q[e], v[e]) for e in range(16)]
+    for key in ("M", "h", "Jcom", "Jf", "oMf", "com"):
+        o = np.stack([r[key] for r in ref])
+        assert diff(t[key], o) < 1e-12 * max(1.0, np.abs(o).max()), key
+
+
 def test_rbd_terms_f32(oracle):
     wc = make(16, "f32")
     perturb(wc, 1, dq=0.5, dv=1.0)

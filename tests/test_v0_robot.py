@@ -155,6 +155,25 @@ def test_v0_tick_matches_oracle_on_gpu(v0):
         assert d(t[key], o) < 1e-10 * max(1.0, np.abs(o).max()), key
 
 
+@pytest.mark.gpu
+def test_v0_rbd_terms_large_joint_angles_f64(v0):
+    """test_gpu_parity.test_rbd_terms_large_joint_angles_f64 on the second robot"""
+    import torch
+    from tsid_control_amd import WalkController
+    from test_gpu_parity import large_joint_angles
+    n = 16
+    wc = WalkController(v0["conf"], num_envs=n, device="cuda:0")
+    g = torch.Generator().manual_seed(6)
+    wc.v[:] = torch.randn(n, NV, generator=g, dtype=torch.float64).to(wc.device)
+    wc.q[:, 7:] = torch.as_tensor(large_joint_angles(n, NA)).to(wc.device)
+    t = wc.rbd_terms()
+    q, v = wc.q.cpu().numpy(), wc.v.cpu().numpy()
+    ref = [v0["orc"].terms(q[e], v[e]) for e in range(n)]
+    for key in ("M", "h", "Jcom", "Jf", "oMf", "com"):
+        o = np.stack([r[key] for r in ref])
+        assert float(np.abs(t[key].double().cpu().numpy().reshape(o.shape) - o).max()) < 1e-12 * max(1.0, np.abs(o).max()), key
+
+
 # ---------------------------------------------------------------- the v0 sim stage (robot/v0/robot.xml)
 def sim_state(v0, z_lift=0.0):
     """sim state of the standing pose: qpos (wxyz, sim joint order), ctrl = the pose (servo force 0 at rest)"""

@@ -209,6 +209,8 @@ __device__ __forceinline__ void sincos_t(double x, double &s, double &c) {
   const double s0 = (q & 1) ? cr : sr, c0 = (q & 1) ? sr : cr;
   s = (q & 2) ? -s0 : s0;
   c = ((q + 1) & 2) ? -c0 : c0;
+  // sin(-0) = -0: the reduction's fma(+0, pi/2, -0) is +0, which loses the sign (sin stays odd bit for bit)
+  s = x == 0.0 ? x : s;
 }
 
 // Workgroup -> env.  The hardware deals consecutive workgroups round-robin to the 8 XCDs (one L2 each); with env =

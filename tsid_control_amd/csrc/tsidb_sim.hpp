@@ -643,7 +643,31 @@ template <typename T> __device__ __forceinline__ T origin_tri_closest(const T *a
   const T den = T(1) / (va + vb + vc), v = vb * den, w = vc * den;
 #pragma unroll
   for (int i = 0; i < 3; i++) q[i] = a[i] + ab[i] * v + ac[i] * w;
-  return dot3(q, q);
+  T best = dot3(q, q);
+  // Thin or collinear triangle: va + vb + vc = |ab x ac|^2 is then rounding noise of either sign (the products in va, vb, vc
+  // are fused, so even an exactly collinear triangle does not give exact zeros), the region tests above pass the case on
+  // to here and the face formula puts q on the triangle's line, anywhere.  Below sin^2 of the angle at a = 4 sqrt(eps) the
+  // answer is the least of: the face point if its weights keep it inside the triangle, and the closest points of the three
+  // edges - every one of them a point of the triangle, so the least is never below the true distance.  A triangle above
+  // that bound never gets here: its arithmetic is what it was.
+  const T thin = sizeof(T) == 8 ? T(6e-8) : T(1.4e-3);
+  if (!((va + vb + vc) > thin * dot3(ab, ab) * dot3(ac, ac))) {
+    if (!(v >= 0 && w >= 0 && v + w <= 1)) best = Eps<T>::inf; // (1e300 / 1e30, not infinity: any edge distance of a finite triangle is below it)
+    T bc[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) bc[i] = c[i] - b[i];
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+      const T *p = e == 2 ? b : a, *d = e == 0 ? ab : (e == 1 ? ac : bc);
+      const T dd = dot3(d, d);
+      T t = dd > 0 ? -dot3(p, d) / dd : T(0);
+      t = t > 0 ? (t < 1 ? t : T(1)) : T(0);
+      const T x = p[0] + t * d[0], y = p[1] + t * d[1], z = p[2] + t * d[2];
+      const T dist = x * x + y * y + z * z;
+      if (dist < best) { best = dist; q[0] = x; q[1] = y; q[2] = z; }
+    }
+  }
+  return best;
 }
 
 // Penetration of the convex hulls of bodies a (geom1) and b (geom2): Minkowski Portal Refinement on A - B, what

@@ -84,7 +84,7 @@ __device__ __forceinline__ double rdlane(double v, int src) {
 }
 
 // The tick's 26 x 26 Cholesky in registers (right-looking; lane i holds row i of the matrix in a[], and of L in a[0..i]
-// afterwards); lane k of rdv = 1 / L[k][k]; notspd is set when a pivot is not positive.
+// afterwards); lane k of rdv = 1 / L[k][k]; notspd is set when a pivot is not positive (the output is then finite, nothing more).
 // DPPB (float64 only): column k's entries reach their FMAs as DPP row broadcasts (row_dup / bcast_fnma, tsidb_common.hpp)
 // instead of v_readlane pairs - same operations, same bits on lanes 0..31.  Lanes >= 32 end up with other values than
 // the v_readlane form leaves there; the caller reads a[] on lanes < NV only.
@@ -96,7 +96,10 @@ template <typename T, bool DPPB> __device__ __forceinline__ void tick_chol(T (&a
     const T akk = rdlane(a[k], k);
     notspd = akk > 0 ? notspd : 1;
     asm volatile("" : "+v"(notspd));
-    const T rk = rsqrt_t(akk > 0 ? akk : T(1));
+    // (a pivot that is not positive scales its column by rk = rsqrt(1e300) = 1e-150 (float32: rsqrt(1e30) = 1e-15) instead of
+    //  leaving it unnormalised: not zero, but its products in the trailing update are 1e-300 / 1e-30 of the entries, so the
+    //  flagged factor stays finite - with rk = 1 the trailing entries squared from pivot to pivot, to inf within NV steps)
+    const T rk = rsqrt_t(akk > 0 ? akk : T(Eps<T>::inf));
     if (ln == k) rdv = rk;
     const T lik = ln == k ? akk * rk : a[k] * rk;
     a[k] = lik;
