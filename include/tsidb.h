@@ -686,6 +686,74 @@ int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsid
 int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done, const int32_t *timeout, const float *value,
                      float gamma, float lam, float *advantage, float *returns, void *stream);
 
+/* ---- the update's side of a PPO iteration: the loss of one minibatch of stored rollout rows and its gradient with respect to
+ * every weight and bias of the actor and the critic and to log_std.  The optimiser, gradient clipping, schedules and all-reduces
+ * stay the caller's, on the gradient buffers.  Plain asynchronous launches on the given stream (three kernels): no allocation, no
+ * host synchronisation, capturable in a graph.  Hot path: v_mfma_f32_16x16x4_f32, float32 throughout.  NO ATOMICS: every sum has
+ * one fixed order, the rows are cut into segments of TSIDB_POL_LEARN_SEG_ROWS whatever the device, so two calls on the same
+ * inputs write the same bits.
+ *
+ * The networks are tsidb_policy_net as tsidb_policy_actor takes them, weights and biases READ IN PLACE; the forward pass is
+ * k_policy_actor's own, bit for bit.  Of the block fields only n_blocks and block_cols are read - their total is the fan-in K of
+ * layer 0 - the input rows come from the batch: minibatch row m is the stored row j = index[m] of
+ *   actor_input [rows, K_actor], critic_input [rows, K_critic], action [rows, NA], logp, value, advantage, returns [rows]
+ * (float32, contiguous: a rollout's [T, N, ...] tensors with rows = T * N; value may be longer).  adv_stats [2] float32 (device):
+ * mean and 1 / std of the advantage, NULL = not normalised.  With c = clip, sigma = exp(log_std), per row:
+ *   mu = actor(actor_input[j]);  z = (action[j] - mu) / sigma;  logp = -sum_a (z_a^2 / 2 + log_std_a) - NA ln(2 pi) / 2
+ *   r = exp(logp - logp_old[j]);  Ahat = (advantage[j] - adv_stats[0]) * adv_stats[1]
+ *   L_pi = mean_m max(-Ahat r, -Ahat clamp(r, 1 - c, 1 + c))
+ *   v = critic(critic_input[j]);  v_clip = value[j] + clamp(v - value[j], -c, c)
+ *   L_v = mean_m max((v - returns[j])^2, (v_clip - returns[j])^2)      (value_clip = 0: (v - returns[j])^2)
+ *   entropy = sum_a (log_std_a + (1 + ln 2 pi) / 2);   loss = L_pi + value_coef L_v - entropy_coef entropy
+ * and the gradient is torch.autograd's for these expressions, ties included (a max of two equal terms gives each half).
+ * Written, OVERWRITTEN not accumulated: actor_grads / critic_grads (weight[l] [width, fan-in], bias[l] [width]; a bias gradient
+ * is required where the network has the bias), log_std_grad [NA], and stats [8] float32:
+ *   0 L_pi   1 L_v   2 entropy   3 mean (logp_old - logp)   4 fraction of rows with r outside [1 - c, 1 + c]   5 loss
+ *   6 rows used   7 bad indices
+ * A row whose index is outside [0, rows) is not read, contributes nothing and is counted in stats[7]; the means stay over M.
+ * critic may be NULL (critic_grads unused, L_v = 0).
+ *
+ * workspace: float32 device memory of at least tsidb_policy_learn_workspace's bytes (a function of the two networks and M),
+ * rewritten by every call.  With Mp = M rounded up to a multiple of 16 its first Mp * NA floats are mu [Mp, NA] and the next Mp
+ * floats v (with a critic), as the forward pass computed them for the M rows; the rest is the library's.
+ * Rejects (message via tsidb_last_error, nothing launched): a NULL actor, batch, actor_grads, cfg, log_std, log_std_grad, stats,
+ * workspace, index or stored array the call reads; critic_grads NULL with a critic; everything tsidb_policy_actor rejects in a
+ * network apart from its block pointers and strides; a NULL weight gradient, a NULL bias gradient where the bias exists; M < 1,
+ * rows < 1; a workspace smaller than the query's; clip <= 0; a critic without critic_input, value or returns. */
+enum { TSIDB_POL_LEARN_SEG_ROWS = 512, TSIDB_POL_LEARN_NSTATS = 8 };
+typedef struct tsidb_policy_learn_batch {
+  const float *actor_input;
+  const float *critic_input;
+  const float *action;
+  const float *logp;
+  const float *value;
+  const float *advantage;
+  const float *returns;
+  const int32_t *index;      /* [M] device */
+  int rows;
+  int M;
+  const float *adv_stats;
+} tsidb_policy_learn_batch;
+
+typedef struct tsidb_policy_grads {
+  float *weight[4];
+  float *bias[4];
+} tsidb_policy_grads;
+
+typedef struct tsidb_policy_learn_cfg {
+  float clip;
+  float value_coef;
+  float entropy_coef;
+  int value_clip;
+} tsidb_policy_learn_cfg;
+
+int tsidb_policy_learn_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes);
+
+int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                       const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                       const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream);
+
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */
 int tsidb_rbd_terms(tsidb_handle h, const void *q, const void *v, void *M, void *hbias, void *Jcom, void *Jf,

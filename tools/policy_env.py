@@ -29,7 +29,13 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               storage - each eager and captured in a graph, in alternating windows of 16-step rollouts (a process per case), at 4096 and 512 envs,
               decimation 4; actor obs -> 256 -> 128 -> NA (ELU), critic obs | priv -> 256 -> 128 -> 1, and the same with obs |
               height_scan (77) as the actor's input; default profiles/policy_actor.json.  The kernel's time comes from a run of its
-              own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --actor --trace ENVS STEPS"""
+              own: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --actor --trace ENVS STEPS
+    python tools/policy_env.py --learn [out.json]   one PPO update on a recorded 16-step rollout (5 epochs x 4 minibatches, Adam): PolicyLearner
+              (three launches per minibatch: loss, backward and weight gradients on the storage's own rows) against TorchLearner below -
+              the same loss in eager torch over nn.Sequential copies of the networks, the same minibatches, the same optimiser - in
+              alternating windows (a process per case), at 4096 and 512 envs, the 256-128 networks; and the first minibatch's loss from
+              both on equal weights; default profiles/policy_learner.json.  The kernels' times come from a run of its own:
+              rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --trace ENVS UPDATES"""
 import json
 import sys
 import time
@@ -361,7 +367,107 @@ def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
 
 
+class TorchLearner:
+    """PolicyLearner's loss and update in eager torch with autograd: nn.Sequential copies of the two networks and of log_std, the
+    forward pass over the storage's own rows"""
+
+    def __init__(self, actor, critic, log_std, clip=0.2, value_coef=1.0, entropy_coef=0.0):
+        import copy
+        self.actor, self.critic = copy.deepcopy(actor), copy.deepcopy(critic)
+        self.log_std = log_std.clone().requires_grad_()
+        self.clip, self.value_coef, self.entropy_coef = clip, value_coef, entropy_coef
+        self.adv_stats = None
+
+    def parameters(self):
+        return list(self.actor.parameters()) + list(self.critic.parameters()) + [self.log_std]
+
+    def loss(self, st, index):
+        rows, c, ls = st.logp.numel(), self.clip, self.log_std
+        j = index.long()
+        flat = lambda t: t.reshape(rows, -1)[j]
+        mu, v = self.actor(flat(st.actor_input)), self.critic(flat(st.critic_input)).squeeze(1)
+        z = (flat(st.action) - mu) / ls.exp()
+        logp = -(0.5 * z * z + ls).sum(1) - 0.5 * mu.shape[1] * 1.8378770664093453
+        r = (logp - st.logp.reshape(-1)[j]).exp()
+        adv = (st.advantage.reshape(-1)[j] - self.adv_stats[0]) * self.adv_stats[1]
+        l_pi = torch.max(-adv * r, -adv * r.clamp(1 - c, 1 + c)).mean()
+        old, ret = st.value[:-1].reshape(-1)[j], st.returns.reshape(-1)[j]
+        l_v = torch.max((v - ret) ** 2, (old + (v - old).clamp(-c, c) - ret) ** 2).mean()
+        entropy = (ls + 0.5 * (1 + 1.8378770664093453)).sum()
+        return l_pi + self.value_coef * l_v - self.entropy_coef * entropy
+
+    def update(self, st, opt, epochs, minibatches, generator):
+        rows = st.logp.numel()
+        self.adv_stats = torch.stack([st.advantage.mean(), 1.0 / (st.advantage.std() + 1e-8)])
+        for _ in range(epochs):
+            perm = torch.randperm(rows, generator=generator, dtype=torch.int32, device=st.logp.device)
+            for k in range(minibatches):
+                opt.zero_grad(set_to_none=True)
+                self.loss(st, perm[k * rows // minibatches:(k + 1) * rows // minibatches]).backward()
+                opt.step()
+
+
+def learn_setup(n, steps=16, decimation=4):
+    """(storage with its advantages, PolicyLearner, TorchLearner on copies of the same weights) after one recorded rollout"""
+    from tsid_control_amd import PolicyActor, PolicyLearner
+    env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delays(n), **dict(KW, action_scale=0.05))
+    actor, critic, ai, ci, ls = actor_nets(env, False)
+    pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls)
+    st = env.rollout(pa, steps)
+    st.gae(0.99, 0.95)
+    kw = dict(clip=0.2, value_coef=1.0, entropy_coef=0.01)
+    return st, PolicyLearner(pa, **kw), TorchLearner(actor, critic, ls, **kw)
+
+
+def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3):
+    """updates/s of one PPO update on the same recorded rollout: fused / torch in alternating windows of one process, and the
+    loss of the first minibatch from both before either has moved a weight"""
+    st, fused, eager = learn_setup(n)
+    rows = st.logp.numel()
+    index = torch.randperm(rows, generator=torch.Generator(device="cuda:0").manual_seed(3), dtype=torch.int32, device="cuda:0")[:rows // minibatches]
+    stats = fused.backward(st, index).clone()
+    eager.adv_stats = fused.adv_stats.clone()
+    with torch.no_grad():
+        loss_torch = float(eager.loss(st, index))
+    grad_torch = torch.autograd.grad(eager.loss(st, index), eager.parameters())
+    grad_rel = max(float((a.grad - b).abs().max() / b.abs().max()) for a, b in zip(fused.parameters(), grad_torch))
+    opts = dict(fused=torch.optim.Adam(fused.parameters(), lr=1e-4), torch=torch.optim.Adam(eager.parameters(), lr=1e-4))
+    gens = {k: torch.Generator(device="cuda:0").manual_seed(5) for k in opts}
+    run = dict(fused=lambda k: [fused.update(st, opts["fused"], epochs, minibatches, gens["fused"]) for _ in range(k)],
+               torch=lambda k: [eager.update(st, opts["torch"], epochs, minibatches, gens["torch"]) for _ in range(k)])
+    r = alternate(run, window, windows, preroll)
+    med = r["policy_steps_per_s_median"]
+    last = fused.update(st, opts["fused"], 1, minibatches, gens["fused"])
+    return dict(envs=n, rollout_steps=st.steps, rows=rows, epochs=epochs, minibatches=minibatches, minibatch_rows=rows // minibatches,
+                window_updates=window, windows=windows, updates_per_s_median=med, updates_per_s_all=r["all"],
+                ms_per_update={k: 1e3 / v for k, v in med.items()}, fused_over_torch=med["fused"] / med["torch"],
+                first_minibatch=dict(loss_fused=float(stats[5]), loss_torch=loss_torch, loss_difference=float(stats[5]) - loss_torch,
+                                     largest_gradient_difference_over_largest_entry=grad_rel,
+                                     stats=dict(zip(_lib.POL_LEARN_STATS, (float(x) for x in stats)))),
+                stats_after=dict(zip(_lib.POL_LEARN_STATS, (float(x) for x in last[-1]))))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--learn":
+        if len(sys.argv) > 2 and sys.argv[2] == "--trace":
+            st, fused, _ = learn_setup(int(sys.argv[3]))
+            opt = torch.optim.Adam(fused.parameters(), lr=1e-4)
+            for _ in range(int(sys.argv[4])):
+                fused.update(st, opt, 5, 4)
+            torch.cuda.synchronize()
+            sys.exit(0)
+        if len(sys.argv) > 2 and sys.argv[2] == "--case":           # one env count, as a JSON line
+            print(json.dumps(measure_learn(int(sys.argv[3]))))
+            sys.exit(0)
+        import subprocess
+        out_path = sys.argv[2] if len(sys.argv) > 2 else "profiles/policy_learner.json"
+        runs = []
+        for n in (4096, 512):
+            r = subprocess.run([sys.executable, sys.argv[0], "--learn", "--case", str(n)], capture_output=True, text=True, check=True)
+            runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        report(out_path, actor="obs -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU", optimizer="Adam, lr 1e-4",
+               loss="clip 0.2, value_coef 1, entropy_coef 0.01, clipped value loss, normalised advantages", runs=runs)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--actor":
         from tsid_control_amd import PolicyActor
         if len(sys.argv) > 2 and sys.argv[2] == "--trace":

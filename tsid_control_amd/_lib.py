@@ -17,7 +17,7 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise",
            "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs",
            "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan",
-           "tsidb_policy_actor", "tsidb_policy_gae"]
+           "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -71,6 +71,9 @@ POL_NET_MAXLAYERS, POL_NET_MAXBLOCKS, POL_NET_MAXWIDTH = 4, 4, 512
 POL_ACTIVATIONS = ("elu", "tanh", "relu")
 POL_ACTOR_SAMPLE = 1
 POL_ACTOR_STREAMS = (21, 22)
+# the policy learner (include/tsidb.h tsidb_policy_learn): the rows of a segment of the weight gradient's sums, and the stats
+POL_LEARN_SEG_ROWS = 512
+POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "loss", "rows", "bad_indices")
 
 
 def pol_teach_nobs(na):
@@ -116,6 +119,23 @@ class PolicyActorOut(C.Structure):
     """tsidb_policy_actor_out (include/tsidb.h): what tsidb_policy_actor writes, every pointer optional"""
     _fields_ = [("action", C.c_void_p), ("action32", C.c_void_p), ("mean", C.c_void_p), ("logp", C.c_void_p), ("value", C.c_void_p),
                 ("actor_input", C.c_void_p), ("critic_input", C.c_void_p)]
+
+
+class PolicyLearnBatch(C.Structure):
+    """tsidb_policy_learn_batch (include/tsidb.h): the stored arrays of a rollout and the minibatch's rows"""
+    _fields_ = [("actor_input", C.c_void_p), ("critic_input", C.c_void_p), ("action", C.c_void_p), ("logp", C.c_void_p),
+                ("value", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("index", C.c_void_p),
+                ("rows", C.c_int), ("M", C.c_int), ("adv_stats", C.c_void_p)]
+
+
+class PolicyGrads(C.Structure):
+    """tsidb_policy_grads (include/tsidb.h): where the gradient of each layer's weight and bias goes"""
+    _fields_ = [("weight", C.c_void_p * 4), ("bias", C.c_void_p * 4)]
+
+
+class PolicyLearnCfg(C.Structure):
+    """tsidb_policy_learn_cfg (include/tsidb.h)"""
+    _fields_ = [("clip", C.c_float), ("value_coef", C.c_float), ("entropy_coef", C.c_float), ("value_clip", C.c_int)]
 
 
 def dims9(L):
@@ -191,6 +211,8 @@ def load(path=None):
     L.tsidb_policy_height_scan.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     L.tsidb_policy_actor.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
     L.tsidb_policy_gae.argtypes = [vp, C.c_int, vp, vp, i32p, vp, C.c_float, C.c_float, vp, vp, vp]
+    L.tsidb_policy_learn_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+    L.tsidb_policy_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -67,39 +67,11 @@ __device__ __forceinline__ float act_fn(int kind, float x) {
   return x > 0.f ? x : 0.f;
 }
 
-template <typename T>
-__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) {
-  extern __shared__ float act_lds[];
-  const int which = blockIdx.y + a.first;
-  const ActorNet &net = a.net[which];
-  const int LD = a.LD, tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform, and said so to the compiler: the tile tests become scalar branches
-  const int e0 = blockIdx.x * ACT_TILE;
-  float *X[2] = {act_lds, act_lds + ACT_TILE * LD};
-
-  // ---- the input rows: block by block, cast on load; rows past the batch and the columns up to the next multiple of 4 are 0
-  int off = 0;
-  for (int bi = 0; bi < net.n_blocks; bi++) {
-    const T *src = (const T *)net.blk[bi];
-    const int cols = net.blk_cols[bi], ld = net.blk_ld[bi];
-    for (int idx = tid; idx < ACT_TILE * cols; idx += WAVE * ACT_WAVES) {
-      const int r = idx / cols, c = idx - r * cols, e = e0 + r;
-      float v = 0.f;
-      if (e < a.n) {
-        v = (float)src[(size_t)e * ld + c];
-        if (net.input) net.input[(size_t)e * net.K + off + c] = v;
-      }
-      X[0][r * LD + off + c] = v;
-    }
-    off += cols;
-  }
-  if (tid < ACT_TILE * 4) {
-    const int r = tid >> 2, c = net.K + (tid & 3);
-    if (c < ((net.K + 3) & ~3)) X[0][r * LD + c] = 0.f;
-  }
-  __syncthreads();
-
-  // ---- the layers
+// The layers of one network on the tile's 16 rows: X[0] holds the input rows (pad columns 0), layer L reads X[L & 1] and writes
+// X[(L + 1) & 1]; after_layer(L, image, width) runs behind each layer's barrier (k_policy_actor: nothing; k_policy_learn_rows
+// stores the rows).  One copy, so that the learner's forward pass is the actor's bit for bit: same k order, same zero padding.
+template <typename Hook>
+__device__ __forceinline__ void act_layers(const ActorNet &net, float *const X[2], int LD, int i, int g, int wave, Hook &&after_layer) {
   int Kin = net.K;
   for (int L = 0; L < net.n_layers; L++) {
     const float *A = X[L & 1], *W = net.W[L], *bias = net.b[L];
@@ -148,7 +120,44 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) 
     }
     Kin = Nout;
     __syncthreads();
+    after_layer(L, D, Nout);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) {
+  extern __shared__ float act_lds[];
+  const int which = blockIdx.y + a.first;
+  const ActorNet &net = a.net[which];
+  const int LD = a.LD, tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform, and said so to the compiler: the tile tests become scalar branches
+  const int e0 = blockIdx.x * ACT_TILE;
+  float *X[2] = {act_lds, act_lds + ACT_TILE * LD};
+
+  // ---- the input rows: block by block, cast on load; rows past the batch and the columns up to the next multiple of 4 are 0
+  int off = 0;
+  for (int bi = 0; bi < net.n_blocks; bi++) {
+    const T *src = (const T *)net.blk[bi];
+    const int cols = net.blk_cols[bi], ld = net.blk_ld[bi];
+    for (int idx = tid; idx < ACT_TILE * cols; idx += WAVE * ACT_WAVES) {
+      const int r = idx / cols, c = idx - r * cols, e = e0 + r;
+      float v = 0.f;
+      if (e < a.n) {
+        v = (float)src[(size_t)e * ld + c];
+        if (net.input) net.input[(size_t)e * net.K + off + c] = v;
+      }
+      X[0][r * LD + off + c] = v;
+    }
+    off += cols;
+  }
+  if (tid < ACT_TILE * 4) {
+    const int r = tid >> 2, c = net.K + (tid & 3);
+    if (c < ((net.K + 3) & ~3)) X[0][r * LD + c] = 0.f;
+  }
+  __syncthreads();
+
+  // ---- the layers
+  act_layers(net, X, LD, i, g, wave, [](int, const float *, int) {});
 
   // ---- the epilogue, from the LDS image of the last layer
   const float *Y = X[net.n_layers & 1];

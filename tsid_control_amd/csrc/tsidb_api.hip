@@ -5,6 +5,7 @@
 #include "tsidb_tick.hpp"
 #include "tsidb_policy.hpp"
 #include "tsidb_actor.hpp"
+#include "tsidb_learner.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -729,6 +730,7 @@ struct tsidb_ctx {
   double pol_ter[TSIDB_POL_TER_NPARAMS] = {};
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
+  bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
   bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
   std::string err;
 };
@@ -1577,6 +1579,154 @@ int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done
     hipLaunchKernelGGL(k_policy_gae<F>, dim3((h->num_envs + 255) / 256), dim3(256), 0, s, h->num_envs, T, (const F *)reward, (const F *)done,
                        timeout, value, gamma, lam, advantage, returns);
   });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+} // extern "C"
+
+// tsidb_policy_net as the learner takes it: the actor's checks apart from the block pointers and strides; the input rows are
+// the batch's
+static LearnNet learn_net(const tsidb_policy_net *p, const char *who, const char *name, int last, const char *last_name) {
+  tsidb_policy_net q = *p;
+  static const float dummy = 0.f;
+  for (int i = 0; i < ACT_MAXB; i++) { q.block[i] = &dummy; q.block_ld[i] = ACT_MAXW; }   // (never read: only n_blocks and block_cols count)
+  LearnNet n = {};
+  n.net = actor_net(&q, who, name, last, last_name, nullptr);
+  n.net.n_blocks = 0;
+  for (int i = 0; i < ACT_MAXB; i++) n.net.blk[i] = nullptr;
+  return n;
+}
+
+// The workspace of a call, in floats: mu [Mp, NA], v [Mp]; per network the gathered rows, the hidden H_l and every G_l; the
+// per-row pieces; the segments' partial sums.  Fills the offsets of the three launches where they are given.
+static size_t learn_layout(LearnNet *nets, int M, WgradArgs *w, ReduceArgs *r, size_t *r_off) {
+  const size_t Mp = (size_t)((M + ACT_TILE - 1) / ACT_TILE) * ACT_TILE;
+  const int nseg = (int)((Mp + LRN_SEG - 1) / LRN_SEG);
+  size_t off = 0, p = 0;
+  int blk = 0, nj = 0, np = 0;
+  for (int y = 0; y < 2; y++) {                      // the outputs first, where the caller may look
+    const ActorNet &n = nets[y].net;
+    if (n.n_layers) nets[y].h[n.n_layers - 1] = off;
+    off += Mp * (y == 0 ? NA : 1);
+  }
+  for (int y = 0; y < 2; y++) {
+    LearnNet &ln = nets[y];
+    const ActorNet &n = ln.net;
+    if (!n.n_layers) continue;
+    ln.x = off; off += Mp * n.K;
+    for (int l = 0; l + 1 < n.n_layers; l++) { ln.h[l] = off; off += Mp * n.width[l]; }
+    for (int l = 0; l < n.n_layers; l++) { ln.g[l] = off; off += Mp * n.width[l]; }
+    for (int l = 0; l < n.n_layers; l++) {
+      const int fan = l ? n.width[l - 1] : n.K, kext = fan + 1;
+      if (w) {
+        WgradJob &j = w->job[nj++];
+        j.g = ln.g[l]; j.h = l ? ln.h[l - 1] : ln.x; j.p = p; j.gw = n.width[l]; j.hw = fan; j.ones = 0;
+        j.nkg = ((kext + 15) / 16 + LRN_KGROUP - 1) / LRN_KGROUP; j.blk0 = blk;
+        blk += ((n.width[l] + 15) / 16) * j.nkg;
+      }
+      if (r) { ReducePiece &pc = r->piece[np++]; pc.p = p; pc.width = n.width[l]; pc.kext = kext; }
+      p += (size_t)n.width[l] * kext;
+    }
+  }
+  const size_t rows_off = off;
+  off += Mp * LRN_NR;
+  if (r_off) *r_off = rows_off;
+  if (w) {
+    WgradJob &j = w->job[nj++];
+    j.g = 0; j.h = rows_off; j.p = p; j.gw = 1; j.hw = LRN_NR; j.ones = 1;
+    j.nkg = ((LRN_NR + 1 + 15) / 16 + LRN_KGROUP - 1) / LRN_KGROUP; j.blk0 = blk;
+    blk += j.nkg;
+    w->njobs = nj; w->Mp = (int)Mp; w->part = off; w->total = p + LRN_NR + 1;
+  }
+  if (r) { r->npieces = np; r->nseg = nseg; r->M = M; r->part = off; r->total = p + LRN_NR + 1; r->rp = p; }
+  off += (size_t)nseg * (p + LRN_NR + 1);
+  return off;
+}
+
+static int learn_blocks(const WgradArgs &w) {
+  const WgradJob &j = w.job[w.njobs - 1];
+  return j.blk0 + ((j.gw + 15) / 16) * j.nkg;
+}
+
+extern "C" {
+
+int tsidb_policy_learn_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_learn_workspace: ";
+  if (!actor) throw std::string(who) + "null actor";
+  if (!bytes) throw std::string(who) + "null bytes";
+  if (M < 1) throw std::string(who) + "M must be >= 1";
+  LearnNet nets[2] = {};
+  nets[0] = learn_net(actor, who, "actor", NA, "NA");
+  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
+  *bytes = learn_layout(nets, M, nullptr, nullptr, nullptr) * sizeof(float);
+  GUARD_END
+}
+
+int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                       const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                       const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_learn: ";
+  hipStream_t s = (hipStream_t)stream;
+  if (!actor) throw std::string(who) + "null actor";
+  if (!batch) throw std::string(who) + "null batch";
+  if (!actor_grads) throw std::string(who) + "null actor_grads";
+  if (critic && !critic_grads) throw std::string(who) + "null critic_grads";
+  if (!cfg) throw std::string(who) + "null cfg";
+  if (!log_std || !log_std_grad) throw std::string(who) + "null log_std or log_std_grad";
+  if (!stats) throw std::string(who) + "null stats";
+  if (!workspace) throw std::string(who) + "null workspace";
+  if (!batch->index) throw std::string(who) + "null index";
+  if (batch->M < 1) throw std::string(who) + "M must be >= 1";
+  if (batch->rows < 1) throw std::string(who) + "rows must be >= 1";
+  if (!(cfg->clip > 0.f)) throw std::string(who) + "clip must be > 0";
+  if (!batch->actor_input || !batch->action || !batch->logp || !batch->advantage)
+    throw std::string(who) + "null stored array (actor_input, action, logp, advantage)";
+  if (critic && (!batch->critic_input || !batch->value || !batch->returns))
+    throw std::string(who) + "a critic needs critic_input, value and returns";
+  LearnArgs a = {};
+  a.net[0] = learn_net(actor, who, "actor", NA, "NA");
+  if (critic) a.net[1] = learn_net(critic, who, "critic", 1, "1");
+  WgradArgs w = {};
+  ReduceArgs r = {};
+  const size_t need = learn_layout(a.net, batch->M, &w, &r, &a.r) * sizeof(float);
+  if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
+  int np = 0, widest = 0;
+  for (int y = 0; y < 2; y++) {
+    const tsidb_policy_net *p = y ? critic : actor;
+    const tsidb_policy_grads *gr = y ? critic_grads : actor_grads;
+    const ActorNet &n = a.net[y].net;
+    if (n.K > widest) widest = n.K;
+    for (int l = 0; l < n.n_layers; l++) {
+      if (n.width[l] > widest) widest = n.width[l];
+      if (!gr->weight[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null weight gradient";
+      if (p->bias[l] && !gr->bias[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null bias gradient where the bias exists";
+      r.piece[np].dW = gr->weight[l];
+      r.piece[np].db = p->bias[l] ? gr->bias[l] : nullptr;
+      np++;
+    }
+  }
+  a.net[0].in = batch->actor_input; a.net[1].in = batch->critic_input;
+  a.M = batch->M; a.rows = batch->rows; a.LD = act_ld(widest); a.value_clip = cfg->value_clip;
+  a.index = batch->index; a.action = batch->action; a.logp = batch->logp; a.value = batch->value; a.advantage = batch->advantage;
+  a.returns = batch->returns; a.adv_stats = batch->adv_stats; a.log_std = log_std;
+  a.clip = cfg->clip; a.value_coef = cfg->value_coef; a.ws = workspace;
+  w.ws = workspace;
+  r.ws = workspace; r.log_std = log_std; r.log_std_grad = log_std_grad; r.stats = stats;
+  r.value_coef = cfg->value_coef; r.entropy_coef = cfg->entropy_coef;
+  const size_t lds = act_lds_bytes(a.LD);
+  if (lds > 65536 && !h->learn_big_lds) {     // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle)
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_learn_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)act_lds_bytes(act_ld(ACT_MAXW))));
+    h->learn_big_lds = true;
+  }
+  h->note_stream(s);
+  hipLaunchKernelGGL(k_policy_learn_rows, dim3(w.Mp / ACT_TILE, critic ? 2 : 1), dim3(WAVE * ACT_WAVES), lds, s, a);
+  hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
+  hipLaunchKernelGGL(k_policy_learn_reduce, dim3((unsigned)((r.rp + NA + 1 + 255) / 256)), dim3(256), 0, s, r);
   HIP_OK(hipGetLastError());
   GUARD_END
 }

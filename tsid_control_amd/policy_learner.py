@@ -1,0 +1,170 @@
+"""PolicyLearner - the loss and the gradients of a PPO update on the device (include/tsidb.h tsidb_policy_learn;
+csrc/tsidb_learner.hpp): the clipped surrogate, the clipped value loss and the entropy bonus of rsl_rl's PPO on one minibatch
+of a RolloutStorage, and the gradient of every weight and bias of the PolicyActor's two networks and of log_std, written into
+their .grad.  The forward pass is the actor kernel's own, so the recomputed log-probability is the stored one's twin.  No
+reference counterpart (the reference's only controller is TSID, main.py:113-129).
+
+What stays the caller's: the optimiser (any torch.optim over the same tensors: its step is what the next act() and the next
+backward() compute with, nothing is copied), gradient clipping, schedules, all-reduces, observation normalisation - all work on
+.grad as they do after loss.backward().  .grad is OVERWRITTEN by every backward(), never accumulated.
+
+No parameter needs requires_grad, log_std included: backward() gives every parameter that has none a zero float32 .grad of
+its own, reads the pointers again at every call (zero_grad(set_to_none=True) is harmless), and torch's optimisers step every
+parameter that has a .grad.  A .grad the caller set is used as it is if it is float32, contiguous and on the device.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .policy_actor import PolicyActor, RolloutStorage
+
+
+def _bad(msg):
+    return _lib.TsidbError("PolicyLearner: " + msg)
+
+
+def _number(name, x, lo=None, strict=False):
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x or x in (float("inf"), float("-inf")):
+        raise _bad(f"{name} must be a finite number, got {x!r}")
+    if lo is not None and (x <= lo if strict else x < lo):
+        raise _bad(f"{name} must be {'>' if strict else '>='} {lo}, got {x!r}")
+    return float(x)
+
+
+def _count(name, x):
+    if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+        raise _bad(f"{name} must be a whole number >= 1, got {x!r}")
+    return x
+
+
+class PolicyLearner:
+    """actor: the PolicyActor whose networks and log_std are learned.  clip: the surrogate's and the value loss's range (> 0);
+    value_coef, entropy_coef (>= 0): loss = L_pi + value_coef L_v - entropy_coef entropy; value_clip: the clipped value loss
+    (False: the plain squared error); normalize_advantage: advantages minus their mean, over their std + 1e-8, of the whole
+    storage.
+
+    Tensors: stats [8] float32, written by backward() - policy_loss, value_loss, entropy, approx_kl, clip_fraction, loss, rows,
+    bad_indices (_lib.POL_LEARN_STATS); adv_stats [2] (mean, 1 / std); workspace (grown to the largest minibatch seen)."""
+
+    def __init__(self, actor, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=True, normalize_advantage=True):
+        if not isinstance(actor, PolicyActor):
+            raise _bad(f"actor must be a PolicyActor, got {type(actor).__name__}")
+        self.actor, self.env = actor, actor.env
+        self.clip = _number("clip", clip, 0.0, strict=True)
+        self.value_coef, self.entropy_coef = _number("value_coef", value_coef, 0.0), _number("entropy_coef", entropy_coef, 0.0)
+        for name, x in (("value_clip", value_clip), ("normalize_advantage", normalize_advantage)):
+            if not isinstance(x, bool):
+                raise _bad(f"{name} must be a bool, got {x!r}")
+        self.value_clip, self.normalize_advantage = value_clip, normalize_advantage
+        dev = self.env.wc.device
+        self.stats = torch.zeros(len(_lib.POL_LEARN_STATS), dtype=torch.float32, device=dev)
+        self.adv_stats = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+        self.workspace, self._ws_rows = None, 0
+        self._cfg = _lib.PolicyLearnCfg(self.clip, self.value_coef, self.entropy_coef, int(value_clip))
+
+    def parameters(self):
+        """every tensor backward() writes a .grad of: the weights and biases of the actor, of the critic, and log_std - what an
+        optimiser is built over"""
+        nets = [self.actor.actor_net] + ([self.actor.critic_net] if self.actor.critic_net is not None else [])
+        return [t for net in nets for w, b in net.layers for t in (w, b) if t is not None] + [self.actor.log_std]
+
+    def _grad(self, p):
+        g = p.grad
+        if g is None:
+            p.grad = g = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+        elif g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape or not g.is_contiguous():
+            raise _bad(f"a .grad must be a contiguous float32 tensor of its parameter's shape on {p.device}, got "
+                       f"{(tuple(g.shape), g.dtype, g.device, g.stride())}")
+        return g
+
+    def _grads_of(self, net):
+        s = _lib.PolicyGrads()
+        for i, (w, b) in enumerate(net.layers):
+            s.weight[i] = self._grad(w).data_ptr()
+            s.bias[i] = self._grad(b).data_ptr() if b is not None else None
+        return s
+
+    def _workspace_for(self, M):
+        if self.workspace is None or M > self._ws_rows:
+            wc, a = self.env.wc, self.actor
+            n = C.c_size_t(0)
+            wc._call("tsidb_policy_learn_workspace", C.byref(a.actor_net.struct),
+                     C.byref(a.critic_net.struct) if a.critic_net is not None else None, M, C.byref(n))
+            self.workspace = torch.empty(max(1, (n.value + 3) // 4), dtype=torch.float32, device=wc.device)
+            self._ws_rows, self._ws_bytes = M, n.value
+        return self.workspace
+
+    def fill_adv_stats(self, storage):
+        """adv_stats = (mean, 1 / (std + 1e-8)) of storage.advantage, with torch ops on the current stream: no host sync"""
+        adv = storage.advantage
+        torch.stack([adv.mean(), 1.0 / (adv.std() + 1e-8)], out=self.adv_stats)
+
+    def backward(self, storage, index, stats=None, adv_stats=None):
+        """The loss of the stored rows index [M] (int32, on the device; any order, duplicates allowed, flat t * N + e into the
+        first T * N rows) and its gradients into .grad, in three launches on the current stream.  Returns stats ([8] float32:
+        self.stats, or the tensor given).  adv_stats: None = self.adv_stats, filled from this storage by this call when
+        normalize_advantage is set; update() fills it once and passes it."""
+        wc, a = self.env.wc, self.actor
+        if not isinstance(storage, RolloutStorage) or storage.actor is not a:
+            raise _bad("storage must be a RolloutStorage of this learner's actor")
+        if storage.advantage is None:
+            raise _bad("storage.gae() has not run: there are no advantages and returns")
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or index.shape[0] < 1 \
+                or index.device != wc.device or not index.is_contiguous():
+            what = (tuple(index.shape), index.dtype, index.device) if isinstance(index, torch.Tensor) else type(index).__name__
+            raise _bad(f"index must be a contiguous [M >= 1] int32 tensor on {wc.device}, got {what}")
+        if stats is None:
+            stats = self.stats
+        elif not isinstance(stats, torch.Tensor) or stats.dtype != torch.float32 or tuple(stats.shape) != (len(_lib.POL_LEARN_STATS),) \
+                or stats.device != wc.device or not stats.is_contiguous():
+            raise _bad(f"stats must be a contiguous [{len(_lib.POL_LEARN_STATS)}] float32 tensor on {wc.device}")
+        if adv_stats is None and self.normalize_advantage:
+            self.fill_adv_stats(storage)
+        M = int(index.shape[0])
+        ws = self._workspace_for(M)
+        p = lambda t: t.data_ptr() if t is not None else None
+        batch = _lib.PolicyLearnBatch(p(storage.actor_input), p(storage.critic_input), p(storage.action), p(storage.logp), p(storage.value),
+                                      p(storage.advantage), p(storage.returns), p(index), storage.steps * self.env.num_envs, M,
+                                      p(self.adv_stats) if self.normalize_advantage else None)
+        ag = self._grads_of(a.actor_net)
+        cg = self._grads_of(a.critic_net) if a.critic_net is not None else None
+        self._last = (batch, ag, cg)       # (alive until the next call: the library copies them during the call, a recorder may look later)
+        wc._call("tsidb_policy_learn", C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None,
+                 C.byref(batch), C.byref(ag), C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()),
+                 C.c_void_p(self._grad(a.log_std).data_ptr()), C.byref(self._cfg), C.c_void_p(ws.data_ptr()),
+                 C.c_size_t(ws.numel() * 4), C.c_void_p(stats.data_ptr()), wc._stream())
+        return stats
+
+    def outputs(self, M):
+        """(mu [M, NA], v [M] or None): the actor's and the critic's outputs on the rows of the last backward() of M rows, views
+        of the workspace (include/tsidb.h: its first floats)"""
+        Mp, NA = (M + 15) // 16 * 16, self.env.NA
+        mu = self.workspace[:Mp * NA].view(Mp, NA)[:M]
+        return mu, (self.workspace[Mp * NA:Mp * NA + M] if self.actor.critic_net is not None else None)
+
+    def update(self, storage, optimizer, epochs=5, minibatches=4, generator=None):
+        """One PPO update on a storage whose gae() has run: per epoch a torch.randperm(T * N) on the device (generator: a
+        torch.Generator of the device, None = the default one), cut into `minibatches` slices; per slice backward() and
+        optimizer.step().  Returns the stats of every slice, [epochs * minibatches, 8]; no host sync anywhere."""
+        wc = self.env.wc
+        epochs, minibatches = _count("epochs", epochs), _count("minibatches", minibatches)
+        if not isinstance(storage, RolloutStorage) or storage.advantage is None:
+            raise _bad("update needs a RolloutStorage whose gae() has run")
+        rows = storage.steps * self.env.num_envs
+        if minibatches > rows:
+            raise _bad(f"{minibatches} minibatches of {rows} stored rows")
+        if self.normalize_advantage:
+            self.fill_adv_stats(storage)
+        out = torch.zeros(epochs * minibatches, len(_lib.POL_LEARN_STATS), dtype=torch.float32, device=wc.device)
+        for ep in range(epochs):
+            perm = torch.randperm(rows, generator=generator, dtype=torch.int32, device=wc.device)
+            for k in range(minibatches):
+                self.backward(storage, perm[k * rows // minibatches:(k + 1) * rows // minibatches], stats=out[ep * minibatches + k],
+                              adv_stats=self.adv_stats)
+                optimizer.step()
+        return out
+
+    def written(self):
+        """the tensors backward() writes: what a caller that captures it in a graph keeps alive"""
+        return [self._grad(p) for p in self.parameters()] + [self.stats, self.adv_stats] + ([self.workspace] if self.workspace is not None else [])
