@@ -678,6 +678,68 @@ int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsid
                        const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
                        void *stream);
 
+/* ---- observation normalisation: rsl_rl's EmpiricalNormalization (empirical_normalization = True) on the policy's input rows,
+ * one state per network over the K columns of its assembled row, applied by the actor's own launch as it loads the blocks.
+ *   stats  [2, K] float64   running mean, running variance        initial 0, 1
+ *   count  [1]    int64     rows seen                              initial 0
+ *   affine [2, K] float32   shift = (float)mean, scale = (float)(1 / (sqrt(var) + eps))  - all the actor reads
+ * (device memory the caller owns; eps > 0, rsl_rl's default 1e-2; the map is rsl_rl's (x - mean) / (std + eps)).
+ *
+ * tsidb_policy_norm_update folds the N current rows into the state of each network given.  Everything is float64 on
+ * x = (double)(float)block[i][e * block_ld[i] + c], the value the actor sees, not the float64 original:
+ *   mean_b, var_b = mean and BIASED variance of the N rows of a column, two passes (the mean, then the centred squares)
+ *   count' = count + N;  rate = N / count'
+ *   delta = mean_b - mean;  mean' = mean + rate * delta
+ *   var'  = var + rate * (var_b - var + delta * (mean_b - mean'))
+ * then affine is rewritten from (mean', var').  until > 0: when count >= until - read FROM DEVICE MEMORY by the kernel, there
+ * is no host read - the call changes nothing, so count stops at the first value >= until.  0 = no limit.
+ * ORDER AND DETERMINISM: the rows are cut into segments of TSIDB_POL_NORM_SEG_ROWS whatever the device; within a segment a
+ * column's rows r are summed per residue r mod 16 in rising r, the 16 sums then in rising residue, for the mean and again for
+ * the centred squares; the segments' (n, mean, M2) are merged in segment order by Chan's formula
+ *   d = mean_s - mean;  mean += d n_s / (n + n_s);  M2 += M2_s + d^2 n n_s / (n + n_s)
+ * by one lane per column.  No atomics, no bit depends on the grid: two calls from the same state write the same bits (a
+ * permutation of the envs may change them).  Two plain asynchronous launches on the given stream, both networks in each (grid
+ * axis = network): no allocation, no host synchronisation, capturable in a graph.
+ * workspace: device memory of tsidb_policy_norm_workspace's bytes - 16 * ceil(N / SEG_ROWS) * (K_actor + K_critic) - rewritten
+ * by every call.  The networks are tsidb_policy_net as tsidb_policy_actor takes them; only the block fields are read, rows at or
+ * beyond N never.  Either network may be NULL (its norm is then ignored).
+ * Rejects (message via tsidb_last_error, nothing launched): both networks NULL; a network whose norm is NULL or has a NULL
+ * stats, count or affine; eps <= 0 or not finite; until < 0; a NULL workspace or one smaller than the query's; n_blocks outside
+ * 1 .. 4, block_cols < 1, block_ld < block_cols, a NULL block, an input total above 512 - what tsidb_policy_actor rejects in a
+ * network's block fields.
+ *
+ * tsidb_policy_actor_norm is tsidb_policy_actor with the map applied on load: for a network whose norm is given (non-NULL, with
+ * a non-NULL affine) column c of the row becomes
+ *   v = ((float)x - shift[c]) * scale[c]     one float32 subtraction, one float32 product, no fused multiply-add
+ *   v = min(max(v, -clip), clip)             where clip > 0 (0 = none)
+ * and THIS v is what the layers see and what actor_input / critic_input receive: a rollout stores the normalised rows, as
+ * rsl_rl does, and tsidb_policy_learn recomputes the actor's outputs from them bit for bit without knowing of the normaliser.
+ * It reads affine and clip only; stats, count, eps and until are the update's.  With both norms NULL (or their affine NULL) it IS
+ * tsidb_policy_actor: the same kernel, the same bits.  tsidb_policy_net is unchanged, so tsidb_policy_learn and its workspace
+ * query cannot see a normaliser.  Rejects what tsidb_policy_actor rejects, a norm for a NULL network, and clip < 0 or NaN.
+ * Not done here: a non-finite input poisons the statistics, as in rsl_rl (no masking); the statistics are per process - a batch
+ * split over ranks is not split-invariant, a rank merge belongs with an all-reduce. */
+enum { TSIDB_POL_NORM_SEG_ROWS = 256 };
+typedef struct tsidb_policy_norm {
+  float *affine;          /* [2, K] float32: shift, scale */
+  float clip;             /* 0 = none */
+  double *stats;          /* [2, K] float64: mean, variance */
+  int64_t *count;         /* [1] */
+  double eps;
+  int64_t until;          /* 0 = no limit */
+} tsidb_policy_norm;
+
+int tsidb_policy_norm_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, size_t *bytes);
+
+int tsidb_policy_norm_update(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                             const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+int tsidb_policy_actor_norm(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                            const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm,
+                            const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                            void *stream);
+
 /* Generalised advantage estimation over T recorded policy steps, float32, one lane per env, backwards from A_T = 0:
  *   r'_t = r_t + gamma V_t timeout_t;   delta_t = r'_t + gamma V_{t+1} (1 - done_t) - V_t;
  *   A_t = delta_t + gamma lam (1 - done_t) A_{t+1};   returns_t = A_t + V_t

@@ -35,7 +35,14 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               the same loss in eager torch over nn.Sequential copies of the networks, the same minibatches, the same optimiser - in
               alternating windows (a process per case), at 4096 and 512 envs, the 256-128 networks; and the first minibatch's loss from
               both on equal weights; default profiles/policy_learner.json.  The kernels' times come from a run of its own:
-              rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --trace ENVS UPDATES"""
+              rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --trace ENVS UPDATES
+    python tools/policy_env.py --actor --normalize [out.json]   --actor's "obs" case with a PolicyNormalizer in the fused actors (two
+              more launches per step, the map inside the actor's) against TorchActor with a torch transcription of rsl_rl's
+              EmpiricalNormalization in front of each network; --learn --normalize: --learn on a rollout recorded with the
+              normaliser (the learner reads the stored, normalised rows; it does not change).  A process per case, four alternating
+              windows, medians, 4096 and 512 envs; default profiles/policy_norm.json (one entry per mode: a run replaces its own).
+              Kernel times: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --actor --normalize --trace ENVS STEPS
+              (a rollout with the normaliser off, then one with it on)"""
 import json
 import sys
 import time
@@ -300,18 +307,45 @@ def actor_nets(env, scan, seed=1):
             torch.full((env.NA,), -2.0, dtype=torch.float32, device=env.device))
 
 
-class TorchActor:
-    """PolicyActor and PolicyEnv.rollout with torch ops in place of the fused launch, into the same RolloutStorage"""
+class TorchNormalizer:
+    """rsl_rl's EmpiricalNormalization, transcribed: float32 buffers, update() then (x - mean) / (std + eps)"""
 
-    def __init__(self, env, actor, critic, actor_inputs, critic_inputs, log_std):
+    def __init__(self, k, device, eps=1e-2):
+        self.eps = eps
+        self.mean, self.var, self.std = torch.zeros(1, k, device=device), torch.ones(1, k, device=device), torch.ones(1, k, device=device)
+        self.count = torch.zeros((), device=device)     # (a device tensor and in-place updates: a captured graph keeps counting)
+
+    def __call__(self, x, update=True):
+        if update:
+            n = x.shape[0]
+            self.count.add_(n)
+            rate = n / self.count
+            var_x, mean_x = torch.var(x, dim=0, unbiased=False, keepdim=True), torch.mean(x, dim=0, keepdim=True)
+            delta = mean_x - self.mean
+            mean = self.mean + rate * delta
+            self.var.add_(rate * (var_x - self.var + delta * (mean_x - mean)))
+            self.mean.copy_(mean)
+            self.std.copy_(torch.sqrt(self.var))
+        return (x - self.mean) / (self.std + self.eps)
+
+
+class TorchActor:
+    """PolicyActor and PolicyEnv.rollout with torch ops in place of the fused launch, into the same RolloutStorage; normalize:
+    a TorchNormalizer in front of each network, updated per step and not by the closing value (PolicyNormalizer's order)"""
+
+    def __init__(self, env, actor, critic, actor_inputs, critic_inputs, log_std, normalize=False):
         self.env, self.actor, self.critic, self.log_std = env, actor, critic, log_std
         self.ai, self.ci = [getattr(env, k) for k in actor_inputs], [getattr(env, k) for k in critic_inputs]
+        width = lambda blocks: sum(b.shape[1] for b in blocks)
+        self.norm = (TorchNormalizer(width(self.ai), env.device), TorchNormalizer(width(self.ci), env.device)) if normalize else None
 
     @torch.no_grad()
     def rollout(self, steps, st):
         env, ls = self.env, self.log_std
         for t in range(steps):
             x, xc = torch.cat(self.ai, dim=1).float(), torch.cat(self.ci, dim=1).float()
+            if self.norm:
+                x, xc = self.norm[0](x), self.norm[1](xc)
             mean = self.actor(x)
             eps = torch.randn_like(mean)
             a = mean + ls.exp() * eps
@@ -320,7 +354,8 @@ class TorchActor:
             st.actor_input[t].copy_(x); st.critic_input[t].copy_(xc); st.action[t].copy_(a); st.mean[t].copy_(mean)
             env.step(a.to(env.dtype))
             st.reward[t].copy_(env.reward); st.done[t].copy_(env.done); st.timeout[t].copy_(env.timeout)
-        st.value[steps].copy_(self.critic(torch.cat(self.ci, dim=1).float()).squeeze(1))
+        xc = torch.cat(self.ci, dim=1).float()
+        st.value[steps].copy_(self.critic(self.norm[1](xc, update=False) if self.norm else xc).squeeze(1))
         return st
 
 
@@ -340,28 +375,30 @@ def captured(fn):
     return lambda keep=fn: g.replay()
 
 
-def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll=3):
-    """policy-steps/s of 16-step rollouts: fused / torch, each eager and graph-captured, in alternating windows of one process"""
-    from tsid_control_amd import PolicyActor, RolloutStorage
+def measure_actor(n, scan, decimation=4, steps=16, window=10, windows=4, preroll=3, normalize=False):
+    """policy-steps/s of 16-step rollouts: fused / torch, each eager and graph-captured, in alternating windows of one process;
+    normalize: a PolicyNormalizer in the fused actors, TorchNormalizers in the torch ones"""
+    from tsid_control_amd import PolicyActor, PolicyNormalizer, RolloutStorage
     delay = delays(n)
     kw = dict(KW, action_scale=0.05, terrain=TERRAIN) if scan else dict(KW, action_scale=0.05)
     run, envs = {}, {}
     for name in ("fused", "fused_graph", "torch", "torch_graph"):
         env = envs[name] = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **kw)
         actor, critic, ai, ci, ls = actor_nets(env, scan)
-        pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls)
+        fused_norm = PolicyNormalizer() if normalize and name.startswith("fused") else None
+        pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls, normalizer=fused_norm)
         st = RolloutStorage(env, pa, steps)
         if name.startswith("fused"):
             fn = lambda env=env, pa=pa, st=st: env.rollout(pa, steps, st)
         else:
-            ta = TorchActor(env, actor, critic, ai, ci, ls)
+            ta = TorchActor(env, actor, critic, ai, ci, ls, normalize=normalize)
             fn = lambda ta=ta, st=st: ta.rollout(steps, st)
         fn = captured(fn) if name.endswith("graph") else fn
         run[name] = lambda k, fn=fn: [fn() for _ in range(k)]
     r = alternate(run, window, windows, preroll, per_call=steps)
     med = r["policy_steps_per_s_median"]
-    return dict(envs=n, actor_input="obs | height_scan" if scan else "obs", decimation=decimation, rollout_steps=steps, window_rollouts=window,
-                windows=windows, **r, fused_over_torch=med["fused"] / med["torch"], fused_graph_over_torch_graph=med["fused_graph"] / med["torch_graph"],
+    return dict(envs=n, actor_input="obs | height_scan" if scan else "obs", normalize=normalize, decimation=decimation, rollout_steps=steps,
+                window_rollouts=window, windows=windows, **r, fused_over_torch=med["fused"] / med["torch"], fused_graph_over_torch_graph=med["fused_graph"] / med["torch_graph"],
                 fused_over_torch_graph=med["fused"] / med["torch_graph"],
                 restarts={k: int(e.episode.sum()) - n for k, e in envs.items()},
                 height_min={k: float(e.wc.qpos[:, 2].min()) for k, e in envs.items()})
@@ -407,22 +444,23 @@ class TorchLearner:
                 opt.step()
 
 
-def learn_setup(n, steps=16, decimation=4):
-    """(storage with its advantages, PolicyLearner, TorchLearner on copies of the same weights) after one recorded rollout"""
-    from tsid_control_amd import PolicyActor, PolicyLearner
+def learn_setup(n, steps=16, decimation=4, normalize=False):
+    """(storage with its advantages, PolicyLearner, TorchLearner on copies of the same weights) after one recorded rollout;
+    normalize: recorded with a PolicyNormalizer, so both learners read the normalised rows the storage holds"""
+    from tsid_control_amd import PolicyActor, PolicyLearner, PolicyNormalizer
     env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delays(n), **dict(KW, action_scale=0.05))
     actor, critic, ai, ci, ls = actor_nets(env, False)
-    pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls)
+    pa = PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls, normalizer=PolicyNormalizer() if normalize else None)
     st = env.rollout(pa, steps)
     st.gae(0.99, 0.95)
     kw = dict(clip=0.2, value_coef=1.0, entropy_coef=0.01)
     return st, PolicyLearner(pa, **kw), TorchLearner(actor, critic, ls, **kw)
 
 
-def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3):
+def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3, normalize=False):
     """updates/s of one PPO update on the same recorded rollout: fused / torch in alternating windows of one process, and the
     loss of the first minibatch from both before either has moved a weight"""
-    st, fused, eager = learn_setup(n)
+    st, fused, eager = learn_setup(n, normalize=normalize)
     rows = st.logp.numel()
     index = torch.randperm(rows, generator=torch.Generator(device="cuda:0").manual_seed(3), dtype=torch.int32, device="cuda:0")[:rows // minibatches]
     stats = fused.backward(st, index).clone()
@@ -438,7 +476,7 @@ def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3):
     r = alternate(run, window, windows, preroll)
     med = r["policy_steps_per_s_median"]
     last = fused.update(st, opts["fused"], 1, minibatches, gens["fused"])
-    return dict(envs=n, rollout_steps=st.steps, rows=rows, epochs=epochs, minibatches=minibatches, minibatch_rows=rows // minibatches,
+    return dict(envs=n, normalize=normalize, rollout_steps=st.steps, rows=rows, epochs=epochs, minibatches=minibatches, minibatch_rows=rows // minibatches,
                 window_updates=window, windows=windows, updates_per_s_median=med, updates_per_s_all=r["all"],
                 ms_per_update={k: 1e3 / v for k, v in med.items()}, fused_over_torch=med["fused"] / med["torch"],
                 first_minibatch=dict(loss_fused=float(stats[5]), loss_torch=loss_torch, loss_difference=float(stats[5]) - loss_torch,
@@ -447,7 +485,47 @@ def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3):
                 stats_after=dict(zip(_lib.POL_LEARN_STATS, (float(x) for x in last[-1]))))
 
 
+def main_normalize(which, args):
+    """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
+    4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
+    import os
+    import subprocess
+    from tsid_control_amd import PolicyActor, PolicyNormalizer
+    if args and args[0] == "--trace":
+        n, k = int(args[1]), int(args[2])
+        if which == "actor":                  # the normaliser off, then on: k_policy_actor beside k_policy_actor_norm and the update's two
+            env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=4, **dict(KW, action_scale=0.05))
+            for nz in (None, PolicyNormalizer()):
+                actor, critic, ai, ci, ls = actor_nets(env, False)
+                env.rollout(PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls, normalizer=nz), k).gae(0.99, 0.95)
+        else:
+            st, fused, _ = learn_setup(n, normalize=True)
+            opt = torch.optim.Adam(fused.parameters(), lr=1e-4)
+            for _ in range(k):
+                fused.update(st, opt, 5, 4)
+        torch.cuda.synchronize()
+        return
+    if args and args[0] == "--case":
+        n = int(args[1])
+        print(json.dumps(measure_actor(n, False, normalize=True) if which == "actor" else measure_learn(n, normalize=True)))
+        return
+    out_path = args[0] if args else "profiles/policy_norm.json"
+    runs = {}
+    if os.path.exists(out_path):
+        with open(out_path) as f:
+            runs = json.load(f).get("runs", {})
+    runs[which] = []
+    for n in (4096, 512):
+        r = subprocess.run([sys.executable, sys.argv[0], "--" + which, "--normalize", "--case", str(n)], capture_output=True, text=True, check=True)
+        runs[which].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    report(out_path, actor="obs -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU", normalizer="eps 1e-2, no clip, both networks",
+           runs=runs)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] in ("--actor", "--learn") and sys.argv[2] == "--normalize":
+        main_normalize(sys.argv[1][2:], sys.argv[3:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--learn":
         if len(sys.argv) > 2 and sys.argv[2] == "--trace":
             st, fused, _ = learn_setup(int(sys.argv[3]))

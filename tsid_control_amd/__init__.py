@@ -19,6 +19,9 @@ def __getattr__(name):
     if name in ("PolicyActor", "RolloutStorage", "rollout_written"):
         from . import policy_actor
         return getattr(policy_actor, name)
+    if name == "PolicyNormalizer":
+        from .policy_normalizer import PolicyNormalizer
+        return PolicyNormalizer
     if name == "PolicyLearner":
         from .policy_learner import PolicyLearner
         return PolicyLearner

@@ -17,7 +17,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_randomize", "tsidb_policy_perturb", "tsidb_policy_reset_noise",
            "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs",
            "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan",
-           "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn"]
+           "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn",
+           "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -74,6 +75,8 @@ POL_ACTOR_STREAMS = (21, 22)
 # the policy learner (include/tsidb.h tsidb_policy_learn): the rows of a segment of the weight gradient's sums, and the stats
 POL_LEARN_SEG_ROWS = 512
 POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "loss", "rows", "bad_indices")
+# the policy normaliser (include/tsidb.h tsidb_policy_norm_update): the rows of a segment of the batch statistics
+POL_NORM_SEG_ROWS = 256
 
 
 def pol_teach_nobs(na):
@@ -119,6 +122,12 @@ class PolicyActorOut(C.Structure):
     """tsidb_policy_actor_out (include/tsidb.h): what tsidb_policy_actor writes, every pointer optional"""
     _fields_ = [("action", C.c_void_p), ("action32", C.c_void_p), ("mean", C.c_void_p), ("logp", C.c_void_p), ("value", C.c_void_p),
                 ("actor_input", C.c_void_p), ("critic_input", C.c_void_p)]
+
+
+class PolicyNorm(C.Structure):
+    """tsidb_policy_norm (include/tsidb.h): one network's normaliser state and settings"""
+    _fields_ = [("affine", C.c_void_p), ("clip", C.c_float), ("stats", C.c_void_p), ("count", C.c_void_p), ("eps", C.c_double),
+                ("until", C.c_int64)]
 
 
 class PolicyLearnBatch(C.Structure):
@@ -213,6 +222,9 @@ def load(path=None):
     L.tsidb_policy_gae.argtypes = [vp, C.c_int, vp, vp, i32p, vp, C.c_float, C.c_float, vp, vp, vp]
     L.tsidb_policy_learn_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]
+    L.tsidb_policy_norm_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.tsidb_policy_actor_norm.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

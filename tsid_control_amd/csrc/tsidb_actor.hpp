@@ -124,8 +124,16 @@ __device__ __forceinline__ void act_layers(const ActorNet &net, float *const X[2
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) {
+// the input normalisation of a launch (k_policy_actor_norm): per network the float32 pair affine [2, K] = shift, scale that
+// tsidb_policy_norm_update keeps (tsidb_norm.hpp; NULL = this network's rows stay raw) and the clamp (0 = none)
+struct ActorNorm {
+  const float *affine[2];
+  float clip[2];
+};
+
+// NORM = false is k_policy_actor as it was before there was a normaliser, instruction for instruction: `nm` is not touched
+template <typename T, bool NORM>
+__device__ __forceinline__ void policy_actor_body(const ActorArgs &a, const ActorNorm *nm) {
   extern __shared__ float act_lds[];
   const int which = blockIdx.y + a.first;
   const ActorNet &net = a.net[which];
@@ -144,6 +152,14 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) 
       float v = 0.f;
       if (e < a.n) {
         v = (float)src[(size_t)e * ld + c];
+        if constexpr (NORM) {
+          const float *aff = nm->affine[which];
+          if (aff) {                                 // one float32 subtraction, one float32 product: nothing to contract
+            const float clip = nm->clip[which];
+            v = (v - aff[off + c]) * aff[net.K + off + c];
+            if (clip > 0.f) v = fminf(fmaxf(v, -clip), clip);
+          }
+        }
         if (net.input) net.input[(size_t)e * net.K + off + c] = v;
       }
       X[0][r * LD + off + c] = v;
@@ -194,6 +210,17 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) 
     }
     a.logp[e0 + tid] = -s - (float)(0.5 * NA * 1.8378770664093453);   // ln 2 pi
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor(ActorArgs a) {
+  policy_actor_body<T, false>(a, nullptr);
+}
+
+// the same launch with the input rows normalised on load: what goes to LDS and to net.input is (x - shift) * scale, clamped
+template <typename T>
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_actor_norm(ActorArgs a, ActorNorm nm) {
+  policy_actor_body<T, true>(a, &nm);
 }
 
 // ---------------------------------------------------------------------------- generalised advantage estimation

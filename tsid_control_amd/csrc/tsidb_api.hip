@@ -6,6 +6,7 @@
 #include "tsidb_policy.hpp"
 #include "tsidb_actor.hpp"
 #include "tsidb_learner.hpp"
+#include "tsidb_norm.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -680,6 +681,7 @@ static_assert((int)CTRL_POSITION == TSIDB_CTRL_POSITION && (int)CTRL_MOTOR == TS
               "include/tsidb.h and the kernels agree on the ctrl modes");
 static_assert(POL_NT == TSIDB_POL_NT && POL_HIST == TSIDB_POL_HIST && POL_NPRIV == TSIDB_POL_NPRIV && (NA != 20 || POL_NOBS == TSIDB_POL_NOBS),
               "include/tsidb.h and the kernels agree on the policy environment's rows");
+static_assert(NORM_SEG == TSIDB_POL_NORM_SEG_ROWS && NORM_SEG % 16 == 0, "include/tsidb.h and the kernels agree on the normaliser's segments");
 static_assert(POL_MAXSCAN == TSIDB_POL_MAXSCAN, "include/tsidb.h and the kernels agree on the height scan's size");
 static_assert(POL_TEACH_NT == TSIDB_POL_TEACH_NT && (NA != 20 || POL_TEACH_NOBS == TSIDB_POL_TEACH_NOBS),
               "include/tsidb.h and the kernels agree on the teacher's rows");
@@ -731,6 +733,7 @@ struct tsidb_ctx {
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
   bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
+  bool actor_norm_big_lds = false;           // tsidb_policy_actor_norm: k_policy_actor_norm's likewise
   bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
   std::string err;
 };
@@ -1522,13 +1525,12 @@ static ActorNet actor_net(const tsidb_policy_net *p, const char *who, const char
   return n;
 }
 
-extern "C" {
-
-int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
-                       const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
-                       void *stream) {
+// tsidb_policy_actor and tsidb_policy_actor_norm: one body; without a normaliser the launch is k_policy_actor's, as ever
+static int policy_actor_call(tsidb_handle h, const char *who, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor,
+                             const tsidb_policy_net *critic, const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm,
+                             const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                             void *stream) {
   GUARD_BEGIN
-  const char *who = "tsidb_policy_actor: ";
   hipStream_t s = (hipStream_t)stream;
   if (!actor && !critic) throw std::string(who) + "null actor (only a call with a critic may leave it out)";
   if (!out) throw std::string(who) + "null out";
@@ -1551,17 +1553,118 @@ int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsid
   a.n = h->num_envs; a.LD = act_ld(widest);
   a.action = out->action; a.action32 = out->action32; a.mean = out->mean; a.logp = out->logp; a.value = out->value;
   a.log_std = (const float *)log_std; a.seed = seed; a.env_offset = env_offset;
+  ActorNorm nm = {};
+  const tsidb_policy_norm *norms[2] = {actor_norm, critic_norm};
+  for (int y = 0; y < 2; y++) {
+    const tsidb_policy_norm *p = norms[y];
+    if (!p) continue;
+    if (!(y ? critic : actor)) throw std::string(who) + (y ? "critic_norm without a critic" : "actor_norm without an actor");
+    if (!(p->clip >= 0.f)) throw std::string(who) + (y ? "critic" : "actor") + "_norm: clip must be >= 0 (0 = none)";
+    nm.affine[y] = p->affine; nm.clip[y] = p->clip;
+  }
+  const bool normed = nm.affine[0] || nm.affine[1];
   const size_t lds = act_lds_bytes(a.LD);
+  const dim3 grid((h->num_envs + ACT_TILE - 1) / ACT_TILE, actor && critic ? 2 : 1);
   with_dtype(h->dtype, [&](auto t) {
     using T = decltype(t);
-    if (lds > 65536 && !h->actor_big_lds) {   // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle)
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_actor<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)act_lds_bytes(act_ld(ACT_MAXW))));
-      h->actor_big_lds = true;
+    bool &big = normed ? h->actor_norm_big_lds : h->actor_big_lds;
+    if (lds > 65536 && !big) {   // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle and kernel)
+      const void *fn = normed ? reinterpret_cast<const void *>(&k_policy_actor_norm<T>) : reinterpret_cast<const void *>(&k_policy_actor<T>);
+      HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
+      big = true;
     }
     h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_actor<T>, dim3((h->num_envs + ACT_TILE - 1) / ACT_TILE, actor && critic ? 2 : 1), dim3(WAVE * ACT_WAVES), lds, s, a);
+    if (normed) hipLaunchKernelGGL(k_policy_actor_norm<T>, grid, dim3(WAVE * ACT_WAVES), lds, s, a, nm);
+    else hipLaunchKernelGGL(k_policy_actor<T>, grid, dim3(WAVE * ACT_WAVES), lds, s, a);
   });
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+// the block fields of a network as the normaliser's update takes them: actor_net's checks of them, nothing else of the struct
+static NormNet norm_net(const tsidb_policy_net *p, const char *who, const char *name) {
+  const std::string pre = std::string(who) + name + ": ";
+  if (p->n_blocks < 1 || p->n_blocks > ACT_MAXB) throw pre + "n_blocks must be 1 .. 4";
+  NormNet n = {};
+  n.n_blocks = p->n_blocks;
+  long total = 0;
+  for (int i = 0; i < p->n_blocks; i++) {
+    if (!p->block[i]) throw pre + "null input block";
+    if (p->block_cols[i] < 1 || p->block_cols[i] > ACT_MAXW) throw pre + "block_cols must be 1 .. 512";
+    if (p->block_ld[i] < p->block_cols[i]) throw pre + "block_ld < block_cols";
+    n.blk[i] = p->block[i]; n.blk_ld[i] = p->block_ld[i]; n.blk_cols[i] = p->block_cols[i];
+    total += p->block_cols[i];
+  }
+  if (total < 1 || total > ACT_MAXW) throw pre + "the input blocks must hold 1 .. 512 columns in total";
+  n.K = (int)total;
+  return n;
+}
+
+static int norm_segments(int n) { return (n + NORM_SEG - 1) / NORM_SEG; }
+
+extern "C" {
+
+int tsidb_policy_actor(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                       void *stream) {
+  return policy_actor_call(h, "tsidb_policy_actor: ", bufs, actor, critic, nullptr, nullptr, out, log_std, seed, env_offset, flags, stream);
+}
+
+int tsidb_policy_actor_norm(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                            const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm,
+                            const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
+                            void *stream) {
+  return policy_actor_call(h, "tsidb_policy_actor_norm: ", bufs, actor, critic, actor_norm, critic_norm, out, log_std, seed, env_offset,
+                           flags, stream);
+}
+
+int tsidb_policy_norm_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, size_t *bytes) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_norm_workspace: ";
+  if (!actor && !critic) throw std::string(who) + "null actor and critic";
+  if (!bytes) throw std::string(who) + "null bytes";
+  size_t cols = 0;
+  if (actor) cols += norm_net(actor, who, "actor").K;
+  if (critic) cols += norm_net(critic, who, "critic").K;
+  *bytes = (size_t)norm_segments(h->num_envs) * 2 * cols * sizeof(double);
+  GUARD_END
+}
+
+int tsidb_policy_norm_update(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                             const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_norm_update: ";
+  hipStream_t s = (hipStream_t)stream;
+  if (!actor && !critic) throw std::string(who) + "null actor and critic";
+  NormArgs a = {};
+  a.n = h->num_envs; a.nseg = norm_segments(h->num_envs); a.first = actor ? 0 : 1;
+  size_t need = 0;
+  int widest = 0;
+  for (int y = 0; y < 2; y++) {
+    const tsidb_policy_net *p = y ? critic : actor;
+    const tsidb_policy_norm *q = y ? critic_norm : actor_norm;
+    const char *name = y ? "critic" : "actor";
+    if (!p) continue;
+    NormNet &n = a.net[y];
+    n = norm_net(p, who, name);
+    if (!q || !q->stats || !q->count || !q->affine) throw std::string(who) + name + ": no normaliser (norm, stats, count, affine)";
+    if (!(q->eps > 0.0) || !std::isfinite(q->eps)) throw std::string(who) + name + ": eps must be > 0";
+    if (q->until < 0) throw std::string(who) + name + ": until must be >= 0 (0 = no limit)";
+    n.stats = q->stats; n.count = (long long *)q->count; n.affine = q->affine; n.eps = q->eps; n.until = q->until;
+    n.part = (double *)workspace + need / sizeof(double);
+    need += (size_t)a.nseg * 2 * n.K * sizeof(double);
+    if (n.K > widest) widest = n.K;
+  }
+  if (!workspace) throw std::string(who) + "null workspace";
+  if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
+  const int nets = actor && critic ? 2 : 1;
+  h->note_stream(s);
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_policy_norm_partial<T>, dim3((widest + 15) / 16, a.nseg, nets), dim3(256), 0, s, a);
+  });
+  hipLaunchKernelGGL(k_policy_norm_merge, dim3(1, nets), dim3(NORM_MERGE_LANES), 0, s, a);
   HIP_OK(hipGetLastError());
   GUARD_END
 }

@@ -124,12 +124,14 @@ class PolicyActor:
     blocks of the input row, up to 4 and 512 columns in total - "obs", "priv", "height_scan", "teacher_obs", "command", or any
     [N, k] tensor of the env's dtype (a strided row view is fine).  log_std: [NA] float32, read in place (None = zeros, kept as
     self.log_std).  seed: of the action noise (None = the env's seed); env_offset (None = the randomisation's, else 0).
+    normalizer: a PolicyNormalizer (policy_normalizer.py) - running mean and variance of each network's input row, applied as
+    the launch loads the row; actor_input / critic_input then hold the normalised rows.  None = the raw rows, as ever.
 
     Tensors, written by act(): action [N, NA] (the env's dtype: hand it to env.step), action32, mean [N, NA], logp [N], value [N]
     (None without a critic), actor_input [N, K_actor], critic_input [N, K_critic] (float32)."""
 
     def __init__(self, env, actor, critic=None, actor_inputs=("obs",), critic_inputs=None, log_std=None, seed=None, env_offset=None,
-                 activation=None):
+                 activation=None, normalizer=None):
         wc = env.wc
         self.env, self.NA = env, env.NA
         N, NA = env.num_envs, env.NA
@@ -157,6 +159,13 @@ class PolicyActor:
         self.value = f32(N) if critic is not None else None
         self.actor_input = f32(N, self.actor_net.K)
         self.critic_input = f32(N, self.critic_net.K) if critic is not None else None
+        self.normalizer = None
+        if normalizer is not None:
+            from .policy_normalizer import PolicyNormalizer
+            if not isinstance(normalizer, PolicyNormalizer):
+                raise _bad(f"normalizer must be a PolicyNormalizer or None, got {type(normalizer).__name__}")
+            normalizer._attach(self)
+            self.normalizer = normalizer
 
     def _launch(self, sample, actor=True, critic=True, action=None, action32=None, mean=None, logp=None, value=None, actor_input=None,
                 critic_input=None):
@@ -166,21 +175,36 @@ class PolicyActor:
         out = _lib.PolicyActorOut(p(action), p(action32), p(mean), p(logp), p(value), p(actor_input), p(critic_input))
         self._out = out      # (alive until the next call: the library copies it during the call, a recorder may look later)
         cn = self.critic_net if critic else None
-        wc._call("tsidb_policy_actor", C.byref(self.env._bufs), C.byref(self.actor_net.struct) if actor else None,
-                 C.byref(cn.struct) if cn is not None else None, C.byref(out), C.c_void_p(self.log_std.data_ptr()),
-                 C.c_uint64(self.seed), C.c_uint64(self.env_offset), _lib.POL_ACTOR_SAMPLE if sample else 0, wc._stream())
+        nets = (C.byref(self.actor_net.struct) if actor else None, C.byref(cn.struct) if cn is not None else None)
+        rest = (C.byref(out), C.c_void_p(self.log_std.data_ptr()), C.c_uint64(self.seed), C.c_uint64(self.env_offset),
+                _lib.POL_ACTOR_SAMPLE if sample else 0, wc._stream())
+        nz = self.normalizer
+        if nz is None:
+            wc._call("tsidb_policy_actor", C.byref(self.env._bufs), *nets, *rest)
+        else:
+            wc._call("tsidb_policy_actor_norm", C.byref(self.env._bufs), *nets, C.byref(nz.actor.struct) if actor else None,
+                     C.byref(nz.critic.struct) if cn is not None and nz.critic is not None else None, *rest)
+
+    def observe(self):
+        """with a normaliser in training mode: its update() on the env's current tensors - what act() and every step of
+        PolicyEnv.rollout do before they evaluate; else nothing"""
+        if self.normalizer is not None and self.normalizer.training:
+            self.normalizer.update()
 
     def act(self, deterministic=False):
         """One launch on the env's current tensors: the actor, the critic, and unless deterministic the sample.  Returns a dict
         of the preallocated tensors action, action32, mean, logp, value (updated in place by every call; value None without a
-        critic).  deterministic: action = mean, logp = the density at the mean."""
+        critic).  deterministic: action = mean, logp = the density at the mean.  With a normaliser in training mode its
+        update() comes first (two more launches), and the rows are normalised with the updated statistics."""
+        self.observe()
         self._launch(not deterministic, action=self.action, action32=self.action32, mean=self.mean, logp=self.logp, value=self.value,
                      actor_input=self.actor_input, critic_input=self.critic_input)
         return dict(action=self.action, action32=self.action32, mean=self.mean, logp=self.logp, value=self.value)
 
     def written(self):
-        """the tensors act() writes"""
-        return [t for t in (self.action, self.action32, self.mean, self.logp, self.value, self.actor_input, self.critic_input) if t is not None]
+        """the tensors act() writes, the normaliser's state among them"""
+        own = [t for t in (self.action, self.action32, self.mean, self.logp, self.value, self.actor_input, self.critic_input) if t is not None]
+        return own + (self.normalizer.written() if self.normalizer is not None else [])
 
 
 class RolloutStorage:
@@ -221,3 +245,5 @@ def rollout_written(storage):
     captures a rollout in a graph keeps alive, and rewinds after its warm-up if it compares runs."""
     yield from storage.tensors()
     yield storage.actor.action
+    if storage.actor.normalizer is not None:
+        yield from storage.actor.normalizer.written()

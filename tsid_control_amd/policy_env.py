@@ -557,6 +557,8 @@ class PolicyEnv:
         """`steps` policy steps with `actor` (a PolicyActor on this env) in the loop: per step one actor launch - networks, sample,
         log-probability and value on the current observation, written straight into slot t of the storage - then step(action) and
         three device copies of reward, done and timeout; last, one critic-only launch on the final observation into value[steps].
+        With a PolicyNormalizer in training mode every step first updates the statistics with its observation; the last launch
+        normalises with the statistics as they are and does not update (the next rollout's first step counts that observation).
         storage: a RolloutStorage of this env, actor and length to reuse (None = a new one); returned.  Everything stays on the
         current stream with no host synchronisation, so a whole rollout can be captured in a graph (policy_actor.rollout_written
         lists what it writes beyond written()).  storage.gae(gamma, lam) then gives the advantages and returns."""
@@ -571,6 +573,7 @@ class PolicyEnv:
             raise _lib.TsidbError("PolicyEnv.rollout: storage must be a RolloutStorage of this env, this actor and this many steps")
         st = storage
         for t in range(steps):
+            actor.observe()
             actor._launch(True, action=actor.action, action32=st.action[t], mean=st.mean[t], logp=st.logp[t], value=st.value[t],
                           actor_input=st.actor_input[t], critic_input=st.critic_input[t] if st.critic_input is not None else None)
             self.step(actor.action)
