@@ -749,8 +749,8 @@ int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done
                      float gamma, float lam, float *advantage, float *returns, void *stream);
 
 /* ---- the update's side of a PPO iteration: the loss of one minibatch of stored rollout rows and its gradient with respect to
- * every weight and bias of the actor and the critic and to log_std.  The optimiser, gradient clipping, schedules and all-reduces
- * stay the caller's, on the gradient buffers.  Plain asynchronous launches on the given stream (three kernels): no allocation, no
+ * every weight and bias of the actor and the critic and to log_std.  The optimiser, gradient clipping and schedules stay the
+ * caller's unless PolicyOptimizer is used (tsidb_policy_opt_step below), all-reduces stay the caller's, on the gradient buffers.  Plain asynchronous launches on the given stream (three kernels): no allocation, no
  * host synchronisation, capturable in a graph.  Hot path: v_mfma_f32_16x16x4_f32, float32 throughout.  NO ATOMICS: every sum has
  * one fixed order, the rows are cut into segments of TSIDB_POL_LEARN_SEG_ROWS whatever the device, so two calls on the same
  * inputs write the same bits.
@@ -815,6 +815,87 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
                        const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
                        const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
                        const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream);
+
+/* ---- the step's side of a PPO iteration: what rsl_rl runs per minibatch behind the loss - its adaptive step size from the
+ * exact Gaussian KL (schedule = "adaptive"), torch's clip_grad_norm_ over all parameters, and torch.optim.Adam's default
+ * single-tensor step - as three plain asynchronous launches on the given stream: no atomics, no counters, no allocation, no
+ * host synchronisation, capturable in a graph; every sum has one fixed order, two calls from the same state write the same bits.
+ *
+ * The parameter set, P elements in this order: the actor's layers (weight, then bias where the network has one), the critic's
+ * layers, log_std [NA].  Weights and biases are the pointers of tsidb_policy_net and ARE WRITTEN IN PLACE ("read in place"
+ * turned round: the next tsidb_policy_actor / tsidb_policy_learn launch computes with the step); the gradients - actor_grads,
+ * critic_grads, log_std_grad, as tsidb_policy_learn wrote them - are READ ONLY, the clip factor is applied inside the step.
+ * State, device memory the caller owns (tsidb_policy_opt_state):
+ *   moments [2, P] float32   exp_avg then exp_avg_sq, the pieces in the order above        initial 0
+ *   lr [1] float32, step [1] int64 (initial 0), log_std_old [NA] float32 (the rollout's log_std; the schedule alone reads it),
+ *   stats [TSIDB_POL_OPT_NSTATS] float32, written by every call.
+ *
+ * One call, float32 unless said otherwise:
+ * NORM.  norm = sqrt(sum g^2) over every gradient element, squares and sums in float64.  Each piece is cut into chunks of
+ * TSIDB_POL_OPT_CHUNK elements (the last one ragged; elements beyond it count as 0).  A chunk's sum: element 4 t + i belongs to
+ * slot t of TSIDB_POL_OPT_LANES; slot sum = ((g_0^2 + g_1^2) + g_2^2) + g_3^2; then the slots are halved,
+ * slot[t] += slot[t + s] for t < s, s = LANES / 2, LANES / 4 .. 1.  The chunk sums are added in chunk order (piece after piece).
+ *   coef = min(1, max_norm / (norm + 1e-6)) in float64, cast once (a NaN stays a NaN); max_norm = 0: coef = 1, no clipping.
+ * KL, only with desired_kl > 0, over the M rows of the learner's last minibatch (tsidb_policy_opt_kl): mu = the first floats of
+ * the learner's workspace, mu[m * NA + a]; mu_old = mean[index[m] * NA + a] of the rollout's stored [rows, NA] means; s =
+ * log_std, s_old = log_std_old; in float64 from those float32 values
+ *   kl_m = sum_a ( s_a - s_old_a + (exp(2 s_old_a) + (mu_old - mu)^2) / (2 exp(2 s_a)) - 1/2 )   in rising a;   kl = (sum_m kl_m) / M
+ * Rows are cut into segments of TSIDB_POL_LEARN_SEG_ROWS; slot t of a segment = kl of its row t + kl of its row t + LANES, the
+ * slots halved as above, the segments added in order.  An index outside [0, rows) contributes nothing; the mean stays over M.
+ * STEP SIZE, rsl_rl's rule, before the step that uses it; the comparisons on the float64 kl, lr in IEEE float32, read from and
+ * written to device memory:
+ *   kl > 2 desired_kl: lr = max(lr_min, lr / 1.5f);   else 0 < kl < desired_kl / 2: lr = min(lr_max, lr * 1.5f)
+ * ADAM.  t = step + 1, g = coef * grad;  m += (g - m) (1 - b1);  v = b2 v + (1 - b2) g^2;  bc1 = 1 - b1^t, bc2 = 1 - b2^t (float64);
+ *   p -= (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))     with lr / bc1 and sqrt(bc2) formed in float64 and cast once;
+ * then step = t.  No weight decay, no amsgrad.
+ * SKIP.  skip_nonfinite set and norm (or, with the schedule, kl) not finite: parameters, moments, lr and step keep their bits,
+ * stats[5] = 1.  Clear: the arithmetic runs as torch's would and poisons the parameters.
+ * stats: 0 norm  1 coef  2 kl (0 without the schedule)  3 lr used  4 step after the call  5 skipped  6 rows that entered the KL
+ *   7 the direction lr moved, -1 / 0 / +1 (0 where a bound held it)
+ *
+ * workspace: device memory of at least tsidb_policy_opt_workspace's bytes (a function of the networks and of M, the rows of the
+ * KL; M = 0 without the schedule), rewritten by every call: nchunks + 2 nseg float64 partial sums (nchunks = the chunks of all
+ * pieces, nseg = ceil(M / TSIDB_POL_LEARN_SEG_ROWS)), then norm and kl in float64 as they were formed, before stats' float32
+ * cast; the rest is the library's.  kl may be NULL without the schedule.
+ * Rejects (message via tsidb_last_error, nothing launched): a NULL actor, actor_grads, cfg, state, log_std, log_std_grad,
+ * moments, lr, step, stats or workspace; critic_grads NULL with a critic; what tsidb_policy_learn rejects in a network; a NULL
+ * weight gradient, a NULL bias gradient where the bias exists; b1 or b2 outside [0, 1); eps <= 0; max_norm < 0; desired_kl < 0;
+ * lr_min <= 0 or lr_min > lr_max; the schedule without kl, mean, index, mu or log_std_old, or with M < 1 or rows < 1; a
+ * workspace smaller than the query's. */
+enum { TSIDB_POL_OPT_CHUNK = 1024, TSIDB_POL_OPT_LANES = 256, TSIDB_POL_OPT_NSTATS = 8 };
+typedef struct tsidb_policy_opt_cfg {
+  double b1;
+  double b2;
+  double eps;
+  double max_norm;           /* 0 = no clipping */
+  double desired_kl;         /* 0 = no schedule */
+  float lr_min;
+  float lr_max;
+  int skip_nonfinite;
+} tsidb_policy_opt_cfg;
+
+typedef struct tsidb_policy_opt_state {
+  float *moments;            /* [2, P] */
+  float *lr;                 /* [1] */
+  int64_t *step;             /* [1] */
+  const float *log_std_old;  /* [NA] */
+  float *stats;              /* [8] */
+} tsidb_policy_opt_state;
+
+typedef struct tsidb_policy_opt_kl {
+  const float *mu;           /* the learner's workspace: [Mp, NA] first */
+  const float *mean;         /* [rows, NA] the rollout's stored means */
+  const int32_t *index;      /* [M] device */
+  int rows;
+  int M;
+} tsidb_policy_opt_kl;
+
+int tsidb_policy_opt_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes);
+
+int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                          const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads, float *log_std,
+                          const float *log_std_grad, const tsidb_policy_opt_cfg *cfg, const tsidb_policy_opt_state *state,
+                          const tsidb_policy_opt_kl *kl, void *workspace, size_t workspace_bytes, void *stream);
 
 /* probe of formulation.computeProblemData's rigid-body terms (main.py:119): M [N,26,26],
  * hbias [N,26], Jcom [N,3,26], Jf [N,2,6,26] (LOCAL), oMf [N,2,12], com [N,3].  Test/debug use. */

@@ -42,7 +42,14 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               normaliser (the learner reads the stored, normalised rows; it does not change).  A process per case, four alternating
               windows, medians, 4096 and 512 envs; default profiles/policy_norm.json (one entry per mode: a run replaces its own).
               Kernel times: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --actor --normalize --trace ENVS STEPS
-              (a rollout with the normaliser off, then one with it on)"""
+              (a rollout with the normaliser off, then one with it on)
+    python tools/policy_env.py --learn --optimizer [out.json]   what follows the gradients in rsl_rl's PPO iteration - the adaptive
+              step size from the exact KL, clip_grad_norm_, Adam - on --learn's recorded rollout, 5 epochs x 4 minibatches, updates/s of
+              PolicyLearner with (plain) torch.optim.Adam alone, --learn's fused path; (a) clip_grad_norm_ + torch.optim.Adam + rsl_rl's
+              rule with its host read of the KL; (b) the same with the rule written sync-free on a tensor lr (Adam capturable);
+              (c) PolicyOptimizer; (d) (c) with the whole update() captured in one graph - each on a learner of its own over equal
+              weights, in alternating windows (a process per case), at 4096 and 512 envs; default profiles/policy_optimizer.json.
+              Kernel times: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --optimizer --trace ENVS UPDATES"""
 import json
 import sys
 import time
@@ -485,6 +492,109 @@ def measure_learn(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3, n
                 stats_after=dict(zip(_lib.POL_LEARN_STATS, (float(x) for x in last[-1]))))
 
 
+OPT = dict(lr=1e-3, desired_kl=0.01, max_grad_norm=1.0, lr_min=1e-5, lr_max=1e-2)      # rsl_rl's defaults
+
+
+def torch_kl(st, learner, index, log_std_old):
+    """rsl_rl's KL between the rollout's policy and the current one on the minibatch of the learner's last backward(), torch ops"""
+    mu = learner.outputs(int(index.shape[0]))[0]
+    old = st.mean.reshape(-1, mu.shape[1])[index.long()]
+    s = learner.actor.log_std
+    return (s - log_std_old + (torch.exp(2 * log_std_old) + (old - mu) ** 2) / (2 * torch.exp(2 * s)) - 0.5).sum(1).mean()
+
+
+def torch_update(st, learner, adam, epochs, minibatches, generator, host_read):
+    """PolicyLearner.update()'s loop with what rsl_rl runs between the gradients and the step in torch: the adaptive rule - with
+    its host read of the KL, or sync-free on the tensor adam holds as lr - clip_grad_norm_, adam.step()"""
+    rows, d = st.logp.numel(), OPT["desired_kl"]
+    learner.fill_adv_stats(st)
+    log_std_old = learner.actor.log_std.detach().clone()
+    params, group = learner.parameters(), adam.param_groups[0]
+    for _ in range(epochs):
+        perm = torch.randperm(rows, generator=generator, dtype=torch.int32, device=st.logp.device)
+        for k in range(minibatches):
+            index = perm[k * rows // minibatches:(k + 1) * rows // minibatches]
+            learner.backward(st, index, adv_stats=learner.adv_stats)
+            kl = torch_kl(st, learner, index, log_std_old)
+            lr = group["lr"]
+            if host_read:
+                kl = float(kl)
+                if kl > 2 * d:
+                    group["lr"] = max(OPT["lr_min"], lr / 1.5)
+                elif 0 < kl < d / 2:
+                    group["lr"] = min(OPT["lr_max"], lr * 1.5)
+            else:
+                lr.copy_(torch.where(kl > 2 * d, (lr / 1.5).clamp(min=OPT["lr_min"]),
+                                     torch.where((kl > 0) & (kl < d / 2), (lr * 1.5).clamp(max=OPT["lr_max"]), lr)))
+            torch.nn.utils.clip_grad_norm_(params, OPT["max_grad_norm"])
+            adam.step()
+
+
+def measure_optimizers(n, epochs=5, minibatches=4, window=40, windows=4, preroll=3):
+    """updates/s of one PPO update on the same recorded rollout (a learner, a storage and weights of its own per runner, equal at
+    the start): plain / a / b / c / d of this file's header, in alternating windows of one process"""
+    from tsid_control_amd import PolicyOptimizer
+    names = ("plain", "a_torch_host_read", "b_torch_tensor_lr", "c_policy_optimizer", "d_policy_optimizer_graph")
+    sets = {k: learn_setup(n)[:2] for k in names}
+    dev = "cuda:0"
+    gens = {k: torch.Generator(device=dev).manual_seed(5) for k in names}
+    adam = dict(plain=torch.optim.Adam(sets["plain"][1].parameters(), lr=1e-4),
+                a_torch_host_read=torch.optim.Adam(sets["a_torch_host_read"][1].parameters(), lr=OPT["lr"]),
+                b_torch_tensor_lr=torch.optim.Adam(sets["b_torch_tensor_lr"][1].parameters(), lr=torch.tensor(OPT["lr"], device=dev), capturable=True))
+    fused = {k: PolicyOptimizer(sets[k][1], **OPT) for k in names[3:]}
+    up = lambda k, opt, gen: sets[k][1].update(sets[k][0], opt, epochs, minibatches, gen)
+    run = dict(plain=lambda c: [up("plain", adam["plain"], gens["plain"]) for _ in range(c)],
+               a_torch_host_read=lambda c: [torch_update(*sets["a_torch_host_read"], adam["a_torch_host_read"], epochs, minibatches, gens["a_torch_host_read"], True)
+                                            for _ in range(c)],
+               b_torch_tensor_lr=lambda c: [torch_update(*sets["b_torch_tensor_lr"], adam["b_torch_tensor_lr"], epochs, minibatches, gens["b_torch_tensor_lr"], False)
+                                            for _ in range(c)],
+               c_policy_optimizer=lambda c: [up("c_policy_optimizer", fused["c_policy_optimizer"], gens["c_policy_optimizer"]) for _ in range(c)])
+    capture = "held"
+    try:                                   # the whole update() - randperm on the default generator included - as one graph
+        k = names[4]
+        up(k, fused[k], None)              # (the workspaces and every .grad exist before the capture)
+        replay = captured(lambda: up(k, fused[k], None))
+        run[k] = lambda c: [replay() for _ in range(c)]
+    except Exception as e:                 # noqa: BLE001 - reported, the other four are measured without it
+        capture = f"failed: {type(e).__name__}: {e}"
+    r = alternate(run, window, windows, preroll)
+    med = r["policy_steps_per_s_median"]
+    c = fused["c_policy_optimizer"]
+    c.log = torch.zeros(epochs * minibatches, 8, dtype=torch.float32, device=dev)
+    up("c_policy_optimizer", c, gens["c_policy_optimizer"])
+    log = c.log.cpu().numpy()
+    return dict(envs=n, rows=sets["plain"][0].logp.numel(), epochs=epochs, minibatches=minibatches, minibatch_rows=sets["plain"][0].logp.numel() // minibatches,
+                parameters=c.P, settings=OPT, window_updates=window, windows=windows, graph_capture=capture, updates_per_s_median=med,
+                updates_per_s_all=r["all"], ms_per_update={k: 1e3 / v for k, v in med.items()},
+                ms_per_update_over_plain={k: 1e3 / v - 1e3 / med["plain"] for k, v in med.items()},
+                lr_after=dict(a_torch_host_read=float(adam["a_torch_host_read"].param_groups[0]["lr"]), b_torch_tensor_lr=float(adam["b_torch_tensor_lr"].param_groups[0]["lr"]),
+                              c_policy_optimizer=float(c.lr)),
+                last_update_of_c={name: [float(x) for x in log[:, i]] for i, name in enumerate(_lib.POL_OPT_STATS)})
+
+
+def main_optimizer(args):
+    """--learn --optimizer: a process per env count, results to profiles/policy_optimizer.json"""
+    import subprocess
+    if args and args[0] == "--trace":
+        from tsid_control_amd import PolicyOptimizer
+        st, fused, _ = learn_setup(int(args[1]))
+        opt = PolicyOptimizer(fused, **OPT)
+        for _ in range(int(args[2])):
+            fused.update(st, opt, 5, 4)
+        torch.cuda.synchronize()
+        return
+    if args and args[0] == "--case":
+        print(json.dumps(measure_optimizers(int(args[1]))))
+        return
+    out_path = args[0] if args else "profiles/policy_optimizer.json"
+    runs = []
+    for n in (4096, 512):
+        r = subprocess.run([sys.executable, sys.argv[0], "--learn", "--optimizer", "--case", str(n)], capture_output=True, text=True, check=True)
+        runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    report(out_path, actor="obs -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU",
+           loss="clip 0.2, value_coef 1, entropy_coef 0.01, clipped value loss, normalised advantages", runs=runs)
+
+
 def main_normalize(which, args):
     """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
     4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
@@ -525,6 +635,9 @@ def main_normalize(which, args):
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] in ("--actor", "--learn") and sys.argv[2] == "--normalize":
         main_normalize(sys.argv[1][2:], sys.argv[3:])
+        sys.exit(0)
+    if len(sys.argv) > 2 and sys.argv[1] == "--learn" and sys.argv[2] == "--optimizer":
+        main_optimizer(sys.argv[3:])
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--learn":
         if len(sys.argv) > 2 and sys.argv[2] == "--trace":

@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "PolicyLearner":
         from .policy_learner import PolicyLearner
         return PolicyLearner
+    if name == "PolicyOptimizer":
+        from .policy_optimizer import PolicyOptimizer
+        return PolicyOptimizer
     if name in ("Footstep", "Support", "FootstepPlanner"):
         from . import footstep_planner
         return getattr(footstep_planner, name)

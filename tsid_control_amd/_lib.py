@@ -18,7 +18,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_teacher_config", "tsidb_policy_teacher", "tsidb_policy_teacher_obs",
            "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan",
            "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn",
-           "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm"]
+           "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm",
+           "tsidb_policy_opt_workspace", "tsidb_policy_opt_step"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -77,6 +78,10 @@ POL_LEARN_SEG_ROWS = 512
 POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "loss", "rows", "bad_indices")
 # the policy normaliser (include/tsidb.h tsidb_policy_norm_update): the rows of a segment of the batch statistics
 POL_NORM_SEG_ROWS = 256
+# the policy optimiser (include/tsidb.h tsidb_policy_opt_step): the elements of a chunk of the gradient norm's sums, the slots
+# of a chunk's (and of a KL segment's) sum, and the stats
+POL_OPT_CHUNK, POL_OPT_LANES = 1024, 256
+POL_OPT_STATS = ("grad_norm", "clip_coef", "kl", "lr", "step", "skipped", "kl_rows", "lr_direction")
 
 
 def pol_teach_nobs(na):
@@ -145,6 +150,22 @@ class PolicyGrads(C.Structure):
 class PolicyLearnCfg(C.Structure):
     """tsidb_policy_learn_cfg (include/tsidb.h)"""
     _fields_ = [("clip", C.c_float), ("value_coef", C.c_float), ("entropy_coef", C.c_float), ("value_clip", C.c_int)]
+
+
+class PolicyOptCfg(C.Structure):
+    """tsidb_policy_opt_cfg (include/tsidb.h)"""
+    _fields_ = [("b1", C.c_double), ("b2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double), ("desired_kl", C.c_double),
+                ("lr_min", C.c_float), ("lr_max", C.c_float), ("skip_nonfinite", C.c_int)]
+
+
+class PolicyOptState(C.Structure):
+    """tsidb_policy_opt_state (include/tsidb.h): the optimiser's device memory"""
+    _fields_ = [("moments", C.c_void_p), ("lr", C.c_void_p), ("step", C.c_void_p), ("log_std_old", C.c_void_p), ("stats", C.c_void_p)]
+
+
+class PolicyOptKl(C.Structure):
+    """tsidb_policy_opt_kl (include/tsidb.h): the learner's last minibatch, as the KL of the adaptive step size reads it"""
+    _fields_ = [("mu", C.c_void_p), ("mean", C.c_void_p), ("index", C.c_void_p), ("rows", C.c_int), ("M", C.c_int)]
 
 
 def dims9(L):
@@ -225,6 +246,8 @@ def load(path=None):
     L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]
     L.tsidb_policy_norm_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.tsidb_policy_actor_norm.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]
+    L.tsidb_policy_opt_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+    L.tsidb_policy_opt_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.tsidb_set_sensors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.tsidb_set_cop_ref.argtypes = [vp, vp]
     L.tsidb_walk_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int] + [C.c_double] * 6 + [vp, vp, vp, vp, vp, C.c_double, vp, vp]

@@ -7,6 +7,7 @@
 #include "tsidb_actor.hpp"
 #include "tsidb_learner.hpp"
 #include "tsidb_norm.hpp"
+#include "tsidb_optim.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -1830,6 +1831,124 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
   hipLaunchKernelGGL(k_policy_learn_rows, dim3(w.Mp / ACT_TILE, critic ? 2 : 1), dim3(WAVE * ACT_WAVES), lds, s, a);
   hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
   hipLaunchKernelGGL(k_policy_learn_reduce, dim3((unsigned)((r.rp + NA + 1 + 255) / 256)), dim3(256), 0, s, r);
+  HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+} // extern "C"
+
+// The pieces of a step in the header's order - the actor's layers (weight, bias), the critic's, log_std - with their chunks
+// counted, and off: where each piece starts among the P elements of all pieces.  The pointers are the call's to fill.
+static void opt_layout(const LearnNet *nets, OptArgs &a, size_t *off) {
+  size_t P = 0;
+  int np = 0, chunks = 0;
+  auto add = [&](int n) {
+    OptPiece &pc = a.piece[np++];
+    pc.n = n; pc.chunk0 = chunks;
+    off[np - 1] = P;
+    chunks += (n + OPT_CHUNK - 1) / OPT_CHUNK;
+    P += (size_t)n;
+  };
+  for (int y = 0; y < 2; y++) {
+    const ActorNet &n = nets[y].net;
+    for (int l = 0; l < n.n_layers; l++) {
+      add(n.width[l] * (l ? n.width[l - 1] : n.K));
+      if (n.b[l]) add(n.width[l]);
+    }
+  }
+  add(NA);
+  a.npieces = np; a.nchunks = chunks; a.P = P;
+}
+
+static int opt_segments(int M) { return M > 0 ? (M + LRN_SEG - 1) / LRN_SEG : 0; }
+
+static size_t opt_workspace_bytes(int nchunks, int nseg) { return ((size_t)nchunks + 2 * (size_t)nseg) * sizeof(double) + sizeof(OptScalars); }
+
+extern "C" {
+
+int tsidb_policy_opt_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_opt_workspace: ";
+  if (!actor) throw std::string(who) + "null actor";
+  if (!bytes) throw std::string(who) + "null bytes";
+  if (M < 0) throw std::string(who) + "M must be >= 0 (0 = no schedule)";
+  LearnNet nets[2] = {};
+  nets[0] = learn_net(actor, who, "actor", NA, "NA");
+  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
+  OptArgs a = {};
+  size_t off[OPT_MAXPIECES];
+  opt_layout(nets, a, off);
+  *bytes = opt_workspace_bytes(a.nchunks, opt_segments(M));
+  GUARD_END
+}
+
+int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                          const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads, float *log_std,
+                          const float *log_std_grad, const tsidb_policy_opt_cfg *cfg, const tsidb_policy_opt_state *state,
+                          const tsidb_policy_opt_kl *kl, void *workspace, size_t workspace_bytes, void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_opt_step: ";
+  hipStream_t s = (hipStream_t)stream;
+  if (!actor) throw std::string(who) + "null actor";
+  if (!actor_grads) throw std::string(who) + "null actor_grads";
+  if (critic && !critic_grads) throw std::string(who) + "null critic_grads";
+  if (!cfg) throw std::string(who) + "null cfg";
+  if (!state) throw std::string(who) + "null state";
+  if (!log_std || !log_std_grad) throw std::string(who) + "null log_std or log_std_grad";
+  if (!state->moments || !state->lr || !state->step || !state->stats) throw std::string(who) + "null state pointer (moments, lr, step, stats)";
+  if (!workspace) throw std::string(who) + "null workspace";
+  if (!(cfg->b1 >= 0.0 && cfg->b1 < 1.0) || !(cfg->b2 >= 0.0 && cfg->b2 < 1.0)) throw std::string(who) + "b1 and b2 must be in [0, 1)";
+  if (!(cfg->eps > 0.0) || !std::isfinite(cfg->eps)) throw std::string(who) + "eps must be > 0";
+  if (!(cfg->max_norm >= 0.0) || !std::isfinite(cfg->max_norm)) throw std::string(who) + "max_norm must be >= 0 (0 = no clipping)";
+  if (!(cfg->desired_kl >= 0.0) || !std::isfinite(cfg->desired_kl)) throw std::string(who) + "desired_kl must be >= 0 (0 = no schedule)";
+  if (!(cfg->lr_min > 0.f) || !(cfg->lr_min <= cfg->lr_max) || !std::isfinite(cfg->lr_max)) throw std::string(who) + "lr_min must be > 0 and <= lr_max";
+  const bool sched = cfg->desired_kl > 0.0;
+  if (sched) {
+    if (!kl || !kl->mean || !kl->index || !kl->mu || !state->log_std_old)
+      throw std::string(who) + "the schedule needs kl (mean, index, mu) and log_std_old";
+    if (kl->M < 1) throw std::string(who) + "M must be >= 1";
+    if (kl->rows < 1) throw std::string(who) + "rows must be >= 1";
+  }
+  LearnNet nets[2] = {};
+  nets[0] = learn_net(actor, who, "actor", NA, "NA");
+  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
+  OptArgs a = {};
+  size_t off[OPT_MAXPIECES];
+  opt_layout(nets, a, off);
+  a.nseg = sched ? opt_segments(kl->M) : 0;
+  const size_t need = opt_workspace_bytes(a.nchunks, a.nseg);
+  if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
+  int np = 0;
+  auto fill = [&](const float *p, const float *g) {
+    OptPiece &pc = a.piece[np];
+    pc.p = const_cast<float *>(p); pc.g = g;
+    pc.m = state->moments + off[np++];
+    pc.vec = (((uintptr_t)pc.p | (uintptr_t)pc.g | (uintptr_t)pc.m | (uintptr_t)(pc.m + a.P)) & 15) == 0;
+  };
+  for (int y = 0; y < 2; y++) {
+    const tsidb_policy_net *p = y ? critic : actor;
+    const tsidb_policy_grads *gr = y ? critic_grads : actor_grads;
+    const ActorNet &n = nets[y].net;
+    for (int l = 0; l < n.n_layers; l++) {
+      if (!gr->weight[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null weight gradient";
+      if (p->bias[l] && !gr->bias[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null bias gradient where the bias exists";
+      fill(p->weight[l], gr->weight[l]);
+      if (p->bias[l]) fill(p->bias[l], gr->bias[l]);
+    }
+  }
+  fill(log_std, log_std_grad);
+  if (sched) { a.mu = kl->mu; a.mean = kl->mean; a.index = kl->index; a.rows = kl->rows; a.M = kl->M; a.log_std_old = state->log_std_old; }
+  a.log_std = log_std;
+  a.b1 = cfg->b1; a.b2 = cfg->b2; a.max_norm = cfg->max_norm; a.desired_kl = cfg->desired_kl;
+  a.omb1 = (float)(1.0 - cfg->b1); a.b2f = (float)cfg->b2; a.omb2 = (float)(1.0 - cfg->b2); a.epsf = (float)cfg->eps;
+  a.lr_min = cfg->lr_min; a.lr_max = cfg->lr_max; a.skip_nonfinite = cfg->skip_nonfinite != 0;
+  a.lr = state->lr; a.step = (long long *)state->step; a.stats = state->stats;
+  a.part = (double *)workspace;
+  a.sc = (OptScalars *)(a.part + a.nchunks + 2 * a.nseg);
+  h->note_stream(s);
+  hipLaunchKernelGGL(k_policy_opt_partial, dim3(a.nchunks + a.nseg), dim3(OPT_LANES), 0, s, a);
+  hipLaunchKernelGGL(k_policy_opt_scalars, dim3(1), dim3(OPT_LANES), 0, s, a);
+  hipLaunchKernelGGL(k_policy_opt_apply, dim3(a.nchunks), dim3(OPT_LANES), 0, s, a);
   HIP_OK(hipGetLastError());
   GUARD_END
 }

@@ -4,9 +4,11 @@ of a RolloutStorage, and the gradient of every weight and bias of the PolicyActo
 their .grad.  The forward pass is the actor kernel's own, so the recomputed log-probability is the stored one's twin.  No
 reference counterpart (the reference's only controller is TSID, main.py:113-129).
 
-What stays the caller's: the optimiser (any torch.optim over the same tensors: its step is what the next act() and the next
-backward() compute with, nothing is copied), gradient clipping, schedules, all-reduces, observation normalisation - all work on
-.grad as they do after loss.backward().  .grad is OVERWRITTEN by every backward(), never accumulated.
+What stays the caller's unless PolicyOptimizer is used (policy_optimizer.py: gradient clipping, Adam and rsl_rl's adaptive step
+size in three launches): the optimiser (any torch.optim over the same tensors: its step is what the next act() and the next
+backward() compute with, nothing is copied), gradient clipping, schedules.  What stays the caller's: all-reduces, observation
+normalisation (PolicyNormalizer) - all work on .grad as they do after loss.backward().  .grad is OVERWRITTEN by every
+backward(), never accumulated.
 
 No parameter needs requires_grad, log_std included: backward() gives every parameter that has none a zero float32 .grad of
 its own, reads the pointers again at every call (zero_grad(set_to_none=True) is harmless), and torch's optimisers step every
@@ -130,6 +132,7 @@ class PolicyLearner:
         ag = self._grads_of(a.actor_net)
         cg = self._grads_of(a.critic_net) if a.critic_net is not None else None
         self._last = (batch, ag, cg)       # (alive until the next call: the library copies them during the call, a recorder may look later)
+        self._last_storage, self._last_index = storage, index    # (what a PolicyOptimizer's KL is taken over)
         wc._call("tsidb_policy_learn", C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None,
                  C.byref(batch), C.byref(ag), C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()),
                  C.c_void_p(self._grad(a.log_std).data_ptr()), C.byref(self._cfg), C.c_void_p(ws.data_ptr()),
@@ -146,7 +149,8 @@ class PolicyLearner:
     def update(self, storage, optimizer, epochs=5, minibatches=4, generator=None):
         """One PPO update on a storage whose gae() has run: per epoch a torch.randperm(T * N) on the device (generator: a
         torch.Generator of the device, None = the default one), cut into `minibatches` slices; per slice backward() and
-        optimizer.step().  Returns the stats of every slice, [epochs * minibatches, 8]; no host sync anywhere."""
+        optimizer.step().  An optimizer with a snapshot() method (PolicyOptimizer: the rollout's log_std, for its KL) has it called
+        once, first.  Returns the stats of every slice, [epochs * minibatches, 8]; no host sync anywhere."""
         wc = self.env.wc
         epochs, minibatches = _count("epochs", epochs), _count("minibatches", minibatches)
         if not isinstance(storage, RolloutStorage) or storage.advantage is None:
@@ -157,6 +161,8 @@ class PolicyLearner:
         if self.normalize_advantage:
             self.fill_adv_stats(storage)
         out = torch.zeros(epochs * minibatches, len(_lib.POL_LEARN_STATS), dtype=torch.float32, device=wc.device)
+        if hasattr(optimizer, "snapshot"):
+            optimizer.snapshot()
         for ep in range(epochs):
             perm = torch.randperm(rows, generator=generator, dtype=torch.int32, device=wc.device)
             for k in range(minibatches):
