@@ -619,6 +619,29 @@ int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *ro
 int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *rows, int rows_ld, const void *qpos,
                              const void *tau, void *teacher_obs, int obs_ld, void *stream);
 
+/* ---- imitation of the teacher: the label of a stored rollout row and DAgger's mixing.  After tsidb_policy_actor (which stored the
+ * row and sampled `action`), before tsidb_policy_act.  One plain asynchronous launch: no allocation, no host read, capturable.
+ * teacher_action [N, NA] (the path's type) is what tsidb_policy_teacher wrote at the end of the PREVIOUS policy step.  Timing: it
+ * was formed by the last tick of that step, on the state one sim step before the observation the actor has just seen - the
+ * closest label the closed loop offers, and a causal one: the same tau is in teacher_obs.  For an env the previous step restarted,
+ * or tsidb_reset / PolicyEnv.reset() has just set up, it belongs to the fallen robot or to nothing: that is ep_len == 0, and such
+ * a row gets weight 0 and is never executed (a failed QP ends in a restart, so it is covered too).  Per env e:
+ *   label[e, a]  = (float)teacher_action[e, a]                 cast once; label [N, NA] float32
+ *   weight[e]    = ep_len[e] > 0 ? 1 : 0                       [N] float32
+ *   executed[e]  = U < beta[0] && ep_len[e] > 0                [N] int32
+ *   action[e, :] = teacher_action[e, :] where executed[e]      the path's bits, an exact copy; elsewhere action keeps its bits
+ * with U one more stream of the randomisation's key layout (key = seed + ((stream * 256 + column) * 2^32), the same hash):
+ *   stream  draw                     column              counter
+ *   23      teacher / student episode  -                 episode * 2^32: one draw per episode - a whole episode is the teacher's
+ *                                                        or the student's
+ * for the env index env_offset + env; episode and ep_len are read from bufs.  beta [1] float32 is read from DEVICE memory at
+ * every launch (as tsidb_policy_opt_step reads lr): a captured rollout follows a beta that a device op decays between replays;
+ * NULL = 0, nothing is executed.  action may be NULL (labels and flags alone).  Rejects (message via tsidb_last_error, nothing
+ * launched): what tsidb_policy_act rejects in bufs and the handle's state; a NULL teacher_action, label, weight or executed;
+ * seed >= 2^32; env_offset >= 2^31. */
+int tsidb_policy_teacher_mix(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *teacher_action, void *action, float *label,
+                             float *weight, int32_t *executed, const float *beta, uint64_t seed, uint64_t env_offset, void *stream);
+
 /* ---- the policy's side of a rollout: a dense actor and an optional critic evaluated on the env's own rows, the Gaussian sample
  * with its log-probability, and the advantages of a recorded rollout.  Both calls are plain asynchronous launches on the given
  * stream: no allocation, no host synchronisation, no state of their own - T policy steps with their actor calls can be captured
@@ -815,6 +838,52 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
                        const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
                        const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
                        const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream);
+
+/* tsidb_policy_learn with an imitation term on the actor's mean (rsl_rl's Distillation; PPO with a behaviour-cloning term) and a
+ * weight on the surrogate.  Everything above holds - three launches, no atomics, one fixed order of every sum, the workspace's
+ * first floats mu and v - with these additions.  Per minibatch row m with j = index[m] valid, d_a = mu_a - target[j, a],
+ * w = weight[j] (1 where weight is NULL):
+ *   TSIDB_POL_IMIT_MSE     l_m = (1 / NA) sum_a d_a^2
+ *   TSIDB_POL_IMIT_HUBER   l_m = (1 / NA) sum_a (|d_a| <= 1 ? d_a^2 / 2 : |d_a| - 1/2)        (delta = 1, torch's default)
+ *   L_im = (1 / M) sum_m w l_m
+ *   loss = surrogate_coef L_pi + value_coef L_v - entropy_coef entropy + imitation_coef L_im
+ * The gradient is torch.autograd's for these expressions: dmu_a gains imitation_coef w / (M NA) times 2 d_a (MSE) or
+ * clamp(d_a, -1, 1) (Huber); log_std gets nothing from the term (the label is for the mean, as in rsl_rl's act_inference); the
+ * surrogate's dlogp, and with it its share of dlog_std, is scaled by surrogate_coef.  surrogate_coef = 1: PPO as it is;
+ * surrogate_coef = value_coef = entropy_coef = 0: pure distillation.
+ * A row with w == 0 exactly contributes exactly 0 and its target is NOT READ (a select, not a product: a NaN label behind a zero
+ * weight is harmless).  A row whose skip_surrogate[j] is nonzero - the env executed another action than the stored one
+ * (tsidb_policy_teacher_mix) - contributes 0 to L_pi, to dlogp and to stats[3] and stats[4]; its value loss and its imitation term
+ * stay, and it still counts in stats[6].  All means stay over M; a bad index contributes nothing to the new term either.
+ * stats[0..7] keep their meanings, stats[5] is the full loss above.  imit->stats [TSIDB_POL_IMIT_NSTATS] float32:
+ *   0 L_im (formed wherever target is given, also with imitation_coef = 0)   1 sum of w over the rows used
+ *   2 rows used with w > 0   3 rows used whose surrogate was skipped
+ * With imitation_coef = 0 the labels add nothing to any gradient or to stats[5] whatever they hold; with surrogate_coef = 1 and
+ * no skipped row besides, the gradients and stats[0..7] are tsidb_policy_learn's bit for bit.  imit NULL is tsidb_policy_learn:
+ * the same kernels, the same bits, tsidb_policy_learn_workspace's bytes.  Otherwise the workspace is at least
+ * tsidb_policy_learn_imit_workspace's bytes (four more floats per row and per segment than tsidb_policy_learn_workspace).
+ * Rejects: what tsidb_policy_learn rejects; a NULL target with imitation_coef > 0; a NULL imit->stats; a negative or non-finite
+ * imitation_coef, surrogate_coef, value_coef or entropy_coef; an unknown loss.
+ * (The struct is tsidb_policy_imit: C has one namespace for a typedef and a function, so it cannot share the entry's name.) */
+enum { TSIDB_POL_IMIT_MSE = 0, TSIDB_POL_IMIT_HUBER = 1 };
+enum { TSIDB_POL_IMIT_NSTATS = 4 };
+typedef struct tsidb_policy_imit {
+  const float *target;            /* [rows, NA] the stored labels */
+  const float *weight;            /* [rows] >= 0, NULL = 1 */
+  const int32_t *skip_surrogate;  /* [rows], NULL = none: nonzero = the row was not the policy's action */
+  float imitation_coef;           /* >= 0 */
+  float surrogate_coef;           /* >= 0 */
+  int loss;                       /* TSIDB_POL_IMIT_* */
+  float *stats;                   /* [TSIDB_POL_IMIT_NSTATS] */
+} tsidb_policy_imit;
+
+int tsidb_policy_learn_imit_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes);
+
+int tsidb_policy_learn_imit(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                            const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                            const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                            const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit, float *workspace,
+                            size_t workspace_bytes, float *stats, void *stream);
 
 /* ---- the step's side of a PPO iteration: what rsl_rl runs per minibatch behind the loss - its adaptive step size from the
  * exact Gaussian KL (schedule = "adaptive"), torch's clip_grad_norm_ over all parameters, and torch.optim.Adam's default

@@ -49,7 +49,17 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               rule with its host read of the KL; (b) the same with the rule written sync-free on a tensor lr (Adam capturable);
               (c) PolicyOptimizer; (d) (c) with the whole update() captured in one graph - each on a learner of its own over equal
               weights, in alternating windows (a process per case), at 4096 and 512 envs; default profiles/policy_optimizer.json.
-              Kernel times: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --optimizer --trace ENVS UPDATES"""
+              Kernel times: rocprofv3 --kernel-trace --stats -- python tools/policy_env.py --learn --optimizer --trace ENVS UPDATES
+    python tools/policy_env.py --distill [--beta B --beta-decay D --iters K] [out.json]   imitation of the TSID teacher: a standing env
+              with TSID beside the policy (tsid="stand", motor mode: an action is a torque), the 256-128 networks, K DAgger
+              iterations at 512 envs - a 16-step teacher rollout at beta (RolloutStorage(teacher=True), rollout(teacher_beta=...)),
+              2 epochs x 4 minibatches of pure distillation (PolicyLearner(imitation_coef=1, surrogate_coef=0, value_coef=0) with a
+              PolicyOptimizer), beta *= D on the device - with L_im, the running episode length, the executed share and the restarts
+              per iteration; `control`: the same rollouts with the untrained student alone; and, at 4096 x 16 and 512 x 16 rows,
+              backward() with the term off (the parent commit's call) and on, and the 16-step rollout into a plain storage (the
+              parent's launches), into a teacher storage, and with beta = 0.5, in alternating windows (a process per case);
+              default profiles/policy_imitation.json.  Kernel times: rocprofv3 --kernel-trace --stats -- python
+              tools/policy_env.py --distill --trace ENVS CALLS (CALLS backward() with the term off, then on)"""
 import json
 import sys
 import time
@@ -595,6 +605,121 @@ def main_optimizer(args):
            loss="clip 0.2, value_coef 1, entropy_coef 0.01, clipped value loss, normalised advantages", runs=runs)
 
 
+def distill_env(n, decimation=4):
+    """the standing env of --distill: TSID beside the policy in motor mode, an action = a torque [N m]"""
+    conf = RobotConfig()
+    conf.closed_loop, conf.reference_quirks = True, False
+    return PolicyEnv(conf, num_envs=n, device="cuda:0", decimation=decimation, tsid="stand", mode="motor", action_scale=1.0, action_clip=100.0,
+                     max_episode_steps=200, reward_weights=dict(alive=0.2, termination=-5.0), seed=1)
+
+
+def distill_actor(env):
+    from tsid_control_amd import PolicyActor
+    actor, critic, ai, ci, ls = actor_nets(env, False)
+    return PolicyActor(env, actor, critic, actor_inputs=ai, critic_inputs=ci, log_std=ls)
+
+
+def run_distill(n, beta, decay, iters, steps=16, epochs=2, minibatches=4, learn=True):
+    """DAgger with the TSID teacher: per iteration a `steps`-step teacher rollout at the current beta, `epochs` x `minibatches` pure
+    distillation steps (PolicyOptimizer, constant lr 1e-3), beta *= decay on the device; per iteration L_im of the last
+    minibatch, the mean length of the episodes that ended in the rollout (None: none ended), the share of rows the teacher's
+    action was executed on, and the restarts.  learn = False: the control - the same rollouts with the untrained student alone
+    (beta as given, no update), for the restarts a student that learns nothing has"""
+    from tsid_control_amd import PolicyLearner, PolicyOptimizer, RolloutStorage
+    env = distill_env(n)
+    pa = distill_actor(env)
+    st = RolloutStorage(env, pa, steps, teacher=True)
+    pl = PolicyLearner(pa, imitation_coef=1.0, surrogate_coef=0.0, value_coef=0.0, entropy_coef=0.0)
+    opt = PolicyOptimizer(pl, lr=1e-3)
+    b = torch.full((1,), float(beta), dtype=torch.float32, device=env.device)
+    rows = []
+    for it in range(iters):
+        before = env.episode.clone()
+        env.rollout(pa, steps, st, teacher_beta=b)
+        st.gae(0.99, 0.95)
+        out = pl.update(st, opt, epochs, minibatches) if learn else torch.full((1, 8), float("nan"))
+        if not learn:
+            pl.backward(st, torch.arange(n * steps, dtype=torch.int32, device=env.device))       # (L_im of the whole rollout, no step)
+        ended = st.done != 0
+        rows.append(dict(iteration=it, beta=float(b), imitation_loss=float(pl.imit_stats[0]), loss=float(out[-1, 5]),
+                         executed_share=float(st.teacher_executed.float().mean()), labelled_share=float(st.teacher_weight.mean()),
+                         restarts=int((env.episode - before).sum()), ended_by_timeout=int(st.timeout.sum()), rows_done=int(ended.sum()),
+                         mean_episode_length_running=float(env.ep_len.float().mean())))
+        b.mul_(decay)
+    return dict(envs=n, learn=learn, rollout_steps=steps, epochs=epochs, minibatches=minibatches, beta=beta, beta_decay=decay, iterations=rows)
+
+
+def time_distill(n, steps=16, window=40, windows=4, preroll=3):
+    """backward() at n x `steps` rows with the term off (tsidb_policy_learn: the parent commit's call) and on (pure distillation and
+    PPO + term), and the 16-step rollout into a plain storage (the parent's launches), into a teacher storage without a beta (the
+    same actions executed: the new launch is the only difference) and with beta = 0.5, in alternating windows of one process"""
+    from tsid_control_amd import PolicyLearner, RolloutStorage
+    env = distill_env(n)
+    pa = distill_actor(env)
+    st = env.rollout(pa, steps, RolloutStorage(env, pa, steps, teacher=True), teacher_beta=0.5)
+    st.gae(0.99, 0.95)
+    kw = dict(clip=0.2, value_coef=1.0, entropy_coef=0.01)
+    learners = dict(off=PolicyLearner(pa, **kw), ppo_bc=PolicyLearner(pa, imitation_coef=0.5, **kw),
+                    distill=PolicyLearner(pa, imitation_coef=1.0, surrogate_coef=0.0, value_coef=0.0, entropy_coef=0.0))
+    index = torch.randperm(n * steps, generator=torch.Generator(device="cuda:0").manual_seed(3), dtype=torch.int32, device="cuda:0")
+    for pl in learners.values():
+        pl.fill_adv_stats(st)
+    back = alternate({k: (lambda c, pl=pl: [pl.backward(st, index, adv_stats=pl.adv_stats) for _ in range(c)]) for k, pl in learners.items()},
+                     window, windows, preroll)
+    plain = RolloutStorage(env, pa, steps)
+    beta = torch.full((1,), 0.5, dtype=torch.float32, device=env.device)
+    roll = alternate(dict(plain=lambda c: [env.rollout(pa, steps, plain) for _ in range(c)],
+                          labels=lambda c: [env.rollout(pa, steps, st) for _ in range(c)],
+                          mixed=lambda c: [env.rollout(pa, steps, st, teacher_beta=beta) for _ in range(c)]), max(2, window // 4), windows, 1)
+    us = lambda r: {k: 1e6 / v for k, v in r["policy_steps_per_s_median"].items()}
+    spread = lambda r: {k: (max(v) - min(v)) / float(np.median(v)) for k, v in r["all"].items()}
+    return dict(envs=n, rows=n * steps, backward_us=us(back), backward_window_spread=spread(back), backward_calls_per_s_all=back["all"],
+                rollout_us=us(roll), rollout_window_spread=spread(roll), rollouts_per_s_all=roll["all"])
+
+
+def main_distill(args):
+    """--distill [--beta B --beta-decay D --iters K] [out.json]: the learning run at 512 envs and the timings at 4096 and 512, a process
+    per case; results to profiles/policy_imitation.json"""
+    import subprocess
+    opts = dict(beta=1.0, decay=0.8, iters=20)
+    rest = []
+    while args:
+        a = args.pop(0)
+        if a in ("--beta", "--beta-decay", "--iters"):
+            opts[dict({"--beta": "beta", "--beta-decay": "decay", "--iters": "iters"})[a]] = float(args.pop(0))
+        else:
+            rest.append(a)
+    if rest and rest[0] == "--trace":                 # backward() with the term off, then on, for rocprofv3 --kernel-trace --stats
+        from tsid_control_amd import PolicyLearner, RolloutStorage
+        n, calls = int(rest[1]), int(rest[2])
+        env = distill_env(n)
+        pa = distill_actor(env)
+        st = env.rollout(pa, 16, RolloutStorage(env, pa, 16, teacher=True), teacher_beta=0.5)
+        st.gae(0.99, 0.95)
+        index = torch.randperm(n * 16, dtype=torch.int32, device="cuda:0")
+        for kw in (dict(), dict(imitation_coef=0.5)):
+            pl = PolicyLearner(pa, entropy_coef=0.01, **kw)
+            for _ in range(calls):
+                pl.backward(st, index)
+        torch.cuda.synchronize()
+        return
+    if rest and rest[0] == "--case":                  # one case, as a JSON line
+        what, n = rest[1], int(rest[2])
+        if what == "time":
+            print(json.dumps(time_distill(n)))
+        else:
+            print(json.dumps(run_distill(n, opts["beta"], opts["decay"], int(opts["iters"])) if what == "run" else
+                             run_distill(n, 0.0, 1.0, int(opts["iters"]), learn=False)))
+        return
+    out_path = rest[0] if rest else "profiles/policy_imitation.json"
+    flags = ["--beta", str(opts["beta"]), "--beta-decay", str(opts["decay"]), "--iters", str(int(opts["iters"]))]
+    case = lambda *c: json.loads(subprocess.run([sys.executable, sys.argv[0], "--distill", *flags, "--case", *c], capture_output=True, text=True,
+                                                check=True).stdout.strip().splitlines()[-1])
+    report(out_path, actor="obs -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU (not trained: pure distillation)",
+           env="tsid = 'stand', motor mode, action = torque [N m], decimation 4", optimizer="PolicyOptimizer, lr 1e-3, max_grad_norm 1",
+           run=case("run", "512"), control=case("control", "512"), timings=[case("time", "4096"), case("time", "512")])
+
+
 def main_normalize(which, args):
     """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
     4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
@@ -633,6 +758,9 @@ def main_normalize(which, args):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--distill":
+        main_distill(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 2 and sys.argv[1] in ("--actor", "--learn") and sys.argv[2] == "--normalize":
         main_normalize(sys.argv[1][2:], sys.argv[3:])
         sys.exit(0)

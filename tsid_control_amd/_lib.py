@@ -19,7 +19,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_terrain_config", "tsidb_policy_terrain_reset", "tsidb_policy_height_scan",
            "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn",
            "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm",
-           "tsidb_policy_opt_workspace", "tsidb_policy_opt_step"]
+           "tsidb_policy_opt_workspace", "tsidb_policy_opt_step",
+           "tsidb_policy_teacher_mix", "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -76,6 +77,11 @@ POL_ACTOR_STREAMS = (21, 22)
 # the policy learner (include/tsidb.h tsidb_policy_learn): the rows of a segment of the weight gradient's sums, and the stats
 POL_LEARN_SEG_ROWS = 512
 POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "loss", "rows", "bad_indices")
+# imitation of the teacher (include/tsidb.h tsidb_policy_teacher_mix, tsidb_policy_learn_imit): the stream of the per-episode
+# teacher / student draw, the losses in the order of TSIDB_POL_IMIT_*, and the imitation stats
+POL_TEACHER_MIX_STREAM = 23
+POL_IMIT_LOSSES = ("mse", "huber")
+POL_IMIT_STATS = ("imitation_loss", "weight_sum", "weighted_rows", "skipped_rows")
 # the policy normaliser (include/tsidb.h tsidb_policy_norm_update): the rows of a segment of the batch statistics
 POL_NORM_SEG_ROWS = 256
 # the policy optimiser (include/tsidb.h tsidb_policy_opt_step): the elements of a chunk of the gradient norm's sums, the slots
@@ -150,6 +156,12 @@ class PolicyGrads(C.Structure):
 class PolicyLearnCfg(C.Structure):
     """tsidb_policy_learn_cfg (include/tsidb.h)"""
     _fields_ = [("clip", C.c_float), ("value_coef", C.c_float), ("entropy_coef", C.c_float), ("value_clip", C.c_int)]
+
+
+class PolicyImit(C.Structure):
+    """tsidb_policy_imit (include/tsidb.h): the imitation term of tsidb_policy_learn_imit"""
+    _fields_ = [("target", C.c_void_p), ("weight", C.c_void_p), ("skip_surrogate", C.c_void_p), ("imitation_coef", C.c_float),
+                ("surrogate_coef", C.c_float), ("loss", C.c_int), ("stats", C.c_void_p)]
 
 
 class PolicyOptCfg(C.Structure):
@@ -243,6 +255,9 @@ def load(path=None):
     L.tsidb_policy_gae.argtypes = [vp, C.c_int, vp, vp, i32p, vp, C.c_float, C.c_float, vp, vp, vp]
     L.tsidb_policy_learn_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.tsidb_policy_teacher_mix.argtypes = [vp, vp, vp, vp, vp, vp, i32p, vp, C.c_uint64, C.c_uint64, vp]
+    L.tsidb_policy_learn_imit_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+    L.tsidb_policy_learn_imit.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]
     L.tsidb_policy_norm_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.tsidb_policy_actor_norm.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]

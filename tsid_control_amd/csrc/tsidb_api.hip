@@ -734,6 +734,7 @@ struct tsidb_ctx {
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
   bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
+  bool learn_imit_big_lds = false;           // tsidb_policy_learn_imit: k_policy_learn_rows_imit's likewise
   bool actor_norm_big_lds = false;           // tsidb_policy_actor_norm: k_policy_actor_norm's likewise
   bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
   std::string err;
@@ -1496,6 +1497,18 @@ int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
   });
 }
 
+int tsidb_policy_teacher_mix(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *teacher_action, void *action, float *label,
+                             float *weight, int32_t *executed, const float *beta, uint64_t seed, uint64_t env_offset, void *stream) {
+  const char *who = "tsidb_policy_teacher_mix: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
+    using T = decltype(t);
+    if (!teacher_action || !label || !weight || !executed) throw std::string(who) + "null buffer (teacher_action, label, weight, executed)";
+    if (seed >= (1ull << 32) || env_offset >= (1ull << 31)) throw std::string(who) + "seed must be below 2^32 and env_offset below 2^31";
+    launch(k_policy_teacher_mix<T>, h->num_envs, b, (const T *)teacher_action, (T *)action, label, weight, executed, beta,
+           (unsigned long long)seed, (unsigned long long)env_offset);
+  });
+}
+
 } // extern "C"
 
 // tsidb_policy_net as the kernel takes it, checked; `name` = "actor" / "critic", last = the width its last layer must have
@@ -1703,8 +1716,9 @@ static LearnNet learn_net(const tsidb_policy_net *p, const char *who, const char
 }
 
 // The workspace of a call, in floats: mu [Mp, NA], v [Mp]; per network the gathered rows, the hidden H_l and every G_l; the
-// per-row pieces; the segments' partial sums.  Fills the offsets of the three launches where they are given.
-static size_t learn_layout(LearnNet *nets, int M, WgradArgs *w, ReduceArgs *r, size_t *r_off) {
+// per-row pieces; the segments' partial sums.  Fills the offsets of the three launches where they are given.  nr: the per-row
+// pieces of a row, LRN_NR, or LRN_NR + LRN_NI for the imitation variant.
+static size_t learn_layout(LearnNet *nets, int M, WgradArgs *w, ReduceArgs *r, size_t *r_off, int nr = LRN_NR) {
   const size_t Mp = (size_t)((M + ACT_TILE - 1) / ACT_TILE) * ACT_TILE;
   const int nseg = (int)((Mp + LRN_SEG - 1) / LRN_SEG);
   size_t off = 0, p = 0;
@@ -1734,17 +1748,17 @@ static size_t learn_layout(LearnNet *nets, int M, WgradArgs *w, ReduceArgs *r, s
     }
   }
   const size_t rows_off = off;
-  off += Mp * LRN_NR;
+  off += Mp * nr;
   if (r_off) *r_off = rows_off;
   if (w) {
     WgradJob &j = w->job[nj++];
-    j.g = 0; j.h = rows_off; j.p = p; j.gw = 1; j.hw = LRN_NR; j.ones = 1;
-    j.nkg = ((LRN_NR + 1 + 15) / 16 + LRN_KGROUP - 1) / LRN_KGROUP; j.blk0 = blk;
+    j.g = 0; j.h = rows_off; j.p = p; j.gw = 1; j.hw = nr; j.ones = 1;
+    j.nkg = ((nr + 1 + 15) / 16 + LRN_KGROUP - 1) / LRN_KGROUP; j.blk0 = blk;
     blk += j.nkg;
-    w->njobs = nj; w->Mp = (int)Mp; w->part = off; w->total = p + LRN_NR + 1;
+    w->njobs = nj; w->Mp = (int)Mp; w->part = off; w->total = p + nr + 1;
   }
-  if (r) { r->npieces = np; r->nseg = nseg; r->M = M; r->part = off; r->total = p + LRN_NR + 1; r->rp = p; }
-  off += (size_t)nseg * (p + LRN_NR + 1);
+  if (r) { r->npieces = np; r->nseg = nseg; r->M = M; r->part = off; r->total = p + nr + 1; r->rp = p; }
+  off += (size_t)nseg * (p + nr + 1);
   return off;
 }
 
@@ -1753,27 +1767,26 @@ static int learn_blocks(const WgradArgs &w) {
   return j.blk0 + ((j.gw + 15) / 16) * j.nkg;
 }
 
-extern "C" {
-
-int tsidb_policy_learn_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+// tsidb_policy_learn_workspace and tsidb_policy_learn_imit_workspace: one body
+static int learn_workspace_call(tsidb_handle h, const char *who, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes,
+                                int nr) {
   GUARD_BEGIN
-  const char *who = "tsidb_policy_learn_workspace: ";
   if (!actor) throw std::string(who) + "null actor";
   if (!bytes) throw std::string(who) + "null bytes";
   if (M < 1) throw std::string(who) + "M must be >= 1";
   LearnNet nets[2] = {};
   nets[0] = learn_net(actor, who, "actor", NA, "NA");
   if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
-  *bytes = learn_layout(nets, M, nullptr, nullptr, nullptr) * sizeof(float);
+  *bytes = learn_layout(nets, M, nullptr, nullptr, nullptr, nr) * sizeof(float);
   GUARD_END
 }
 
-int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
-                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
-                       const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
-                       const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream) {
+// tsidb_policy_learn and tsidb_policy_learn_imit: one body; without imit the launches are the three kernels' as ever
+static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                      const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads,
+                      const float *log_std, float *log_std_grad, const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit,
+                      float *workspace, size_t workspace_bytes, float *stats, void *stream) {
   GUARD_BEGIN
-  const char *who = "tsidb_policy_learn: ";
   hipStream_t s = (hipStream_t)stream;
   if (!actor) throw std::string(who) + "null actor";
   if (!batch) throw std::string(who) + "null batch";
@@ -1791,12 +1804,20 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
     throw std::string(who) + "null stored array (actor_input, action, logp, advantage)";
   if (critic && (!batch->critic_input || !batch->value || !batch->returns))
     throw std::string(who) + "a critic needs critic_input, value and returns";
+  if (imit) {
+    const float coefs[] = {imit->imitation_coef, imit->surrogate_coef, cfg->value_coef, cfg->entropy_coef};
+    for (float c : coefs) if (!(c >= 0.f) || !std::isfinite(c)) throw std::string(who) + "a coefficient is negative or not finite";
+    if (imit->imitation_coef > 0.f && !imit->target) throw std::string(who) + "imitation_coef > 0 needs target";
+    if (!imit->stats) throw std::string(who) + "null imit stats";
+    if (imit->loss != TSIDB_POL_IMIT_MSE && imit->loss != TSIDB_POL_IMIT_HUBER) throw std::string(who) + "unknown loss (TSIDB_POL_IMIT_MSE or _HUBER)";
+  }
+  const int nr = imit ? LRN_NR + LRN_NI : LRN_NR;
   LearnArgs a = {};
   a.net[0] = learn_net(actor, who, "actor", NA, "NA");
   if (critic) a.net[1] = learn_net(critic, who, "critic", 1, "1");
   WgradArgs w = {};
   ReduceArgs r = {};
-  const size_t need = learn_layout(a.net, batch->M, &w, &r, &a.r) * sizeof(float);
+  const size_t need = learn_layout(a.net, batch->M, &w, &r, &a.r, nr) * sizeof(float);
   if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
   int np = 0, widest = 0;
   for (int y = 0; y < 2; y++) {
@@ -1822,17 +1843,55 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
   r.ws = workspace; r.log_std = log_std; r.log_std_grad = log_std_grad; r.stats = stats;
   r.value_coef = cfg->value_coef; r.entropy_coef = cfg->entropy_coef;
   const size_t lds = act_lds_bytes(a.LD);
-  if (lds > 65536 && !h->learn_big_lds) {     // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle)
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_learn_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)act_lds_bytes(act_ld(ACT_MAXW))));
-    h->learn_big_lds = true;
+  bool &big = imit ? h->learn_imit_big_lds : h->learn_big_lds;
+  if (lds > 65536 && !big) {     // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle and kernel)
+    const void *fn = imit ? reinterpret_cast<const void *>(&k_policy_learn_rows_imit) : reinterpret_cast<const void *>(&k_policy_learn_rows);
+    HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
+    big = true;
   }
   h->note_stream(s);
-  hipLaunchKernelGGL(k_policy_learn_rows, dim3(w.Mp / ACT_TILE, critic ? 2 : 1), dim3(WAVE * ACT_WAVES), lds, s, a);
-  hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
-  hipLaunchKernelGGL(k_policy_learn_reduce, dim3((unsigned)((r.rp + NA + 1 + 255) / 256)), dim3(256), 0, s, r);
+  const dim3 rows_grid(w.Mp / ACT_TILE, critic ? 2 : 1), reduce_grid((unsigned)((r.rp + NA + (imit ? LRN_NI : 1) + 255) / 256));
+  if (imit) {
+    const LearnImit li = {imit->target, imit->weight, imit->skip_surrogate, imit->imitation_coef, imit->surrogate_coef,
+                          imit->loss == TSIDB_POL_IMIT_HUBER};
+    const ReduceImit ri = {imit->imitation_coef, imit->surrogate_coef, imit->stats};
+    hipLaunchKernelGGL(k_policy_learn_rows_imit, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a, li);
+    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
+    hipLaunchKernelGGL(k_policy_learn_reduce_imit, reduce_grid, dim3(256), 0, s, r, ri);
+  } else {
+    hipLaunchKernelGGL(k_policy_learn_rows, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a);
+    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
+    hipLaunchKernelGGL(k_policy_learn_reduce, reduce_grid, dim3(256), 0, s, r);
+  }
   HIP_OK(hipGetLastError());
   GUARD_END
+}
+
+extern "C" {
+
+int tsidb_policy_learn_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+  return learn_workspace_call(h, "tsidb_policy_learn_workspace: ", actor, critic, M, bytes, LRN_NR);
+}
+
+int tsidb_policy_learn_imit_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+  return learn_workspace_call(h, "tsidb_policy_learn_imit_workspace: ", actor, critic, M, bytes, LRN_NR + LRN_NI);
+}
+
+int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                       const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                       const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream) {
+  return learn_call(h, "tsidb_policy_learn: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr, workspace,
+                    workspace_bytes, stats, stream);
+}
+
+int tsidb_policy_learn_imit(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                            const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                            const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                            const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit, float *workspace, size_t workspace_bytes,
+                            float *stats, void *stream) {
+  return learn_call(h, "tsidb_policy_learn_imit: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, imit, workspace,
+                    workspace_bytes, stats, stream);
 }
 
 } // extern "C"

@@ -21,6 +21,12 @@
 // TSIDB_POL_LEARN_SEG_ROWS, a constant that depends on nothing, each segment's result goes to its own slice of the workspace.
 //
 // k_policy_learn_reduce: one thread per gradient element adds the segments' slices in segment order and overwrites .grad.
+//
+// The imitation variant (tsidb_policy_learn_imit): k_policy_learn_rows_imit and k_policy_learn_reduce_imit are the IMIT = true
+// instantiations of the two bodies below, k_policy_learn_wgrad is shared.  The rows kernel adds the label's term to G_last = dmu,
+// scales the surrogate's dlogp, zeroes the surrogate pieces of a row the policy did not act on, and writes LRN_NI more per-row
+// pieces behind the six; the row-piece job of the weight gradient sums them with the others, in the same fixed order.  The
+// IMIT = false instantiations are the kernels as they were: same names, same arguments, same code.
 #pragma once
 #include "tsidb_actor.hpp"
 
@@ -30,6 +36,8 @@ constexpr int LRN_SEG = TSIDB_POL_LEARN_SEG_ROWS;
 constexpr int LRN_KGROUP = 4;              // input tiles per wavefront of the weight gradient: they share the A fragment
 constexpr int LRN_NR = NA + 6;             // per-row pieces: dlogp (z_a^2 - 1) [NA], then the LRN_R_* columns
 enum { LRN_R_LPI = 0, LRN_R_LV, LRN_R_KL, LRN_R_CLIPPED, LRN_R_USED, LRN_R_BAD };
+constexpr int LRN_NI = 4;                  // the imitation variant's pieces, behind the six: w l_m, w, w > 0, surrogate skipped
+enum { LRN_I_LIM = 0, LRN_I_WSUM, LRN_I_WPOS, LRN_I_SKIPPED };
 constexpr int LRN_MAXJOBS = 2 * ACT_MAXL + 1;
 
 struct LearnNet {
@@ -48,13 +56,23 @@ struct LearnArgs {
   size_t r;                                // workspace offset of the per-row pieces [Mp, LRN_NR]
 };
 
+// tsidb_policy_learn_imit's additions to the rows kernel; target is read only where coef > 0 or the row's weight is not 0
+struct LearnImit {
+  const float *target, *weight;            // [rows, NA], [rows] (NULL: 1)
+  const int *skip;                         // [rows] (NULL: none)
+  float coef, surrogate_coef;
+  int huber;
+};
+
 __device__ __forceinline__ float act_prime(int kind, float y) {   // the activation's derivative from its output
   if (kind == ACT_ELU) return y > 0.f ? 1.f : y + 1.f;
   if (kind == ACT_TANH) return 1.f - y * y;
   return y > 0.f ? 1.f : 0.f;
 }
 
-__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArgs a) {
+template <bool IMIT>
+__device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const LearnImit &im) {
+  constexpr int NR = IMIT ? LRN_NR + LRN_NI : LRN_NR;   // the stride of the per-row pieces
   extern __shared__ float lrn_lds[];
   __shared__ int lrn_row[ACT_TILE];        // the stored row of each tile row, -1 = none
   const int which = blockIdx.y;
@@ -121,7 +139,7 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArg
         }
         dv = raw * a.value_coef * invM;
       }
-      R[(size_t)(m0 + tid) * LRN_NR + NA + LRN_R_LV] = lv;
+      R[(size_t)(m0 + tid) * NR + NA + LRN_R_LV] = lv;
       G[tid * LD] = dv;
       G[tid * LD + 1] = G[tid * LD + 2] = G[tid * LD + 3] = 0.f;
       ws[ln.g[last] + (size_t)(m0 + tid)] = dv;
@@ -136,6 +154,7 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArg
     if (tid < ACT_TILE) {
       const int j = lrn_row[tid];
       float piece[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dlogp = 0.f;
+      [[maybe_unused]] float ipiece[LRN_NI] = {0.f, 0.f, 0.f, 0.f};
       if (j >= 0) {
         float s = 0.f;
         for (int c = 0; c < NA; c++) {
@@ -156,22 +175,55 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArg
         piece[LRN_R_KL] = old - logp;
         piece[LRN_R_CLIPPED] = inside ? 0.f : 1.f;
         piece[LRN_R_USED] = 1.f;
+        if constexpr (IMIT) {
+          dlogp = dlogp * im.surrogate_coef;
+          if (im.skip && im.skip[j] != 0) {  // the env executed another action than the stored one: no surrogate for the row
+            dlogp = 0.f;
+            piece[LRN_R_LPI] = piece[LRN_R_KL] = piece[LRN_R_CLIPPED] = 0.f;
+            ipiece[LRN_I_SKIPPED] = 1.f;
+          }
+          const float w = im.weight ? im.weight[j] : 1.f;
+          ipiece[LRN_I_WSUM] = w;
+          ipiece[LRN_I_WPOS] = w > 0.f ? 1.f : 0.f;
+          if (im.target && w != 0.f) {       // a select, not a product: the label behind a zero weight is not read
+            float li = 0.f;
+            for (int c = 0; c < NA; c++) {
+              const float d = Y[tid * LD + c] - im.target[(size_t)j * NA + c], ad = fabsf(d);
+              li += im.huber ? (ad <= 1.f ? 0.5f * d * d : ad - 0.5f) : d * d;
+            }
+            ipiece[LRN_I_LIM] = w * (li / (float)NA);
+          }
+        }
       } else if (m0 + tid < a.M) {
         piece[LRN_R_BAD] = 1.f;
       }
       DL[tid * LD] = dlogp;
-      float *Rr = R + (size_t)(m0 + tid) * LRN_NR + NA;
+      float *Rr = R + (size_t)(m0 + tid) * NR + NA;
       for (int c = 0; c < 6; c++)
         if (c != LRN_R_LV || a.net[1].net.n_layers == 0) Rr[c] = piece[c];   // (LV is the critic's workgroup's; 0 without one)
+      if constexpr (IMIT)
+        for (int c = 0; c < LRN_NI; c++) Rr[6 + c] = ipiece[c];
     }
     __syncthreads();
     for (int idx = tid; idx < ACT_TILE * NA; idx += WAVE * ACT_WAVES) {
       const int r = idx / NA, c = idx - r * NA;
       const float z = G[r * LD + c], dlogp = DL[r * LD];
-      const float dmu = dlogp * z / expf(a.log_std[c]);
+      float dmu = dlogp * z / expf(a.log_std[c]);
+      if constexpr (IMIT) {                  // the label's term: on the mean alone, log_std gets nothing from it
+        const int j = lrn_row[r];
+        if (j >= 0 && im.coef > 0.f) {
+          const float w = im.weight ? im.weight[j] : 1.f;
+          if (w != 0.f) {
+            const float d = Y[r * LD + c] - im.target[(size_t)j * NA + c];
+            const float gd = im.huber ? fminf(fmaxf(d, -1.f), 1.f) : 2.f * d;
+            const float gi = im.coef * invM / (float)NA * w * gd;
+            dmu = dmu + gi;
+          }
+        }
+      }
       G[r * LD + c] = dmu;
       ws[ln.g[last] + (size_t)(m0 + r) * NA + c] = dmu;
-      R[(size_t)(m0 + r) * LRN_NR + c] = dlogp * (z * z - 1.f);
+      R[(size_t)(m0 + r) * NR + c] = dlogp * (z * z - 1.f);
     }
     if (tid < ACT_TILE * 4) {
       const int r = tid >> 2, c = NA + (tid & 3);
@@ -226,6 +278,9 @@ __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArg
     __syncthreads();
   }
 }
+
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArgs a) { policy_learn_rows_body<false>(a, LearnImit{}); }
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows_imit(LearnArgs a, LearnImit im) { policy_learn_rows_body<true>(a, im); }
 
 // ---------------------------------------------------------------------------- the weight gradients, segment by segment
 struct WgradJob {
@@ -297,7 +352,14 @@ struct ReduceArgs {
   float value_coef, entropy_coef;
 };
 
-__global__ __launch_bounds__(256) void k_policy_learn_reduce(ReduceArgs a) {
+// tsidb_policy_learn_imit's additions to the reduction: the coefficients of the full loss and where the four sums go
+struct ReduceImit {
+  float coef, surrogate_coef;
+  float *stats;          // [TSIDB_POL_IMIT_NSTATS]
+};
+
+template <bool IMIT>
+__device__ __forceinline__ void policy_learn_reduce_body(const ReduceArgs &a, const ReduceImit &im) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   const float *P = a.ws + a.part;
   auto total_of = [&](size_t off) {
@@ -327,10 +389,28 @@ __global__ __launch_bounds__(256) void k_policy_learn_reduce(ReduceArgs a) {
     a.stats[2] = ent;
     a.stats[3] = total_of(a.rp + NA + LRN_R_KL) * invM;
     a.stats[4] = total_of(a.rp + NA + LRN_R_CLIPPED) * invM;
-    a.stats[5] = lpi + a.value_coef * lv - a.entropy_coef * ent;
+    if constexpr (!IMIT) {
+      a.stats[5] = lpi + a.value_coef * lv - a.entropy_coef * ent;
+    } else {
+      const float lim = total_of(a.rp + NA + 6 + LRN_I_LIM) * invM;
+      const float spi = im.surrogate_coef * lpi;          // (statements of their own: a coefficient of 1 and one of 0 leave
+      float loss = spi + a.value_coef * lv - a.entropy_coef * ent;   //  the expression above, bit for bit)
+      if (im.coef > 0.f) {
+        const float t = im.coef * lim;
+        loss = loss + t;
+      }
+      a.stats[5] = loss;
+      im.stats[0] = lim;
+    }
     a.stats[6] = total_of(a.rp + NA + LRN_R_USED);
     a.stats[7] = total_of(a.rp + NA + LRN_R_BAD);
+  } else if (IMIT && e < a.rp + NA + LRN_NI) {   // the three other sums, a thread each: a segment-ordered sum is a serial chain of loads
+    const int k = (int)(e - (a.rp + NA));        // 1 .. LRN_NI - 1
+    im.stats[k] = total_of(a.rp + NA + 6 + k);
   }
 }
+
+__global__ __launch_bounds__(256) void k_policy_learn_reduce(ReduceArgs a) { policy_learn_reduce_body<false>(a, ReduceImit{}); }
+__global__ __launch_bounds__(256) void k_policy_learn_reduce_imit(ReduceArgs a, ReduceImit im) { policy_learn_reduce_body<true>(a, im); }
 
 } // namespace tsidb

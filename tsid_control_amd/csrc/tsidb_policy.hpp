@@ -4,7 +4,9 @@
 // state of the envs just reset, command resampling and observation noise - every draw a hash of (seed, stream, column, env,
 // episode, ep_len), no random state anywhere; with a terrain configured (tsidb_policy_terrain_config) the sim's per-env mass
 // scale, friction, floor plane and stepped terrain are redrawn for the envs just reset, and a height scan of that floor is
-// written beside the observation.  No reference counterpart: the reference runs one TSID-driven episode (main.py:113-124).
+// written beside the observation; with TSID in the loop its command is written as an action (the teacher), and
+// k_policy_teacher_mix turns that into the label of a stored rollout row and, for a share of the episodes, into the action the
+// env executes.  No reference counterpart: the reference runs one TSID-driven episode (main.py:113-124).
 //
 // Shape of all the kernels, as k_reset: one wavefront per env, lane = column of the env's rows (coalesced row loads and
 // stores), wave reductions (DPP) for the sums over actuators and wave votes for the flags over contacts; four envs per
@@ -531,6 +533,34 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_teacher_ob
     o[2 + lane] = fresh && g != 1 ? T(0) : v;
   }
   if (lane < NA) o[14 + lane] = fresh ? T(0) : tau[E * NA + m.mj_ctrl_qidx[lane] - 7];
+}
+
+// ---------------------------------------------------------------------------- imitation: the teacher's label, DAgger's mixing
+constexpr int DR_S_TEACHER_MIX = 23;   // stream 23 of the key layout (21 / 22: the action noise, tsidb_actor.hpp)
+
+// after the actor launch, before k_policy_act: the label of the row the actor has just stored, and - for the episodes the draw
+// hands to the teacher - the teacher's action in place of the policy's.  teacher_action is what k_policy_teacher left at the end
+// of the previous step: formed on the state one sim step before the observation the actor saw.  ep_len == 0: the previous step
+// (or reset()) restarted the env, the label belongs to the fallen robot or to nothing - weight 0, never executed.  Lane a < NA
+// holds actuator a; U is the same on every lane (a hash of wave-uniform values).  action may be NULL (labels alone).
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_teacher_mix(int n, PolicyBufs<T> b, const T *__restrict__ teacher_action, T *action,
+                                                                                  float *label, float *weight, int *executed,
+                                                                                  const float *__restrict__ beta, unsigned long long seed,
+                                                                                  unsigned long long env_offset) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= NA) return;
+  const size_t E = (size_t)e, row = E * NA + lane;
+  const bool live = b.ep_len[E] > 0;
+  const double u = pol_draw(seed, DR_S_TEACHER_MIX, 0, env_offset + (unsigned long long)e, (unsigned long long)b.episode[E] << 32);
+  const bool exec = live && beta && u < (double)beta[0];
+  const T ta = teacher_action[row];
+  label[row] = (float)ta;
+  if (exec && action) action[row] = ta;
+  if (lane == 0) {
+    weight[E] = live ? 1.f : 0.f;
+    executed[E] = exec ? 1 : 0;
+  }
 }
 
 } // namespace tsidb

@@ -210,9 +210,17 @@ class PolicyActor:
 class RolloutStorage:
     """[T, N, ...] tensors of PolicyEnv.rollout: actor_input, critic_input (None without a critic), action, mean [T, N, .], logp
     [T, N] in float32, value [T + 1, N] float32 (the last row: the critic on the observation after the last step; zeros without a
-    critic), reward, done [T, N] in the env's dtype, timeout [T, N] int32; advantage, returns [T, N] float32 once gae() has run."""
+    critic), reward, done [T, N] in the env's dtype, timeout [T, N] int32; advantage, returns [T, N] float32 once gae() has run.
 
-    def __init__(self, env, actor, steps):
+    teacher = True (an env with tsid set, in "position" or "motor" mode) adds what PolicyEnv.rollout records of the TSID teacher
+    (include/tsidb.h tsidb_policy_teacher_mix): teacher_action [T, N, NA] float32, the label of each stored row; teacher_weight
+    [T, N] float32, 0 for the rows whose env had just been restarted (their label belongs to the fallen robot); teacher_executed
+    [T, N] int32, 1 where the env executed the teacher's action instead of the stored one.  action and logp stay the policy's own
+    sample and density.  The default allocates nothing new."""
+
+    teacher_action = teacher_weight = teacher_executed = None
+
+    def __init__(self, env, actor, steps, teacher=False):
         wc = env.wc
         T, N, NA = int(steps), env.num_envs, env.NA
         self.env, self.actor, self.steps = env, actor, T
@@ -223,10 +231,21 @@ class RolloutStorage:
         self.value = z(T + 1, N)
         self.reward, self.done, self.timeout = z(T, N, dt=wc.dtype), z(T, N, dt=wc.dtype), z(T, N, dt=torch.int32)
         self.advantage = self.returns = None
+        if not isinstance(teacher, bool):
+            raise _lib.TsidbError(f"RolloutStorage: teacher must be a bool, got {teacher!r}")
+        if teacher:
+            if getattr(env, "tsid", None) is None:
+                raise _lib.TsidbError("RolloutStorage: teacher = True needs an env with tsid = 'stand' or 'walk': there is no teacher to label with")
+            if getattr(env, "mode", None) not in ("position", "motor"):
+                raise _lib.TsidbError(f"RolloutStorage: teacher = True needs mode 'position' or 'motor', got {getattr(env, 'mode', None)!r} "
+                                      "(in residual mode teacher_action is 0 by definition: there is nothing to imitate)")
+            self.teacher_action, self.teacher_weight = z(T, N, NA), z(T, N)
+            self.teacher_executed = z(T, N, dt=torch.int32)
 
     def tensors(self):
         return [t for t in (self.actor_input, self.critic_input, self.action, self.mean, self.logp, self.value, self.reward, self.done,
-                            self.timeout, self.advantage, self.returns) if t is not None]
+                            self.timeout, self.advantage, self.returns, self.teacher_action, self.teacher_weight, self.teacher_executed)
+                if t is not None]
 
     def gae(self, gamma=0.99, lam=0.95):
         """(advantage, returns), each [T, N] float32: rsl_rl's generalised advantage estimation of the stored rollout, one launch
@@ -243,7 +262,10 @@ class RolloutStorage:
 def rollout_written(storage):
     """Every tensor a PolicyEnv.rollout into `storage` writes beyond the env's own (PolicyEnv.written()): what a caller that
     captures a rollout in a graph keeps alive, and rewinds after its warm-up if it compares runs."""
-    yield from storage.tensors()
+    yield from storage.tensors()    # (a teacher storage's labels, weights and executed flags among them)
     yield storage.actor.action
+    beta = getattr(storage.env, "_teacher_beta", None)
+    if beta is not None:
+        yield beta
     if storage.actor.normalizer is not None:
         yield from storage.actor.normalizer.written()

@@ -24,6 +24,10 @@ steps (tick on the sim state, then sim; in "walk" each behind the walking refere
 launches join the step - after the reward the teacher terms, TSID's failed QPs and its command as an action
 (tsidb_policy_teacher), after the observation the controller's references in the base frame (tsidb_policy_teacher_obs).
 mode = "residual" adds the policy's torque to TSID's tau; "position" / "motor" leave the sim to the policy and TSID beside it.
+
+In those two modes the teacher can be learned from: rollout() into a RolloutStorage(teacher=True) records TSID's action as the
+label of every stored row and, with teacher_beta, executes it in place of the policy's for that share of the episodes (DAgger's
+mixing; one more launch per step, tsidb_policy_teacher_mix), and PolicyLearner(imitation_coef=...) has the term for the labels.
 """
 import copy
 import ctypes as C
@@ -277,6 +281,8 @@ class PolicyEnv:
     terrain = terrain_level = height_scan = None
     # TSID in the loop: None = no tick; sched = the walking schedule of tsid = "walk", clock its device time
     tsid = sched = clock = None
+    # the [1] float32 device tensor behind rollout(teacher_beta = a float), made at the first such call
+    _teacher_beta = None
 
     def __init__(self, conf=None, num_envs=None, device=None, decimation=10, mode="position", action_scale=0.25,
                  default_joint_pos=None, action_clip=100.0, delay=None, filter_alpha=1.0, command_range=((0.0, 0.0),) * 3,
@@ -484,6 +490,31 @@ class PolicyEnv:
         wc._call("tsidb_policy_teacher_obs", C.byref(self._bufs), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos), _ptr(wc.tau),
                  _ptr(self.teacher_obs), self.teacher_obs.shape[1], wc._stream())
 
+    def _teacher_mix(self, actor, action, label, weight, executed, beta):
+        """one tsidb_policy_teacher_mix launch: labels, weights and executed flags of this step into the three tensors, and the
+        teacher's action over `action` (None: not touched) for the envs whose episode the draw gives to the teacher; beta: a [1]
+        float32 device tensor or None (= 0); the seed and the env offset are the actor's, as for its action noise"""
+        self.wc._call("tsidb_policy_teacher_mix", C.byref(self._bufs), _ptr(self.teacher_action), _ptr(action),
+                      _ptr(label), _ptr(weight), _ptr(executed), _ptr(beta), C.c_uint64(actor.seed),
+                      C.c_uint64(actor.env_offset), self.wc._stream())
+
+    def _beta_tensor(self, teacher_beta):
+        """teacher_beta as the [1] float32 device tensor the launch reads, or None"""
+        wc = self.wc
+        if teacher_beta is None:
+            return None
+        if isinstance(teacher_beta, torch.Tensor):
+            if teacher_beta.dtype != torch.float32 or tuple(teacher_beta.shape) != (1,) or teacher_beta.device != wc.device:
+                raise _lib.TsidbError(f"PolicyEnv.rollout: a teacher_beta tensor must be [1] float32 on {wc.device}, got "
+                                      f"{(tuple(teacher_beta.shape), teacher_beta.dtype, teacher_beta.device)}")
+            return teacher_beta
+        if isinstance(teacher_beta, bool) or not isinstance(teacher_beta, (int, float)) or not 0 <= teacher_beta <= 1:
+            raise _lib.TsidbError(f"PolicyEnv.rollout: teacher_beta must be None, a number in [0, 1] or a [1] float32 tensor, got {teacher_beta!r}")
+        if self._teacher_beta is None:
+            self._teacher_beta = torch.zeros(1, dtype=torch.float32, device=wc.device)
+        self._teacher_beta.fill_(float(teacher_beta))
+        return self._teacher_beta
+
     def _after_reset_done(self):
         """what reset() and step() launch behind reset_done, each only while its group is on: a new plan, reset noise and new
         tables for the envs just restarted, then the observation, the height scan and the teacher's observation of every env"""
@@ -553,7 +584,7 @@ class PolicyEnv:
             info["push"] = wc.xfrc[:, 0, :3]
         return self.obs, self.reward, self.done, info
 
-    def rollout(self, actor, steps, storage=None):
+    def rollout(self, actor, steps, storage=None, teacher_beta=None):
         """`steps` policy steps with `actor` (a PolicyActor on this env) in the loop: per step one actor launch - networks, sample,
         log-probability and value on the current observation, written straight into slot t of the storage - then step(action) and
         three device copies of reward, done and timeout; last, one critic-only launch on the final observation into value[steps].
@@ -561,7 +592,17 @@ class PolicyEnv:
         normalises with the statistics as they are and does not update (the next rollout's first step counts that observation).
         storage: a RolloutStorage of this env, actor and length to reuse (None = a new one); returned.  Everything stays on the
         current stream with no host synchronisation, so a whole rollout can be captured in a graph (policy_actor.rollout_written
-        lists what it writes beyond written()).  storage.gae(gamma, lam) then gives the advantages and returns."""
+        lists what it writes beyond written()).  storage.gae(gamma, lam) then gives the advantages and returns.
+
+        With a storage built with teacher = True one more launch per step sits between the actor launch and step()
+        (tsidb_policy_teacher_mix): slot t of teacher_action / teacher_weight / teacher_executed gets TSID's label for the stored
+        row, its weight (0 for an env the previous step restarted) and whether the env executes the teacher's action - DAgger's
+        mixing: for a share teacher_beta of the EPISODES (one draw per env and episode, stream 23 of the randomisation's keys, with
+        the actor's seed and env_offset) the teacher's action overwrites the sampled one before the step; storage.action and
+        storage.logp stay the policy's own.  teacher_beta: None (no mixing), a number in [0, 1] (kept in a [1] device tensor of
+        the env's), or a [1] float32 device tensor of the caller's - read on the device at every launch, so a captured rollout
+        follows a beta that a device op decays between replays.  With a plain storage the launches are those above, and
+        teacher_beta must be None."""
         from .policy_actor import PolicyActor, RolloutStorage
         if not isinstance(actor, PolicyActor) or actor.env is not self:
             raise _lib.TsidbError("PolicyEnv.rollout: actor must be a PolicyActor built on this env")
@@ -572,10 +613,17 @@ class PolicyEnv:
         elif not isinstance(storage, RolloutStorage) or storage.env is not self or storage.actor is not actor or storage.steps != steps:
             raise _lib.TsidbError("PolicyEnv.rollout: storage must be a RolloutStorage of this env, this actor and this many steps")
         st = storage
+        labels = st.teacher_action is not None
+        if teacher_beta is not None and not labels:
+            raise _lib.TsidbError("PolicyEnv.rollout: teacher_beta needs a storage built with teacher = True (the executed flags are "
+                                  "what keeps the surrogate off the teacher's rows)")
+        beta = self._beta_tensor(teacher_beta)
         for t in range(steps):
             actor.observe()
             actor._launch(True, action=actor.action, action32=st.action[t], mean=st.mean[t], logp=st.logp[t], value=st.value[t],
                           actor_input=st.actor_input[t], critic_input=st.critic_input[t] if st.critic_input is not None else None)
+            if labels:
+                self._teacher_mix(actor, actor.action, st.teacher_action[t], st.teacher_weight[t], st.teacher_executed[t], beta)
             self.step(actor.action)
             st.reward[t].copy_(self.reward)
             st.done[t].copy_(self.done)

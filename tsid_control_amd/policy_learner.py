@@ -44,12 +44,19 @@ class PolicyLearner:
     """actor: the PolicyActor whose networks and log_std are learned.  clip: the surrogate's and the value loss's range (> 0);
     value_coef, entropy_coef (>= 0): loss = L_pi + value_coef L_v - entropy_coef entropy; value_clip: the clipped value loss
     (False: the plain squared error); normalize_advantage: advantages minus their mean, over their std + 1e-8, of the whole
-    storage.
+    storage.  imitation_coef (>= 0), imitation_loss ("mse" or "huber", delta 1): a term imitation_coef L_im on the distance of the
+    actor's mean from the storage's teacher labels (a RolloutStorage built with teacher = True; include/tsidb.h
+    tsidb_policy_learn_imit), weighted by teacher_weight, with the surrogate kept off the rows the env executed the teacher's
+    action on (teacher_executed); surrogate_coef (>= 0) scales L_pi - loss = surrogate_coef L_pi + value_coef L_v - entropy_coef
+    entropy + imitation_coef L_im, so surrogate_coef = value_coef = entropy_coef = 0 is pure distillation (rsl_rl's Distillation)
+    and the defaults are PPO as it is, with the calls it made before the term existed.  imit_stats [4] float32
+    (_lib.POL_IMIT_STATS): L_im, the sum of the weights, the rows with a weight, the rows whose surrogate was skipped.
 
     Tensors: stats [8] float32, written by backward() - policy_loss, value_loss, entropy, approx_kl, clip_fraction, loss, rows,
     bad_indices (_lib.POL_LEARN_STATS); adv_stats [2] (mean, 1 / std); workspace (grown to the largest minibatch seen)."""
 
-    def __init__(self, actor, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=True, normalize_advantage=True):
+    def __init__(self, actor, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=True, normalize_advantage=True, imitation_coef=0.0,
+                 imitation_loss="mse", surrogate_coef=1.0):
         if not isinstance(actor, PolicyActor):
             raise _bad(f"actor must be a PolicyActor, got {type(actor).__name__}")
         self.actor, self.env = actor, actor.env
@@ -59,11 +66,21 @@ class PolicyLearner:
             if not isinstance(x, bool):
                 raise _bad(f"{name} must be a bool, got {x!r}")
         self.value_clip, self.normalize_advantage = value_clip, normalize_advantage
+        self.imitation_coef, self.surrogate_coef = _number("imitation_coef", imitation_coef, 0.0), _number("surrogate_coef", surrogate_coef, 0.0)
+        if imitation_loss not in _lib.POL_IMIT_LOSSES:
+            raise _bad(f"imitation_loss must be one of {_lib.POL_IMIT_LOSSES}, got {imitation_loss!r}")
+        self.imitation_loss = imitation_loss
         dev = self.env.wc.device
         self.stats = torch.zeros(len(_lib.POL_LEARN_STATS), dtype=torch.float32, device=dev)
         self.adv_stats = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+        self.imit_stats = torch.zeros(len(_lib.POL_IMIT_STATS), dtype=torch.float32, device=dev)
         self.workspace, self._ws_rows = None, 0
         self._cfg = _lib.PolicyLearnCfg(self.clip, self.value_coef, self.entropy_coef, int(value_clip))
+
+    @property
+    def _imit_on(self):
+        """anything but PPO as it is: backward() goes through tsidb_policy_learn_imit"""
+        return self.imitation_coef != 0.0 or self.surrogate_coef != 1.0
 
     def parameters(self):
         """every tensor backward() writes a .grad of: the weights and biases of the actor, of the critic, and log_std - what an
@@ -91,7 +108,7 @@ class PolicyLearner:
         if self.workspace is None or M > self._ws_rows:
             wc, a = self.env.wc, self.actor
             n = C.c_size_t(0)
-            wc._call("tsidb_policy_learn_workspace", C.byref(a.actor_net.struct),
+            wc._call("tsidb_policy_learn_imit_workspace" if self._imit_on else "tsidb_policy_learn_workspace", C.byref(a.actor_net.struct),
                      C.byref(a.critic_net.struct) if a.critic_net is not None else None, M, C.byref(n))
             self.workspace = torch.empty(max(1, (n.value + 3) // 4), dtype=torch.float32, device=wc.device)
             self._ws_rows, self._ws_bytes = M, n.value
@@ -112,6 +129,8 @@ class PolicyLearner:
             raise _bad("storage must be a RolloutStorage of this learner's actor")
         if storage.advantage is None:
             raise _bad("storage.gae() has not run: there are no advantages and returns")
+        if self.imitation_coef > 0 and storage.teacher_action is None:
+            raise _bad("imitation_coef > 0 needs a storage with the teacher's labels (RolloutStorage(..., teacher=True))")
         if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or index.shape[0] < 1 \
                 or index.device != wc.device or not index.is_contiguous():
             what = (tuple(index.shape), index.dtype, index.device) if isinstance(index, torch.Tensor) else type(index).__name__
@@ -133,10 +152,17 @@ class PolicyLearner:
         cg = self._grads_of(a.critic_net) if a.critic_net is not None else None
         self._last = (batch, ag, cg)       # (alive until the next call: the library copies them during the call, a recorder may look later)
         self._last_storage, self._last_index = storage, index    # (what a PolicyOptimizer's KL is taken over)
-        wc._call("tsidb_policy_learn", C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None,
-                 C.byref(batch), C.byref(ag), C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()),
-                 C.c_void_p(self._grad(a.log_std).data_ptr()), C.byref(self._cfg), C.c_void_p(ws.data_ptr()),
-                 C.c_size_t(ws.numel() * 4), C.c_void_p(stats.data_ptr()), wc._stream())
+        head = (C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None, C.byref(batch), C.byref(ag),
+                C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()), C.c_void_p(self._grad(a.log_std).data_ptr()),
+                C.byref(self._cfg))
+        tail = (C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel() * 4), C.c_void_p(stats.data_ptr()), wc._stream())
+        if not self._imit_on:
+            wc._call("tsidb_policy_learn", *head, *tail)
+            return stats
+        imit = _lib.PolicyImit(p(storage.teacher_action), p(storage.teacher_weight), p(storage.teacher_executed), self.imitation_coef,
+                               self.surrogate_coef, _lib.POL_IMIT_LOSSES.index(self.imitation_loss), p(self.imit_stats))
+        self._last_imit = imit             # (alive until the next call, as the batch)
+        wc._call("tsidb_policy_learn_imit", *head, C.byref(imit), *tail)
         return stats
 
     def outputs(self, M):
@@ -172,5 +198,6 @@ class PolicyLearner:
         return out
 
     def written(self):
-        """the tensors backward() writes: what a caller that captures it in a graph keeps alive"""
-        return [self._grad(p) for p in self.parameters()] + [self.stats, self.adv_stats] + ([self.workspace] if self.workspace is not None else [])
+        """the tensors backward() writes: what a caller that captures it in a graph keeps alive (imit_stats while the imitation
+        term or a surrogate_coef is on: the plain call does not write it)"""
+        return [self._grad(p) for p in self.parameters()] + [self.stats, self.adv_stats] + ([self.imit_stats] if self._imit_on else []) + ([self.workspace] if self.workspace is not None else [])
