@@ -642,6 +642,78 @@ int tsidb_policy_teacher_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
 int tsidb_policy_teacher_mix(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *teacher_action, void *action, float *label,
                              float *weight, int32_t *executed, const float *beta, uint64_t seed, uint64_t env_offset, void *stream);
 
+/* ---- episode statistics and a terrain curriculum: what a training loop logs every iteration (mean episode return and length,
+ * per-term episode sums, share of timeouts, distance travelled) and legged_gym's terrain curriculum (_update_terrain_curriculum),
+ * kept on the device inside the step - tsidb_policy_episode_end after tsidb_policy_reward (and tsidb_policy_teacher where it runs)
+ * and before tsidb_reset_done, which wipes the final position of a fallen env; tsidb_policy_episode_begin after tsidb_reset_done,
+ * tsidb_policy_reset_noise and tsidb_policy_terrain_reset, where the first position of the new episode exists.  Off by default:
+ * neither launch is made by anything else, and no other entry reads what they write except tsidb_policy_terrain_reset its level.
+ *
+ * The record of an episode, float64 whatever the path's type (as the normaliser's statistics), TSIDB_POL_EP_NREC columns:
+ *   COUNT         1 per finished episode
+ *   TIMEOUT       1 if the episode ended by its length alone (timeout of tsidb_policy_bufs)
+ *   LENGTH        policy steps: ep_len after tsidb_policy_reward incremented it
+ *   RETURN        sum over the episode of the env's reward as it stands in the rows when the kernel runs, teacher terms included
+ *   DISPLACEMENT  d = sqrt(dx^2 + dy^2) of the base xy between the episode's first state and its last [m]
+ *   LEVEL         the terrain level the episode ran on
+ *   TERMS ..      the TSIDB_POL_NT sums of the unweighted reward terms
+ *   TEACH ..      the TSIDB_POL_TEACH_NT sums of the unweighted teacher terms; 0 while no teacher_terms pointer is given */
+enum { TSIDB_POL_EP_COUNT = 0, TSIDB_POL_EP_TIMEOUT, TSIDB_POL_EP_LENGTH, TSIDB_POL_EP_RETURN, TSIDB_POL_EP_DISPLACEMENT, TSIDB_POL_EP_LEVEL,
+       TSIDB_POL_EP_TERMS /*TSIDB_POL_NT*/, TSIDB_POL_EP_TEACH = TSIDB_POL_EP_TERMS + TSIDB_POL_NT /*TSIDB_POL_TEACH_NT*/,
+       TSIDB_POL_EP_NREC = TSIDB_POL_EP_TEACH + TSIDB_POL_TEACH_NT };
+
+/* tsidb_policy_episode_config's parameter vector (float64, host) */
+enum { TSIDB_POL_EPP_CURRICULUM = 0 /* 0 / 1: tsidb_policy_episode_end writes level */, TSIDB_POL_EPP_UP_DISTANCE /* m, > 0 */,
+       TSIDB_POL_EPP_DOWN_FRACTION /* >= 0, of the distance the command asked for */, TSIDB_POL_EPP_RANDOM_TOP /* 0 / 1 */,
+       TSIDB_POL_EPP_NPARAMS };
+
+/* the per-env episode state: device buffers owned by the caller; all but level and teacher_terms are required */
+typedef struct tsidb_policy_episode {
+  double *run;               /* [N, TSIDB_POL_EP_NREC] the running episode's sums in the columns LENGTH, RETURN, TERMS, TEACH; the others stay 0 */
+  double *start_xy;          /* [N, 2] base xy of the running episode's first state */
+  double *last;              /* [N, TSIDB_POL_EP_NREC] the record of the env's most recently finished episode */
+  double *sum;               /* [N, TSIDB_POL_EP_NREC] per-env sums of the records since the caller last zeroed it */
+  int32_t *level;            /* [N] the terrain level tsidb_policy_terrain_reset reads; may be NULL while the curriculum is off */
+  const void *teacher_terms; /* [N, TSIDB_POL_TEACH_NT] in the path's type, as tsidb_policy_teacher wrote them; may be NULL */
+} tsidb_policy_episode;
+
+/* Copies ep_params [TSIDB_POL_EPP_NPARAMS] (host, float64) into the handle; NULL with n_params 0 switches the slice off again (the
+ * state of a new handle: both launches fail).  First waits for the kernels in flight, as tsidb_policy_config does.  Rejects a
+ * wrong n_params, non-finite values, a flag other than 0 / 1, UP_DISTANCE <= 0 with the curriculum on and a negative fraction;
+ * nothing of a rejected vector is taken.  The curriculum also needs tsidb_policy_terrain_config (num_levels, the seed and the env
+ * offset are the terrain's), max_episode_steps > 0 and a level pointer: tsidb_policy_episode_end fails without them. */
+int tsidb_policy_episode_config(tsidb_handle h, const double *ep_params, int n_params);
+
+/* after tsidb_policy_reward (and tsidb_policy_teacher), before tsidb_reset_done.  qpos [N, NQ] the sim state the step ended on;
+ * reward and done point at the first env's values, row_ld elements apart, as tsidb_policy_reward takes them; terms, timeout,
+ * ep_len, episode and command are read from bufs.  For every env, with x+ = x finite ? x : 0 (a select: one NaN step does not
+ * poison an iteration's log):
+ *   run[LENGTH] += 1, run[RETURN] += (double)reward +, run[TERMS + k] += (double)terms[k] +, run[TEACH + k] += (double)teacher_terms[k] +
+ * For an env whose done flag is set: record = (1, timeout, ep_len, run[RETURN], d, lvl, run[TERMS ..], run[TEACH ..]) with
+ * d = |(double)qpos[0:2] - start_xy| and lvl = level[e] clamped to 0 .. num_levels - 1 (to >= 0 before
+ * tsidb_policy_terrain_config; 0 where level is NULL); last[e] = record; sum[e] += record, RETURN and DISPLACEMENT through the
+ * same select.  last of the other envs is not touched.
+ * With the curriculum on, level[e] of a done env becomes legged_gym's rule, L = num_levels, T = max_episode_steps * (decimation *
+ * dt) - the seconds of a whole episode, decimation * dt the step tsidb_policy_reward advances the air times by:
+ *   up = d > UP_DISTANCE;  down = !up && d < DOWN_FRACTION |command_xy| T  (the command as it stands, before the reset redraws it)
+ *   lvl += up - down;  below 0 -> 0;  >= L -> RANDOM_TOP ? min(L - 1, floor(U L)) : L - 1
+ * everything in float64; a NaN d compares false both ways and leaves the clamped level.  U is one more stream of the
+ * randomisation's key layout (key = seed + ((stream * 256 + column) * 2^32), the same hash), seed and env_offset the terrain's:
+ *   stream  draw                     column              counter
+ *   24      graduate's level         -                   the episode about to start (episode + 1 when the kernel runs), as 12-19
+ * A plain asynchronous launch in the policy kernels' shape: no atomics, no host read, no allocation, capturable.  Fails (message
+ * via tsidb_last_error) where tsidb_policy_act fails, before tsidb_policy_episode_config, on a NULL required buffer or
+ * row_ld < 1, and with the curriculum on before tsidb_policy_terrain_config, with max_episode_steps = 0 or with level NULL. */
+int tsidb_policy_episode_end(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *qpos,
+                             const void *reward, const void *done, int row_ld, void *stream);
+
+/* after tsidb_reset_done(done_rows, ...), tsidb_policy_reset_noise and tsidb_policy_terrain_reset; before or after
+ * tsidb_policy_obs.  For an env whose done flag is set (column TSIDB_NOBS + 1 of done_rows [N, rows_ld >= TSIDB_NROW]):
+ * start_xy = (double)qpos[0:2] and the run row zeroed; every other row stays bit for bit.  Launch and failures as above (the
+ * curriculum asks nothing of this one). */
+int tsidb_policy_episode_begin(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *done_rows,
+                               int rows_ld, const void *qpos, void *stream);
+
 /* ---- the policy's side of a rollout: a dense actor and an optional critic evaluated on the env's own rows, the Gaussian sample
  * with its log-probability, and the advantages of a recorded rollout.  Both calls are plain asynchronous launches on the given
  * stream: no allocation, no host synchronisation, no state of their own - T policy steps with their actor calls can be captured

@@ -59,7 +59,14 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               backward() with the term off (the parent commit's call) and on, and the 16-step rollout into a plain storage (the
               parent's launches), into a teacher storage, and with beta = 0.5, in alternating windows (a process per case);
               default profiles/policy_imitation.json.  Kernel times: rocprofv3 --kernel-trace --stats -- python
-              tools/policy_env.py --distill --trace ENVS CALLS (CALLS backward() with the term off, then on)"""
+              tools/policy_env.py --distill --trace ENVS CALLS (CALLS backward() with the term off, then on)
+    python tools/policy_env.py --episodes [out.json]   episode statistics and the terrain curriculum (PolicyEnv(curriculum=...): two
+              launches per step) against the env without them and against the same bookkeeping with torch ops behind every step
+              (TorchEpisodes below, which cannot see a fallen env's final position), in alternating windows, at 4096 and 512 envs,
+              decimation 4; then the curriculum under TSID's own walk (tsid="walk", zero residual, eight levels of steps up to 4 cm, strips of 3 - 6 cm):
+              the level histogram per iteration and the share of each level's episodes that went up; default
+              profiles/policy_episode.json.  --episodes --curriculum: that second part alone.  Kernel times: rocprofv3 --kernel-trace
+              --stats -- python tools/policy_env.py --episodes --trace ENVS STEPS"""
 import json
 import sys
 import time
@@ -720,6 +727,129 @@ def main_distill(args):
            run=case("run", "512"), control=case("control", "512"), timings=[case("time", "4096"), case("time", "512")])
 
 
+EP_TERRAIN = dict(TERRAIN, num_levels=3)
+EP_CURRICULUM = dict(up_distance=0.05, down_fraction=0.5, random_top=True)
+
+
+class TorchEpisodes:
+    """the slice's bookkeeping with torch ops after each step() of a plain env, as a caller had to write it: running sums of
+    reward and terms, records of the finished episodes, legged_gym's level rule.  It runs behind the reset, so the position it
+    reads for a done env is already the new episode's: its displacement of a finished episode is wrong (measured from the
+    penultimate position here), and its level reaches the terrain one episode late.  The cost is what is compared."""
+
+    def __init__(self, env, cur):
+        self.env, self.cur = env, cur
+        n, dev = env.num_envs, env.device
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+        self.run, self.last, self.sum, self.start = z(n, _lib.POL_EP_NREC), z(n, _lib.POL_EP_NREC), z(n, _lib.POL_EP_NREC), env.wc.qpos[:, :2].double().clone()
+        self.prev_xy, self.prev_cmd = env.wc.qpos[:, :2].double().clone(), env.command[:, :2].double().clone()
+        self.t_episode = float(env.params[_lib.POL_P_MAX_EPISODE_STEPS]) * env.decimation * env.wc.conf.dt
+        self.levels = int(env.ter_params[_lib.POL_TER_NUM_LEVELS])
+
+    def step(self, action):
+        env = self.env
+        _, reward, done, info = env.step(action)
+        fin = lambda x: torch.where(torch.isfinite(x), x, torch.zeros_like(x)).double()
+        self.run[:, _lib.POL_EP_LENGTH] += 1
+        self.run[:, _lib.POL_EP_RETURN] += fin(reward)
+        self.run[:, _lib.POL_EP_TERMS:_lib.POL_EP_TEACH] += fin(info["terms"])
+        fresh = done != 0
+        d = (self.prev_xy - self.start).norm(dim=1)
+        lvl = env.terrain_level.clamp(0, self.levels - 1)
+        rec = self.run.clone()
+        rec[:, _lib.POL_EP_COUNT], rec[:, _lib.POL_EP_TIMEOUT], rec[:, _lib.POL_EP_DISPLACEMENT] = 1, info["timeout"].double(), d
+        rec[:, _lib.POL_EP_LEVEL] = lvl.double()
+        self.last = torch.where(fresh[:, None], rec, self.last)
+        self.sum += torch.where(fresh[:, None], torch.nan_to_num(rec), torch.zeros_like(rec))
+        up = d > self.cur["up_distance"]
+        down = (d < self.prev_cmd.norm(dim=1) * self.t_episode * self.cur["down_fraction"]) & ~up
+        new = lvl + up.int() - down.int()
+        new = torch.where(new >= self.levels, torch.randint_like(new, self.levels), new.clamp(min=0))
+        env.terrain_level.copy_(torch.where(fresh, new, env.terrain_level))
+        xy = env.wc.qpos[:, :2].double()
+        self.start = torch.where(fresh[:, None], xy, self.start)
+        self.run *= (~fresh)[:, None]
+        self.prev_xy.copy_(xy)
+        self.prev_cmd.copy_(env.command[:, :2])
+
+
+def measure_episodes(n, decimation, window=300, windows=4, preroll=60):
+    """off: PolicyEnv(terrain=EP_TERRAIN); on: the same with the curriculum (statistics and levels on the device); torch: `off`
+    with TorchEpisodes behind every step.  Policy-steps/s in alternating windows of one process"""
+    delay = delays(n)
+    make = lambda **kw: PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, terrain=EP_TERRAIN, **kw, **KW)
+    envs = dict(off=make(), on=make(curriculum=EP_CURRICULUM), torch=make())
+    book = TorchEpisodes(envs["torch"], EP_CURRICULUM)
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, envs["on"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    run = {k: stepper(envs[k], n, envs[k].NA) for k in ("off", "on")}
+    run["torch"] = lambda k: [book.step(actions[i & 15]) for i in range(k)]
+    r = alternate(run, window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    stats = {k: float(v) for k, v in envs["on"].episode_stats().items()}
+    return dict(envs=n, decimation=decimation, window_policy_steps=window, windows=windows, **r, on_over_off=med["on"] / med["off"],
+                torch_over_off=med["torch"] / med["off"], episode_us_per_policy_step=us["on"] - us["off"],
+                torch_us_per_policy_step=us["torch"] - us["off"], torch_cost_over_fused_cost=(us["torch"] - us["off"]) / max(us["on"] - us["off"], 1e-9),
+                restarts={k: int(e.episode.sum()) - n for k, e in envs.items()}, episode_stats_on=stats)
+
+
+def curriculum_run(n=512, iters=10, levels=8, height=0.04, up_distance=None, steps=400, decimation=4):
+    """TSID walking with a zero residual on stepped terrain with the curriculum on: per iteration (one episode length of policy
+    steps) the level histogram and the episode statistics; per level the share of its finished episodes that went up"""
+    from tsid_control_amd.walk_planner import op3_closed_loop_walking_conf
+    conf = op3_closed_loop_walking_conf(RobotConfig())
+    conf.closed_loop, conf.reference_quirks = True, False
+    ter = dict(seed=1, step_height=(height, height), step_length=(0.03, 0.06), step_prob=0.5, flat_cells=0, num_levels=levels)   # (short strips, none kept flat but the one under the robot: a 3.2 s walk of some 12 cm crosses several edges)
+    kw = dict(num_envs=n, device="cuda:0", decimation=decimation, mode="residual", action_scale=0.05, max_episode_steps=steps, tsid="walk",
+              teacher_weights=TEACH, reward_weights=WEIGHTS, terrain=ter, command_range=((0.08, 0.08), (0.0, 0.0), (0.0, 0.0)))   # (about TSID's own pace: less than half of it moves an env down)
+    if up_distance is None:        # half of what TSID walks in an episode on the level floor, measured first
+        flat = PolicyEnv(conf, episode_stats=True, **dict(kw, terrain=dict(ter, step_height=(0.0, 0.0))))
+        a = torch.zeros(n, flat.NA, dtype=flat.dtype, device=flat.device)
+        for _ in range(steps):
+            flat.step(a)
+        s = flat.episode_stats()
+        flat_stats = {k: float(s[k]) for k in ("episodes", "timeouts", "length", "displacement")}
+        up_distance = 0.5 * flat_stats["displacement"]
+    else:
+        flat_stats = None
+    env = PolicyEnv(conf, curriculum=dict(up_distance=up_distance, down_fraction=0.5, random_top=False), **kw)
+    a = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
+    out, ups, ends = [], torch.zeros(levels, device=env.device), torch.zeros(levels, device=env.device)
+    for it in range(iters):
+        for _ in range(steps):
+            _, _, done, info = env.step(a)
+            rec = info["episode_last"]
+            fresh = done != 0
+            lvl = rec[:, _lib.POL_EP_LEVEL].long()
+            ends.index_add_(0, lvl, fresh.float())
+            ups.index_add_(0, lvl, (fresh & (rec[:, _lib.POL_EP_DISPLACEMENT] > up_distance)).float())
+        s = env.episode_stats()
+        out.append(dict(iteration=it, level_histogram=torch.bincount(env.terrain_level.long(), minlength=levels).tolist(),
+                        **{k: float(s[k]) for k in ("episodes", "timeouts", "length", "return", "displacement", "level")}))
+    share = (ups / ends.clamp(min=1)).tolist()
+    return dict(envs=n, tsid="walk", mode="residual, zero residual", policy_steps_per_iteration=steps, decimation=decimation, num_levels=levels,
+                step_height_of_level_m=[height * (l + 1) / levels for l in range(levels)], up_distance_m=up_distance, flat_floor=flat_stats,
+                iterations=out, episodes_finished_by_level=ends.tolist(), share_that_went_up_by_level=share)
+
+
+def main_episodes(args):
+    """--episodes: the cost of the slice against off and against torch bookkeeping, and the curriculum under TSID's walk"""
+    if args and args[0] == "--trace":
+        n, k = int(args[1]), int(args[2])
+        env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=4, terrain=EP_TERRAIN, curriculum=EP_CURRICULUM, **KW)
+        a = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
+        for _ in range(k):
+            env.step(a)
+        torch.cuda.synchronize()
+        return
+    if args and args[0] == "--curriculum":
+        print(json.dumps(curriculum_run(), indent=1))
+        return
+    out_path = args[0] if args else "profiles/policy_episode.json"
+    report(out_path, terrain=EP_TERRAIN, curriculum=EP_CURRICULUM, runs=[measure_episodes(n, 4) for n in (4096, 512)],
+           curriculum_under_tsid_walk=curriculum_run())
+
+
 def main_normalize(which, args):
     """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
     4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
@@ -758,6 +888,9 @@ def main_normalize(which, args):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--episodes":
+        main_episodes(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--distill":
         main_distill(sys.argv[2:])
         sys.exit(0)

@@ -20,7 +20,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_actor", "tsidb_policy_gae", "tsidb_policy_learn_workspace", "tsidb_policy_learn",
            "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm",
            "tsidb_policy_opt_workspace", "tsidb_policy_opt_step",
-           "tsidb_policy_teacher_mix", "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit"]
+           "tsidb_policy_teacher_mix", "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit",
+           "tsidb_policy_episode_config", "tsidb_policy_episode_end", "tsidb_policy_episode_begin"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -82,6 +83,13 @@ POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fr
 POL_TEACHER_MIX_STREAM = 23
 POL_IMIT_LOSSES = ("mse", "huber")
 POL_IMIT_STATS = ("imitation_loss", "weight_sum", "weighted_rows", "skipped_rows")
+# episode statistics and the terrain curriculum (include/tsidb.h TSIDB_POL_EP_*, TSIDB_POL_EPP_*): the columns of an episode's
+# record, tsidb_policy_episode_config's parameter vector, PolicyCurriculum's fields and the stream of a graduate's level
+POL_EP_COUNT, POL_EP_TIMEOUT, POL_EP_LENGTH, POL_EP_RETURN, POL_EP_DISPLACEMENT, POL_EP_LEVEL, POL_EP_TERMS, POL_EP_TEACH, POL_EP_NREC = \
+    0, 1, 2, 3, 4, 5, 6, 18, 22
+POL_EPP_CURRICULUM, POL_EPP_UP_DISTANCE, POL_EPP_DOWN_FRACTION, POL_EPP_RANDOM_TOP, POL_EPP_NPARAMS = range(5)
+POL_CURRICULUM_FIELDS = ("up_distance", "down_fraction", "random_top")
+POL_CURRICULUM_STREAM = 24
 # the policy normaliser (include/tsidb.h tsidb_policy_norm_update): the rows of a segment of the batch statistics
 POL_NORM_SEG_ROWS = 256
 # the policy optimiser (include/tsidb.h tsidb_policy_opt_step): the elements of a chunk of the gradient norm's sums, the slots
@@ -120,6 +128,12 @@ class PolicyBufs(C.Structure):
     _fields_ = [("act_hist", C.c_void_p), ("last_action", C.c_void_p), ("prev_action", C.c_void_p), ("command", C.c_void_p),
                 ("air_time", C.c_void_p), ("ep_len", C.c_void_p), ("episode", C.c_void_p), ("delay", C.c_void_p),
                 ("terms", C.c_void_p), ("timeout", C.c_void_p), ("obs", C.c_void_p), ("obs_ld", C.c_int)]
+
+
+class PolicyEpisode(C.Structure):
+    """tsidb_policy_episode (include/tsidb.h): the per-env episode state of the statistics and the curriculum"""
+    _fields_ = [("run", C.c_void_p), ("start_xy", C.c_void_p), ("last", C.c_void_p), ("sum", C.c_void_p), ("level", C.c_void_p),
+                ("teacher_terms", C.c_void_p)]
 
 
 class PolicyNet(C.Structure):
@@ -256,6 +270,9 @@ def load(path=None):
     L.tsidb_policy_learn_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_policy_teacher_mix.argtypes = [vp, vp, vp, vp, vp, vp, i32p, vp, C.c_uint64, C.c_uint64, vp]
+    L.tsidb_policy_episode_config.argtypes = [vp, vp, C.c_int]
+    L.tsidb_policy_episode_end.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.tsidb_policy_episode_begin.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
     L.tsidb_policy_learn_imit_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn_imit.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]

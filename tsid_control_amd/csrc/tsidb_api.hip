@@ -733,6 +733,8 @@ struct tsidb_ctx {
   double pol_ter[TSIDB_POL_TER_NPARAMS] = {};
   bool teach_set = false;                    // tsidb_policy_teacher_config: the two sigmas and the teacher terms' weights
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
+  bool ep_set = false;                       // tsidb_policy_episode_config: episode statistics, the terrain curriculum
+  double pol_ep[TSIDB_POL_EPP_NPARAMS] = {};
   bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
   bool learn_imit_big_lds = false;           // tsidb_policy_learn_imit: k_policy_learn_rows_imit's likewise
   bool actor_norm_big_lds = false;           // tsidb_policy_actor_norm: k_policy_actor_norm's likewise
@@ -1258,6 +1260,14 @@ static PolicyTeach policy_teach(const tsidb_ctx *h) {
   return tc;
 }
 
+// what both episode launches need on top of policy_bufs: the configuration and the required buffers
+template <typename T>
+static PolicyEpisode<T> policy_episode(const tsidb_ctx *h, const tsidb_policy_episode *ep, const char *who) {
+  if (!h->ep_set) throw std::string(who) + "not configured (call tsidb_policy_episode_config first)";
+  if (!ep || !ep->run || !ep->start_xy || !ep->last || !ep->sum) throw std::string(who) + "null buffer in tsidb_policy_episode (run, start_xy, last, sum)";
+  return PolicyEpisode<T>{ep->run, ep->start_xy, ep->last, ep->sum, ep->level, (const T *)ep->teacher_terms};
+}
+
 // the controller's rows a launch reads (or, the teacher, writes): `what` says which for the message
 static void need_rows(const char *who, const void *rows, int ld, const char *what = "tsidb_reset_done read (done flag in column TSIDB_NOBS + 1)") {
   if (!rows || ld < NROW) throw std::string(who) + "needs the [N, >= TSIDB_NROW] rows " + what;
@@ -1506,6 +1516,64 @@ int tsidb_policy_teacher_mix(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
     if (seed >= (1ull << 32) || env_offset >= (1ull << 31)) throw std::string(who) + "seed must be below 2^32 and env_offset below 2^31";
     launch(k_policy_teacher_mix<T>, h->num_envs, b, (const T *)teacher_action, (T *)action, label, weight, executed, beta,
            (unsigned long long)seed, (unsigned long long)env_offset);
+  });
+}
+
+int tsidb_policy_episode_config(tsidb_handle h, const double *ep_params, int n_params) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_episode_config: ";
+  if (lacks_sim(h, true, who)) throw h->err;
+  double p[TSIDB_POL_EPP_NPARAMS] = {};
+  const bool on = ep_params || n_params;
+  if (on) {
+    if (!ep_params || n_params != TSIDB_POL_EPP_NPARAMS) throw std::string(who) + "needs TSIDB_POL_EPP_NPARAMS parameters (or NULL, 0: the slice off)";
+    for (int i = 0; i < n_params; i++) {
+      if (!std::isfinite(ep_params[i])) throw std::string(who) + "non-finite parameter";
+      p[i] = ep_params[i];
+    }
+    for (int i : {(int)TSIDB_POL_EPP_CURRICULUM, (int)TSIDB_POL_EPP_RANDOM_TOP})
+      if (p[i] != 0 && p[i] != 1) throw std::string(who) + "curriculum and random_top are flags: 0 or 1";
+    if (p[TSIDB_POL_EPP_CURRICULUM] == 1 && !(p[TSIDB_POL_EPP_UP_DISTANCE] > 0)) throw std::string(who) + "up_distance must be positive with the curriculum on";
+    if (p[TSIDB_POL_EPP_DOWN_FRACTION] < 0) throw std::string(who) + "down_fraction must be >= 0";
+  }
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->pol_ep, p, sizeof h->pol_ep);
+  h->ep_set = on;
+  GUARD_END
+}
+
+int tsidb_policy_episode_end(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *qpos, const void *reward,
+                             const void *done, int row_ld, void *stream) {
+  const char *who = "tsidb_policy_episode_end: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &b, auto launch) {
+    using T = decltype(t);
+    const PolicyEpisode<T> pe = policy_episode<T>(h, ep, who);
+    if (!qpos || !reward || !done || row_ld < 1) throw std::string(who) + "null buffer or row stride < 1";
+    PolicyCur c = {};
+    c.curriculum = h->pol_ep[TSIDB_POL_EPP_CURRICULUM] == 1;
+    c.num_levels = h->ter_set ? (int)h->pol_ter[TSIDB_POL_TER_NUM_LEVELS] : 0;
+    if (c.curriculum) {
+      if (!h->ter_set) throw std::string(who) + "the curriculum needs a terrain (call tsidb_policy_terrain_config first: num_levels, seed and env_offset are its)";
+      if (!(h->pol[TSIDB_POL_P_MAX_EPISODE_STEPS] > 0)) throw std::string(who) + "the curriculum needs max_episode_steps > 0 (the distance a command asks for is over a whole episode)";
+      if (!pe.level) throw std::string(who) + "the curriculum needs the level buffer of tsidb_policy_episode";
+      c.seed = (unsigned long long)h->pol_ter[TSIDB_POL_TER_SEED]; c.env_offset = (unsigned long long)h->pol_ter[TSIDB_POL_TER_ENV_OFFSET];
+      c.up_distance = h->pol_ep[TSIDB_POL_EPP_UP_DISTANCE]; c.down_fraction = h->pol_ep[TSIDB_POL_EPP_DOWN_FRACTION];
+      c.random_top = h->pol_ep[TSIDB_POL_EPP_RANDOM_TOP] == 1;
+      c.t_episode = h->pol[TSIDB_POL_P_MAX_EPISODE_STEPS] * (h->pol[TSIDB_POL_P_DECIMATION] * h->params[P_DT]);
+    }
+    launch(k_policy_episode_end<T>, h->num_envs, b, pe, c, (const T *)qpos, (const T *)reward, (const T *)done, row_ld);
+  });
+}
+
+int tsidb_policy_episode_begin(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *done_rows, int rows_ld,
+                               const void *qpos, void *stream) {
+  const char *who = "tsidb_policy_episode_begin: ";
+  return policy_call(h, bufs, who, stream, [&](auto t, const auto &, auto launch) {
+    using T = decltype(t);
+    const PolicyEpisode<T> pe = policy_episode<T>(h, ep, who);
+    need_rows(who, done_rows, rows_ld);
+    if (!qpos) throw std::string(who) + "null buffer";
+    launch(k_policy_episode_begin<T>, h->num_envs, pe, (const T *)done_rows, rows_ld, (const T *)qpos);
   });
 }
 

@@ -563,4 +563,86 @@ __global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_teacher_mi
   }
 }
 
+// ---------------------------------------------------------------------------- episode statistics, terrain curriculum
+enum { POL_EP_COUNT = 0, POL_EP_TIMEOUT, POL_EP_LENGTH, POL_EP_RETURN, POL_EP_DISPLACEMENT, POL_EP_LEVEL, POL_EP_TERMS,
+       POL_EP_TEACH = POL_EP_TERMS + POL_NT, POL_EP_NREC = POL_EP_TEACH + POL_TEACH_NT };   // TSIDB_POL_EP_*
+constexpr int DR_S_CURRICULUM = 24;   // stream 24 of the key layout: the level of an env that graduates from the top
+
+// tsidb_policy_episode in the path's arithmetic type: the statistics are float64 on either path
+template <typename T>
+struct PolicyEpisode {
+  double *run, *start_xy, *last, *sum;
+  int *level;
+  const T *teacher_terms;
+};
+
+// tsidb_policy_episode_config's values and what the curriculum needs of the two other configurations, passed by value
+struct PolicyCur {
+  unsigned long long seed, env_offset;   // the terrain's
+  double up_distance, down_fraction, t_episode /* max_episode_steps * (decimation * dt) */;
+  int curriculum, random_top, num_levels /* 0: no terrain configured */;
+};
+
+// x where it is finite, else 0: a select, so that a NaN adds nothing (0 * NaN would)
+__device__ __forceinline__ double pol_finite(double x) { return isfinite(x) ? x : 0.0; }
+
+// after k_policy_reward (and k_policy_teacher), before k_reset.  lane = column of the record: every lane adds its column's addend
+// of this step to the running sums; for a done env it then forms its column of the record, stores it to `last` and adds it to
+// `sum`.  The displacement, the level and the curriculum's rule are formed on every lane from wave-uniform values (a hash, a
+// square root); lane 0 stores the new level - after every lane of the wavefront has read the old one.
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_episode_end(int n, PolicyBufs<T> b, PolicyEpisode<T> ep, PolicyCur c,
+                                                                                  const T *__restrict__ qpos, const T *__restrict__ reward,
+                                                                                  const T *__restrict__ done, int row_ld) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= POL_EP_NREC) return;
+  const size_t E = (size_t)e, at = E * POL_EP_NREC + lane;
+  const bool summed = lane == POL_EP_LENGTH || lane == POL_EP_RETURN || lane >= POL_EP_TERMS;
+  double run = 0;
+  if (summed) {
+    double add = 1.0;   // LENGTH
+    if (lane == POL_EP_RETURN) add = (double)reward[E * row_ld];
+    else if (lane >= POL_EP_TEACH) add = ep.teacher_terms ? (double)ep.teacher_terms[E * POL_TEACH_NT + (lane - POL_EP_TEACH)] : 0.0;
+    else if (lane >= POL_EP_TERMS) add = (double)b.terms[E * POL_NT + (lane - POL_EP_TERMS)];
+    run = ep.run[at] + pol_finite(add);
+    ep.run[at] = run;
+  }
+  if (done[E * row_ld] == T(0)) return;
+  const double dx = (double)qpos[E * NQ] - ep.start_xy[E * 2], dy = (double)qpos[E * NQ + 1] - ep.start_xy[E * 2 + 1];
+  const double d = sqrt(dx * dx + dy * dy);
+  int lvl = ep.level ? ep.level[E] : 0;
+  lvl = lvl < 0 ? 0 : c.num_levels > 0 && lvl > c.num_levels - 1 ? c.num_levels - 1 : lvl;
+  const double rec = lane == POL_EP_COUNT ? 1.0 : lane == POL_EP_TIMEOUT ? (b.timeout[E] ? 1.0 : 0.0) : lane == POL_EP_LENGTH ? (double)b.ep_len[E]
+                   : lane == POL_EP_DISPLACEMENT ? d : lane == POL_EP_LEVEL ? (double)lvl : run;
+  ep.last[at] = rec;
+  ep.sum[at] += lane == POL_EP_RETURN || lane == POL_EP_DISPLACEMENT ? pol_finite(rec) : rec;
+  if (c.curriculum) {
+    const double cx = (double)b.command[E * 3], cy = (double)b.command[E * 3 + 1];
+    const bool up = d > c.up_distance, down = !up && d < c.down_fraction * sqrt(cx * cx + cy * cy) * c.t_episode;   // (NaN d: neither)
+    int next = lvl + (up ? 1 : 0) - (down ? 1 : 0);
+    if (next < 0) next = 0;
+    else if (next >= c.num_levels) {
+      next = c.num_levels - 1;
+      if (c.random_top) {
+        const unsigned long long ge = c.env_offset + (unsigned long long)e, epn = (unsigned long long)(b.episode[E] + 1);   // (the episode about to start)
+        const int r = (int)(pol_draw(c.seed, DR_S_CURRICULUM, 0, ge, epn) * (double)c.num_levels);   // floor: the product is >= 0
+        next = r < next ? r : next;
+      }
+    }
+    if (lane == 0) ep.level[E] = next;
+  }
+}
+
+// after k_reset, the reset noise and the terrain's redraw: the first position of the episodes that start, their sums zeroed
+template <typename T>
+__global__ __launch_bounds__(WAVE * POL_ENVS_PER_BLOCK) void k_policy_episode_begin(int n, PolicyEpisode<T> ep, const T *__restrict__ done_rows, int rows_ld,
+                                                                                    const T *__restrict__ qpos) {
+  const int e = pol_env(n), lane = threadIdx.x & 63;
+  if (e < 0 || lane >= POL_EP_NREC) return;
+  const size_t E = (size_t)e;
+  if (done_rows[E * rows_ld + NROW - 1] == T(0)) return;
+  ep.run[E * POL_EP_NREC + lane] = 0;
+  if (lane < 2) ep.start_xy[E * 2 + lane] = (double)qpos[E * NQ + lane];
+}
+
 } // namespace tsidb

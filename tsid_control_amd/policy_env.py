@@ -28,6 +28,11 @@ mode = "residual" adds the policy's torque to TSID's tau; "position" / "motor" l
 In those two modes the teacher can be learned from: rollout() into a RolloutStorage(teacher=True) records TSID's action as the
 label of every stored row and, with teacher_beta, executes it in place of the policy's for that share of the episodes (DAgger's
 mixing; one more launch per step, tsidb_policy_teacher_mix), and PolicyLearner(imitation_coef=...) has the term for the labels.
+
+With episode_stats = True or a PolicyCurriculum two more launches join the step: right before the reset the running sums of the
+episode, the record of every episode that ends and - with the curriculum - the terrain level of the env's next episode
+(tsidb_policy_episode_end), behind the reset, its noise and the terrain's redraw the first position of the episodes that start
+(tsidb_policy_episode_begin).  episode_stats() turns the per-env sums into what a training loop logs, without a host read.
 """
 import copy
 import ctypes as C
@@ -233,6 +238,42 @@ class PolicyTerrain:
         return p
 
 
+@dataclasses.dataclass
+class PolicyCurriculum:
+    """The terrain curriculum of a PolicyEnv (include/tsidb.h tsidb_policy_episode_end, TSIDB_POL_EPP_*): legged_gym's rule on
+    PolicyEnv.terrain_level, applied on the device to every env whose episode ends.  With d the distance of the base from where
+    the episode started: d > up_distance [m] moves the env one level up; otherwise d < down_fraction x the distance its command
+    asked for over a whole episode (|command_xy| max_episode_steps decimation dt) moves it one level down.  A level below 0
+    stays 0; an env that graduates from the top level gets a uniformly drawn level (random_top) or stays at the top."""
+    up_distance: float
+    down_fraction: float = 0.5
+    random_top: bool = True
+
+    @classmethod
+    def of(cls, c):
+        """c as a PolicyCurriculum: one, or a dict of its fields"""
+        return _of(cls, c, "curriculum", _lib.POL_CURRICULUM_FIELDS)
+
+    def params(self):
+        """the float64 vector tsidb_policy_episode_config takes (the curriculum on), checked as the library checks it"""
+        bad = lambda msg: _lib.TsidbError("PolicyCurriculum: " + msg)
+        if not isinstance(self.random_top, (bool, np.bool_)) and self.random_top not in (0, 1):
+            raise bad(f"random_top must be True or False, got {self.random_top!r}")
+        p = np.zeros(_lib.POL_EPP_NPARAMS)
+        try:
+            p[_lib.POL_EPP_UP_DISTANCE], p[_lib.POL_EPP_DOWN_FRACTION] = float(self.up_distance), float(self.down_fraction)
+        except (TypeError, ValueError) as err:
+            raise bad(f"up_distance = {self.up_distance!r}, down_fraction = {self.down_fraction!r}: not numbers") from err
+        p[_lib.POL_EPP_CURRICULUM], p[_lib.POL_EPP_RANDOM_TOP] = 1.0, float(bool(self.random_top))
+        if not np.isfinite(p).all():
+            raise bad("non-finite value")
+        if not p[_lib.POL_EPP_UP_DISTANCE] > 0:
+            raise bad("up_distance must be positive")
+        if p[_lib.POL_EPP_DOWN_FRACTION] < 0:
+            raise bad("down_fraction must be >= 0")
+        return p
+
+
 class PolicyEnv:
     """conf: a RobotConfig (used as a copy with reference_quirks = False, sim_enabled = True: a reset then writes a proper wxyz
     qpos).  decimation: sim steps per policy step.  mode: "position" (ctrl = joint targets [rad] = default_joint_pos +
@@ -270,9 +311,18 @@ class PolicyEnv:
     without the argument).  The env registers nominal tables once (wc.set_env_params(mass_scale=1, terrain="flat")) and the
     kernels rewrite wc.env_params [N, 8] and wc.terrain [N, 20] in place, for the envs a step or reset() restarts.  terrain_level
     [N] int32, zero at first, is the caller's to write: the level of the env's NEXT episodes (the hook of a terrain curriculum;
-    no promotion rule is built in).  height_scan [N, nx * ny]: point ix * ny + iy.  All three are in step()'s info (env_params
+    curriculum= below writes it on the device, otherwise no promotion rule runs).  height_scan [N, nx * ny]: point ix * ny + iy.  All three are in step()'s info (env_params
     under that name).  Accepted with tsid = "stand" / "walk", but the controller is NOT told about the floor: its references,
-    contact frames and plan assume the level floor z = 0, so a tilt or steps are a disturbance TSID has to absorb."""
+    contact frames and plan assume the level floor z = 0, so a tilt or steps are a disturbance TSID has to absorb.
+
+    episode_stats = True: two more launches per step keep what a training loop logs (include/tsidb.h tsidb_policy_episode_end
+    before the reset, _begin behind it): episode_last [N, NREC] float64, the record of each env's most recently finished
+    episode (columns _lib.POL_EP_*: count, timeout, length, return, displacement, level, the 12 term sums, the 4 teacher term
+    sums), and episode_sum [N, NREC], the per-env sums of the records since episode_stats() last cleared them; both in step()'s
+    info.  episode_run [N, NREC] and episode_start_xy [N, 2] are the running episode's state.  reset() starts the episodes it
+    forces and records nothing for the ones it abandons.  curriculum: a PolicyCurriculum or a dict of its fields (None =
+    none); implies episode_stats, needs terrain= and max_episode_steps > 0: the same launch then writes terrain_level, the level
+    of each done env's next episode, before the terrain's redraw reads it."""
 
     # the randomisation's launches a step makes; class-level so that an instance built without __init__ steps unrandomised
     randomization = None
@@ -283,11 +333,14 @@ class PolicyEnv:
     tsid = sched = clock = None
     # the [1] float32 device tensor behind rollout(teacher_beta = a float), made at the first such call
     _teacher_beta = None
+    # episode statistics and the terrain curriculum: _episode = the tsidb_policy_episode block, None = the slice is off
+    curriculum = _episode = episode_run = episode_start_xy = episode_last = episode_sum = None
 
     def __init__(self, conf=None, num_envs=None, device=None, decimation=10, mode="position", action_scale=0.25,
                  default_joint_pos=None, action_clip=100.0, delay=None, filter_alpha=1.0, command_range=((0.0, 0.0),) * 3,
                  max_episode_steps=0, reward_weights=None, term_bodies=None, sigma=0.25, h_target=None, t_air=0.25, deadband=0.1,
-                 seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05, terrain=None):
+                 seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05, terrain=None,
+                 episode_stats=False, curriculum=None):
         from .conf import RobotConfig
         conf = copy.copy(conf) if conf is not None else RobotConfig()
         conf.reference_quirks = False
@@ -300,13 +353,21 @@ class PolicyEnv:
         # the four parameter vectors: checked before anything is built
         self.params = base = self._base_params(int(decimation), action_clip, filter_alpha, sigma, t_air, deadband, max_episode_steps, seed,
                                                command_range, reward_weights)
-        dr = ter = teach = None
+        dr = ter = teach = epp = None
         if randomization is not None:
             self.randomization = PolicyRandomization.of(randomization)
             dr = self.randomization.params(seed)
         if terrain is not None:
             self.terrain = PolicyTerrain.of(terrain)
             ter = self.terrain.params(seed, 0 if dr is None else int(dr[_lib.POL_DR_ENV_OFFSET]))
+        if curriculum is not None:
+            self.curriculum = PolicyCurriculum.of(curriculum)
+            epp = self.curriculum.params()
+            if ter is None or not base[_lib.POL_P_MAX_EPISODE_STEPS] > 0:
+                raise _lib.TsidbError("PolicyEnv: a curriculum needs terrain= (the levels are the terrain's) and max_episode_steps > 0 "
+                                      "(the distance a command asks for is over a whole episode)")
+        elif episode_stats:
+            epp = np.zeros(_lib.POL_EPP_NPARAMS)
         if tsid is None:
             if walk is not None or teacher_weights:
                 raise _lib.TsidbError("PolicyEnv: walk and teacher_weights need tsid = 'stand' or 'walk'")
@@ -377,6 +438,15 @@ class PolicyEnv:
             wc._call("tsidb_policy_teacher_config", *vec(teach))
             if tsid == "walk":
                 self._build_schedule(dict(walk or {}))
+        if epp is not None:
+            self.ep_params = epp
+            d = lambda *s: torch.zeros(*s, dtype=torch.float64, device=wc.device)   # float64 whatever the path's dtype
+            self.episode_run, self.episode_start_xy = d(N, _lib.POL_EP_NREC), d(N, 2)
+            self.episode_last, self.episode_sum = d(N, _lib.POL_EP_NREC), d(N, _lib.POL_EP_NREC)
+            self._episode = _lib.PolicyEpisode(*(t.data_ptr() if t is not None else None for t in (
+                self.episode_run, self.episode_start_xy, self.episode_last, self.episode_sum, self.terrain_level,
+                self.teacher_terms if tsid is not None else None)))
+            wc._call("tsidb_policy_episode_config", *vec(epp))
         self.reset()   # (episode 1 starts)
 
     @staticmethod
@@ -433,6 +503,10 @@ class PolicyEnv:
         if self.sched is not None:
             s = self.sched
             yield from (self.clock, s.td_latch, s.coef, s.rest, s.com, s.side, s.nsteps, s.steps, s.flags, s.episode, s.t_offset)
+        if self._episode is not None:
+            yield from (self.episode_run, self.episode_start_xy, self.episode_last, self.episode_sum)
+            if self.curriculum is not None:
+                yield self.terrain_level
 
     def _act(self, action):
         self.wc._call("tsidb_policy_act", C.byref(self._bufs), _ptr(action), self.wc._stream())
@@ -498,6 +572,38 @@ class PolicyEnv:
                       _ptr(label), _ptr(weight), _ptr(executed), _ptr(beta), C.c_uint64(actor.seed),
                       C.c_uint64(actor.env_offset), self.wc._stream())
 
+    def _episode_end(self):
+        wc = self.wc
+        wc._call("tsidb_policy_episode_end", C.byref(self._bufs), C.byref(self._episode), _ptr(wc.qpos), _ptr(wc.reward), _ptr(wc.done),
+                 wc.NROW, wc._stream())
+
+    def _episode_begin(self):
+        wc = self.wc
+        wc._call("tsidb_policy_episode_begin", C.byref(self._bufs), C.byref(self._episode), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos),
+                 wc._stream())
+
+    def episode_stats(self, clear=True):
+        """What the episodes that finished since the last clear amount to, as 0-dim float64 device tensors (no host read):
+        episodes and timeouts (counts), then means over the finished episodes (divisor max(episodes, 1)): length [policy steps],
+        return, displacement [m], level, rew_<term> for the twelve reward terms (unweighted episode sums) and, with tsid,
+        teacher_<term>.  One torch.sum over episode_sum; clear: episode_sum is then zeroed, in stream order."""
+        if self._episode is None:
+            raise _lib.TsidbError("PolicyEnv.episode_stats: the env was built without episode_stats = True or a curriculum")
+        s = self.episode_sum.sum(0)
+        div = s[_lib.POL_EP_COUNT].clamp(min=1.0)
+        out = dict(episodes=s[_lib.POL_EP_COUNT], timeouts=s[_lib.POL_EP_TIMEOUT])
+        for k, i in (("length", _lib.POL_EP_LENGTH), ("return", _lib.POL_EP_RETURN), ("displacement", _lib.POL_EP_DISPLACEMENT),
+                     ("level", _lib.POL_EP_LEVEL)):
+            out[k] = s[i] / div
+        for j, k in enumerate(_lib.POL_TERMS):
+            out["rew_" + k] = s[_lib.POL_EP_TERMS + j] / div
+        if self.tsid is not None:
+            for j, k in enumerate(_lib.POL_TEACH_TERMS):
+                out["teacher_" + k] = s[_lib.POL_EP_TEACH + j] / div
+        if clear:
+            self.episode_sum.zero_()
+        return out
+
     def _beta_tensor(self, teacher_beta):
         """teacher_beta as the [1] float32 device tensor the launch reads, or None"""
         wc = self.wc
@@ -524,6 +630,8 @@ class PolicyEnv:
             self._reset_noise()
         if self.terrain is not None:
             self._terrain_reset()
+        if self._episode is not None:
+            self._episode_begin()
         self._obs()
         if self.terrain is not None:
             self._height_scan()
@@ -558,7 +666,8 @@ class PolicyEnv:
         done and terms belong to the step that ended the old one.  With pushes on, info["push"] [N, 3] is the torso force the
         step applied (0 for an env it restarted: the reset clears the wrenches).  With tsid set, info also holds teacher_terms
         [N, 4] (unweighted; already in reward with teacher_weights), teacher_action [N, NA] and teacher_obs [N, 14 + NA].  With
-        terrain set, height_scan [N, nx * ny], env_params [N, 8] (the sim's table, as the restarts left it) and terrain_level."""
+        terrain set, height_scan [N, nx * ny], env_params [N, 8] (the sim's table, as the restarts left it) and terrain_level.
+        With episode_stats or a curriculum, episode_last and episode_sum [N, NREC] float64 (see the class)."""
         wc = self.wc
         if action is None:
             raise _lib.TsidbError("PolicyEnv.step: action is None")
@@ -573,9 +682,13 @@ class PolicyEnv:
             self._tsid_steps()
             self._reward()
             self._teacher()
+        if self._episode is not None:
+            self._episode_end()
         wc.reset_done()
         self._after_reset_done()
         info = dict(timeout=self.timeout, terms=self.terms, episode_length=self.ep_len)
+        if self._episode is not None:
+            info.update(episode_last=self.episode_last, episode_sum=self.episode_sum)
         if self.terrain is not None:
             info.update(height_scan=self.height_scan, env_params=wc.env_params, terrain_level=self.terrain_level)
         if self.tsid is not None:
