@@ -714,6 +714,44 @@ int tsidb_policy_episode_end(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
 int tsidb_policy_episode_begin(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *done_rows,
                                int rows_ld, const void *qpos, void *stream);
 
+/* ---- observation history: the last `frames` observations of every env stacked into one row, what a feed-forward actor is given
+ * in place of a memory (Isaac Lab's history_length, the frame stacks of legged_gym and humanoid-gym).  One launch per policy step,
+ * behind the kernels that write the observation tensors; nothing else reads or writes the history.
+ *
+ * A frame is the concatenation of 1 .. TSIDB_POL_OBSH_MAXSRC column blocks of the caller's tensors, src[i][e * src_ld[i] + c] for
+ * c < src_cols[i], in the path's type and in the order given (any [N, k] view with a row stride: obs or priv inside their row, a
+ * column range of either, command, the height scan, the teacher's observation; the same tensor may be named twice); K = the sum
+ * of src_cols.  history [N, frames * K] in the path's type is frame-major, oldest frame first: frame f of env e is
+ * history[e * frames * K + f * K + k], k < K, and the newest frame, f = frames - 1, is the row an actor without a history
+ * would see.  frames * K <= TSIDB_POL_OBSH_MAXCOLS.  Frames are copies: what the observation kernels left in the sources,
+ * observation noise included, bit for bit. */
+enum { TSIDB_POL_OBSH_MAXSRC = 4, TSIDB_POL_OBSH_MAXFRAMES = 32, TSIDB_POL_OBSH_MAXCOLS = 4096 };
+
+/* device buffers owned by the caller.  THE SOURCES AND history MUST NOT OVERLAP: the library cannot check it.  The struct shares
+ * its name with the entry point, as stat does: it has no typedef and is always written `struct tsidb_policy_obs_history`. */
+struct tsidb_policy_obs_history {
+  void *history;                             /* [N, frames * K] */
+  int frames;                                /* 1 .. TSIDB_POL_OBSH_MAXFRAMES */
+  int n_src;                                 /* 1 .. TSIDB_POL_OBSH_MAXSRC */
+  const void *src[TSIDB_POL_OBSH_MAXSRC];    /* first column of each block, env 0 */
+  int src_ld[TSIDB_POL_OBSH_MAXSRC];         /* row stride in elements, >= src_cols */
+  int src_cols[TSIDB_POL_OBSH_MAXSRC];       /* columns of each block, >= 1 */
+};
+
+/* after tsidb_reset_done(done_rows, ...) and the launches that write the sources (tsidb_policy_obs, tsidb_policy_height_scan,
+ * tsidb_policy_teacher_obs).  With x[e] the current frame of env e:
+ *   done flag set (column TSIDB_NOBS + 1 of done_rows [N, rows_ld >= TSIDB_NROW]): every one of the `frames` frames = x[e] -
+ *     the first observation of an episode carries nothing of the one that ended;
+ *   otherwise, push = 1 (a policy step): frame[f] = frame[f + 1] for f < frames - 1, frame[frames - 1] = x[e];
+ *   otherwise, push = 0 (a reset of other envs, which recomputes the observations but is no new time step): untouched, bit for bit.
+ * So the newest frame always equals the current selection.  The shift is in place; the struct is copied into the launch and the
+ * handle keeps nothing of it.  A plain asynchronous launch in the policy kernels' shape: no atomics, no host read, no
+ * allocation, capturable.  Fails (message via tsidb_last_error) on a NULL struct, history or source, frames or n_src out of
+ * range, src_cols < 1, src_ld < src_cols, frames * K > TSIDB_POL_OBSH_MAXCOLS, done_rows NULL or rows_ld < TSIDB_NROW, and a
+ * push other than 0 / 1. */
+int tsidb_policy_obs_history(tsidb_handle h, const struct tsidb_policy_obs_history *hist, const void *done_rows, int rows_ld,
+                             int push, void *stream);
+
 /* ---- the policy's side of a rollout: a dense actor and an optional critic evaluated on the env's own rows, the Gaussian sample
  * with its log-probability, and the advantages of a recorded rollout.  Both calls are plain asynchronous launches on the given
  * stream: no allocation, no host synchronisation, no state of their own - T policy steps with their actor calls can be captured

@@ -66,7 +66,13 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               decimation 4; then the curriculum under TSID's own walk (tsid="walk", zero residual, eight levels of steps up to 4 cm, strips of 3 - 6 cm):
               the level histogram per iteration and the share of each level's episodes that went up; default
               profiles/policy_episode.json.  --episodes --curriculum: that second part alone.  Kernel times: rocprofv3 --kernel-trace
-              --stats -- python tools/policy_env.py --episodes --trace ENVS STEPS"""
+              --stats -- python tools/policy_env.py --episodes --trace ENVS STEPS
+    python tools/policy_env.py --history H [out.json]   the observation history (PolicyEnv(obs_history=dict(frames=H, sources=("obs",))):
+              one launch per step) against the env without it and against the same stack with torch ops behind every step
+              (TorchHistory below: cat, where on done, repeat), in alternating windows, at 4096 and 512 envs, decimation 4; whether
+              the two stacks end bit-identical; then eager 16-step rollouts of an actor on the stacked row against the same actor
+              on obs alone (H x 71 <= 512); default profiles/policy_obs_history.json.  Kernel time: rocprofv3 --kernel-trace
+              --stats -- python tools/policy_env.py --history H --trace ENVS STEPS (which prints the bytes a launch moves)"""
 import json
 import sys
 import time
@@ -850,6 +856,83 @@ def main_episodes(args):
            curriculum_under_tsid_walk=curriculum_run())
 
 
+class TorchHistory:
+    """the observation history with torch ops behind every step: a cat, a where on done, a repeat for the restarted envs"""
+
+    def __init__(self, env, frames):
+        self.env, self.frames = env, frames
+        self.hist = env.obs.repeat(1, frames)
+
+    def step(self, action):
+        obs, _, done, _ = self.env.step(action)
+        pushed = torch.cat([self.hist[:, obs.shape[1]:], obs], 1)
+        self.hist = torch.where((done != 0)[:, None], obs.repeat(1, self.frames), pushed)
+
+
+def history_bytes(n, K, frames, item=8):
+    """what one tsidb_policy_obs_history launch moves when no env restarts: frames - 1 frames read and written, the current
+    selection read, the newest frame written"""
+    return n * K * item * (2 * (frames - 1) + 2)
+
+
+def measure_history(n, frames, decimation=4, window=300, windows=4, preroll=60, rollout_steps=16):
+    """off: PolicyEnv; on: the same with obs_history on obs; torch: `off` with TorchHistory behind every step.  Policy-steps/s in
+    alternating windows of one process; then rollouts of an actor that reads the stacked row"""
+    from tsid_control_amd import PolicyActor
+    delay = delays(n)
+    make = lambda **kw: PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=decimation, delay=delay, **kw, **KW)
+    envs = dict(off=make(), on=make(obs_history=dict(frames=frames, sources=("obs",))), torch=make())
+    book = TorchHistory(envs["torch"], frames)
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    actions = [(torch.rand(n, envs["on"].NA, generator=g, dtype=torch.float64, device="cuda:0") - 0.5) * 0.2 for _ in range(16)]
+    run = {k: stepper(envs[k], n, envs[k].NA) for k in ("off", "on")}
+    run["torch"] = lambda k: [book.step(actions[i & 15]) for i in range(k)]
+    r = alternate(run, window, windows, preroll)
+    med, us = r["policy_steps_per_s_median"], r["us_per_policy_step"]
+    K = envs["on"].NOBS
+    out = dict(envs=n, decimation=decimation, frames=frames, K=K, window_policy_steps=window, windows=windows, **r,
+               on_over_off=med["on"] / med["off"], torch_over_off=med["torch"] / med["off"], history_us_per_policy_step=us["on"] - us["off"],
+               torch_us_per_policy_step=us["torch"] - us["off"], torch_cost_over_fused_cost=(us["torch"] - us["off"]) / max(us["on"] - us["off"], 1e-9),
+               torch_history_equals_fused=bool(torch.equal(book.hist, envs["on"].obs_history)),   # (the same actions, the same number of steps)
+               bytes_per_launch_without_restarts=history_bytes(n, K, frames), restarts={k: int(e.episode.sum()) - n for k, e in envs.items()})
+    env = envs["on"]
+    if frames * K > _lib.POL_NET_MAXWIDTH:
+        out["actor_rollout"] = f"not run: frames * K = {frames * K} columns exceed the actor's {_lib.POL_NET_MAXWIDTH}"
+        return out
+    torch.manual_seed(1)
+    mlp = lambda k, last: torch.nn.Sequential(torch.nn.Linear(k, 256), torch.nn.ELU(), torch.nn.Linear(256, 128), torch.nn.ELU(),
+                                              torch.nn.Linear(128, last)).to("cuda:0")
+    both = {}
+    for name, e, inputs in (("obs", envs["off"], ("obs",)), ("obs_history", env, ("obs_history",))):
+        k_in = e.NOBS if name == "obs" else frames * K
+        with torch.no_grad():
+            actor = mlp(k_in, e.NA)
+            actor[-1].weight.mul_(0.05)                       # (small actions: the robots keep standing)
+        pa = PolicyActor(e, actor, mlp(e.NOBS + 4, 1), actor_inputs=inputs, critic_inputs=("obs", "priv"),
+                         log_std=torch.full((e.NA,), -3.0, device="cuda:0"))
+        st = e.rollout(pa, rollout_steps)
+        both[name] = (lambda e, pa, st: lambda k: [e.rollout(pa, rollout_steps, st) for _ in range(k)])(e, pa, st)
+    rr = alternate(both, 10, windows, 3, per_call=rollout_steps)
+    out["actor_rollout"] = dict(actor=f"{frames * K} -> 256 -> 128 -> NA against {K} -> 256 -> 128 -> NA, ELU; eager {rollout_steps}-step rollouts", **rr)
+    return out
+
+
+def main_history(args):
+    """--history H: the cost of the history against off and against the torch stack, and an actor rollout on the stacked row"""
+    frames, args = int(args[0]), args[1:]
+    if args and args[0] == "--trace":
+        n, k = int(args[1]), int(args[2])
+        env = PolicyEnv(RobotConfig(), num_envs=n, device="cuda:0", decimation=4, obs_history=dict(frames=frames, sources=("obs",)), **KW)
+        a = torch.zeros(n, env.NA, dtype=env.dtype, device=env.device)
+        for _ in range(k):
+            env.step(a)
+        torch.cuda.synchronize()
+        print(json.dumps(dict(envs=n, steps=k, frames=frames, K=env.NOBS, bytes_per_launch_without_restarts=history_bytes(n, env.NOBS, frames))))
+        return
+    out_path = args[0] if args else "profiles/policy_obs_history.json"
+    report(out_path, obs_history=dict(frames=frames, sources=["obs"]), runs=[measure_history(n, frames) for n in (4096, 512)])
+
+
 def main_normalize(which, args):
     """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
     4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
@@ -888,6 +971,9 @@ def main_normalize(which, args):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--history":
+        main_history(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--episodes":
         main_episodes(sys.argv[2:])
         sys.exit(0)

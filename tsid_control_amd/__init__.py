@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("WalkPlanner", "WalkSchedule", "op3_walking_conf", "op3_walking_posture", "op3_closed_loop_walking_conf"):
         from . import walk_planner
         return getattr(walk_planner, name)
-    if name in ("PolicyEnv", "PolicyRandomization", "PolicyTerrain", "PolicyCurriculum"):
+    if name in ("PolicyEnv", "PolicyRandomization", "PolicyTerrain", "PolicyCurriculum", "PolicyObsHistory"):
         from . import policy_env
         return getattr(policy_env, name)
     if name in ("PolicyActor", "RolloutStorage", "rollout_written"):

@@ -21,7 +21,8 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_norm_workspace", "tsidb_policy_norm_update", "tsidb_policy_actor_norm",
            "tsidb_policy_opt_workspace", "tsidb_policy_opt_step",
            "tsidb_policy_teacher_mix", "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit",
-           "tsidb_policy_episode_config", "tsidb_policy_episode_end", "tsidb_policy_episode_begin"]
+           "tsidb_policy_episode_config", "tsidb_policy_episode_end", "tsidb_policy_episode_begin",
+           "tsidb_policy_obs_history"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -90,6 +91,11 @@ POL_EP_COUNT, POL_EP_TIMEOUT, POL_EP_LENGTH, POL_EP_RETURN, POL_EP_DISPLACEMENT,
 POL_EPP_CURRICULUM, POL_EPP_UP_DISTANCE, POL_EPP_DOWN_FRACTION, POL_EPP_RANDOM_TOP, POL_EPP_NPARAMS = range(5)
 POL_CURRICULUM_FIELDS = ("up_distance", "down_fraction", "random_top")
 POL_CURRICULUM_STREAM = 24
+# the observation history (include/tsidb.h tsidb_policy_obs_history, TSIDB_POL_OBSH_*): the most sources of a frame, frames and
+# columns of a history row, the tensors of a PolicyEnv a source may name, and PolicyObsHistory's fields
+POL_OBSH_MAXSRC, POL_OBSH_MAXFRAMES, POL_OBSH_MAXCOLS = 4, 32, 4096
+POL_OBSH_SOURCES = ("obs", "priv", "command", "height_scan", "teacher_obs")
+POL_OBSH_FIELDS = ("frames", "sources")
 # the policy normaliser (include/tsidb.h tsidb_policy_norm_update): the rows of a segment of the batch statistics
 POL_NORM_SEG_ROWS = 256
 # the policy optimiser (include/tsidb.h tsidb_policy_opt_step): the elements of a chunk of the gradient norm's sums, the slots
@@ -134,6 +140,12 @@ class PolicyEpisode(C.Structure):
     """tsidb_policy_episode (include/tsidb.h): the per-env episode state of the statistics and the curriculum"""
     _fields_ = [("run", C.c_void_p), ("start_xy", C.c_void_p), ("last", C.c_void_p), ("sum", C.c_void_p), ("level", C.c_void_p),
                 ("teacher_terms", C.c_void_p)]
+
+
+class PolicyObsHistory(C.Structure):
+    """tsidb_policy_obs_history (include/tsidb.h): the history rows and the column blocks a frame is made of"""
+    _fields_ = [("history", C.c_void_p), ("frames", C.c_int), ("n_src", C.c_int), ("src", C.c_void_p * 4), ("src_ld", C.c_int * 4),
+                ("src_cols", C.c_int * 4)]
 
 
 class PolicyNet(C.Structure):
@@ -273,6 +285,7 @@ def load(path=None):
     L.tsidb_policy_episode_config.argtypes = [vp, vp, C.c_int]
     L.tsidb_policy_episode_end.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.tsidb_policy_episode_begin.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp]
+    L.tsidb_policy_obs_history.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     L.tsidb_policy_learn_imit_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn_imit.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]

@@ -4,6 +4,7 @@
 #include "tsidb_sim.hpp"
 #include "tsidb_tick.hpp"
 #include "tsidb_policy.hpp"
+#include "tsidb_history.hpp"
 #include "tsidb_actor.hpp"
 #include "tsidb_learner.hpp"
 #include "tsidb_norm.hpp"
@@ -1575,6 +1576,39 @@ int tsidb_policy_episode_begin(tsidb_handle h, const tsidb_policy_bufs *bufs, co
     if (!qpos) throw std::string(who) + "null buffer";
     launch(k_policy_episode_begin<T>, h->num_envs, pe, (const T *)done_rows, rows_ld, (const T *)qpos);
   });
+}
+
+// (no tsidb_policy_bufs: the sources are whatever the caller names, so the frame is the guard's, not policy_call's)
+int tsidb_policy_obs_history(tsidb_handle h, const struct tsidb_policy_obs_history *hist, const void *done_rows, int rows_ld, int push,
+                             void *stream) {
+  GUARD_BEGIN
+  const char *who = "tsidb_policy_obs_history: ";
+  static_assert(TSIDB_POL_OBSH_MAXSRC == POL_OBSH_MAXSRC && TSIDB_POL_OBSH_MAXFRAMES == POL_OBSH_MAXFRAMES && TSIDB_POL_OBSH_MAXCOLS == POL_OBSH_MAXCOLS);
+  if (!hist || !hist->history) throw std::string(who) + "null struct tsidb_policy_obs_history or history buffer";
+  if (hist->frames < 1 || hist->frames > POL_OBSH_MAXFRAMES) throw std::string(who) + "frames must be 1 .. TSIDB_POL_OBSH_MAXFRAMES";
+  if (hist->n_src < 1 || hist->n_src > POL_OBSH_MAXSRC) throw std::string(who) + "n_src must be 1 .. TSIDB_POL_OBSH_MAXSRC";
+  int K = 0;
+  for (int s = 0; s < hist->n_src; s++) {
+    if (!hist->src[s]) throw std::string(who) + "null source";
+    if (hist->src_cols[s] < 1 || hist->src_cols[s] > POL_OBSH_MAXCOLS || hist->src_ld[s] < hist->src_cols[s])
+      throw std::string(who) + "a source needs src_cols >= 1 and src_ld >= src_cols";
+    K += hist->src_cols[s];
+  }
+  if (hist->frames * K > POL_OBSH_MAXCOLS) throw std::string(who) + "frames * K exceeds TSIDB_POL_OBSH_MAXCOLS";
+  need_rows(who, done_rows, rows_ld);
+  if (push != 0 && push != 1) throw std::string(who) + "push is a flag: 0 or 1";
+  hipStream_t s = (hipStream_t)stream;
+  with_dtype(h->dtype, [&](auto t) {
+    using T = decltype(t);
+    PolicyObsHistory<T> a = {};
+    a.history = (T *)hist->history; a.frames = hist->frames; a.n_src = hist->n_src; a.K = K;
+    for (int i = 0; i < hist->n_src; i++) { a.src[i] = (const T *)hist->src[i]; a.src_ld[i] = hist->src_ld[i]; a.src_cols[i] = hist->src_cols[i]; }
+    h->note_stream(s);
+    hipLaunchKernelGGL(k_policy_obs_history<T>, dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s,
+                       h->num_envs, a, (const T *)done_rows, rows_ld, push);
+  });
+  HIP_OK(hipGetLastError());
+  GUARD_END
 }
 
 } // extern "C"

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .policy_env import _whole_below
 
-_INPUT_NAMES = ("obs", "priv", "height_scan", "teacher_obs", "command")
+_INPUT_NAMES = ("obs", "priv", "height_scan", "teacher_obs", "command", "obs_history")
 
 
 def _bad(msg):
@@ -77,7 +77,8 @@ class _Net:
                     raise _bad(f"{name}_inputs: unknown input {b!r} (known: {_INPUT_NAMES}, or an [N, k] tensor)")
                 t = getattr(env, b, None)
                 if t is None:
-                    raise _bad(f"{name}_inputs: the env has no {b} (height_scan needs terrain with a scan, teacher_obs needs tsid)")
+                    raise _bad(f"{name}_inputs: the env has no {b} (height_scan needs terrain with a scan, teacher_obs needs tsid, "
+                               "obs_history needs obs_history=)")
             else:
                 t = b
             if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != env.num_envs or t.shape[1] < 1 or t.dtype != wc.dtype \
@@ -121,8 +122,9 @@ class PolicyActor:
     with one activation type (ELU, Tanh or ReLU) between them, or a list of (weight, bias) pairs with activation = "elu" / "tanh" /
     "relu"; 1 .. 4 layers of at most 512 outputs, the actor's last width NA, the critic's 1; float32, contiguous, on the env's
     device; the tensors are kept and read in place at every launch.  actor_inputs, critic_inputs (None = the actor's): the column
-    blocks of the input row, up to 4 and 512 columns in total - "obs", "priv", "height_scan", "teacher_obs", "command", or any
-    [N, k] tensor of the env's dtype (a strided row view is fine).  log_std: [NA] float32, read in place (None = zeros, kept as
+    blocks of the input row, up to 4 and 512 columns in total - "obs", "priv", "height_scan", "teacher_obs", "command", "obs_history"
+    (the stacked frames of an env built with obs_history=, which the env keeps current inside step(): frames * K columns count
+    against the 512), or any [N, k] tensor of the env's dtype (a strided row view is fine).  log_std: [NA] float32, read in place (None = zeros, kept as
     self.log_std).  seed: of the action noise (None = the env's seed); env_offset (None = the randomisation's, else 0).
     normalizer: a PolicyNormalizer (policy_normalizer.py) - running mean and variance of each network's input row, applied as
     the launch loads the row; actor_input / critic_input then hold the normalised rows.  None = the raw rows, as ever.

@@ -33,6 +33,9 @@ With episode_stats = True or a PolicyCurriculum two more launches join the step:
 episode, the record of every episode that ends and - with the curriculum - the terrain level of the env's next episode
 (tsidb_policy_episode_end), behind the reset, its noise and the terrain's redraw the first position of the episodes that start
 (tsidb_policy_episode_begin).  episode_stats() turns the per-env sums into what a training loop logs, without a host read.
+
+With a PolicyObsHistory one more launch closes the step (tsidb_policy_obs_history; csrc/tsidb_history.hpp): the observation it
+just wrote becomes the newest of the last `frames` frames in obs_history, the stacked row a feed-forward actor reads as a memory.
 """
 import copy
 import ctypes as C
@@ -274,6 +277,50 @@ class PolicyCurriculum:
         return p
 
 
+@dataclasses.dataclass
+class PolicyObsHistory:
+    """The observation history of a PolicyEnv (include/tsidb.h tsidb_policy_obs_history): PolicyEnv.obs_history [N, frames * K],
+    the last `frames` observations of every env, frame-major, oldest first.  frames: 1 .. 32.  sources: 1 .. 4 entries, each the
+    name of one of the env's tensors - "obs", "priv", "command", "height_scan", "teacher_obs" - or (name, lo, hi), its columns
+    lo .. hi - 1; a frame is their concatenation in the order given, K columns, and the same name may come twice with different
+    ranges.  frames * K may be up to 4096; a PolicyActor's input row holds 512 columns."""
+    frames: int
+    sources: object = ("obs",)
+
+    @classmethod
+    def of(cls, h):
+        """h as a PolicyObsHistory: one, or a dict of its fields"""
+        return _of(cls, h, "obs_history", _lib.POL_OBSH_FIELDS)
+
+    def resolve(self, columns):
+        """[(name, lo, hi)] of the sources, checked as the library checks them; columns: {name: the columns of the env's tensor,
+        or a str saying why the env has none}.  K is the sum of hi - lo."""
+        bad = lambda msg: _lib.TsidbError("PolicyObsHistory: " + msg)
+        f = self.frames
+        if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)) or f != math.floor(f) \
+                or not 1 <= f <= _lib.POL_OBSH_MAXFRAMES:
+            raise bad(f"frames must be a whole number in 1 .. {_lib.POL_OBSH_MAXFRAMES}, got {f!r}")
+        sources = (self.sources,) if isinstance(self.sources, str) else self.sources
+        if not isinstance(sources, (list, tuple)) or not 1 <= len(sources) <= _lib.POL_OBSH_MAXSRC:
+            raise bad(f"sources must be a list of 1 .. {_lib.POL_OBSH_MAXSRC} entries, got {self.sources!r}")
+        out = []
+        for s in sources:
+            name, rng = (s, None) if isinstance(s, str) else (s[0], tuple(s[1:])) if isinstance(s, (list, tuple)) and len(s) == 3 else (None, None)
+            if name not in _lib.POL_OBSH_SOURCES:
+                raise bad(f"unknown source {s!r} (a source is a name of {_lib.POL_OBSH_SOURCES} or (name, lo, hi))")
+            n = columns[name]
+            if isinstance(n, str):
+                raise bad(f"the env has no {name} ({n})")
+            lo, hi = (0, n) if rng is None else rng
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (lo, hi)) or not 0 <= lo < hi <= n:
+                raise bad(f"column range ({lo!r}, {hi!r}) of {name} must be whole numbers with 0 <= lo < hi <= {n}")
+            out.append((name, int(lo), int(hi)))
+        total = int(f) * sum(hi - lo for _, lo, hi in out)
+        if total > _lib.POL_OBSH_MAXCOLS:
+            raise bad(f"frames * K = {total} columns, at most {_lib.POL_OBSH_MAXCOLS}")
+        return out
+
+
 class PolicyEnv:
     """conf: a RobotConfig (used as a copy with reference_quirks = False, sim_enabled = True: a reset then writes a proper wxyz
     qpos).  decimation: sim steps per policy step.  mode: "position" (ctrl = joint targets [rad] = default_joint_pos +
@@ -322,7 +369,16 @@ class PolicyEnv:
     info.  episode_run [N, NREC] and episode_start_xy [N, 2] are the running episode's state.  reset() starts the episodes it
     forces and records nothing for the ones it abandons.  curriculum: a PolicyCurriculum or a dict of its fields (None =
     none); implies episode_stats, needs terrain= and max_episode_steps > 0: the same launch then writes terrain_level, the level
-    of each done env's next episode, before the terrain's redraw reads it."""
+    of each done env's next episode, before the terrain's redraw reads it.
+
+    obs_history: a PolicyObsHistory or a dict of its fields (None = none: the launches and every result are those of an env
+    built without the argument).  One more launch closes step() and reset() (include/tsidb.h tsidb_policy_obs_history) and keeps
+    obs_history [N, frames * K] in the env's dtype: the last `frames` selections of the named tensors, frame-major, oldest
+    first - frame h is columns h K .. (h + 1) K, the newest frame is the current selection.  Frames are copies of what the
+    observation kernels left, noise included.  An env a step or reset() restarts holds `frames` copies of its first
+    observation; reset() leaves the history of the envs it does not restart as it is (it is no new time step).  The tensor is
+    in step()'s info, and "obs_history" is an input block of a PolicyActor - so rollout() runs with a history as it is.
+    obs_history_spec is the PolicyObsHistory, obs_history_sources its sources resolved to [(name, lo, hi)]."""
 
     # the randomisation's launches a step makes; class-level so that an instance built without __init__ steps unrandomised
     randomization = None
@@ -335,12 +391,15 @@ class PolicyEnv:
     _teacher_beta = None
     # episode statistics and the terrain curriculum: _episode = the tsidb_policy_episode block, None = the slice is off
     curriculum = _episode = episode_run = episode_start_xy = episode_last = episode_sum = None
+    # the observation history: obs_history = the [N, frames * K] tensor, _obs_history = the tsidb_policy_obs_history block;
+    # None = off
+    obs_history = _obs_history = None
 
     def __init__(self, conf=None, num_envs=None, device=None, decimation=10, mode="position", action_scale=0.25,
                  default_joint_pos=None, action_clip=100.0, delay=None, filter_alpha=1.0, command_range=((0.0, 0.0),) * 3,
                  max_episode_steps=0, reward_weights=None, term_bodies=None, sigma=0.25, h_target=None, t_air=0.25, deadband=0.1,
                  seed=0, randomization=None, tsid=None, walk=None, teacher_weights=None, sigma_com=0.05, sigma_foot=0.05, terrain=None,
-                 episode_stats=False, curriculum=None):
+                 episode_stats=False, curriculum=None, obs_history=None):
         from .conf import RobotConfig
         conf = copy.copy(conf) if conf is not None else RobotConfig()
         conf.reference_quirks = False
@@ -383,6 +442,14 @@ class PolicyEnv:
                 raise _lib.TsidbError(f"PolicyEnv: {', '.join(moved)} cannot be used with tsid: the walking plan and the contact "
                                       "references start from the base pose the reset captured (joint and velocity noise are fine: "
                                       "the closed-loop tick reads the sim state)")
+        if obs_history is not None:
+            from .model import ModelBlob
+            self.obs_history_spec = PolicyObsHistory.of(obs_history)
+            na = int(ModelBlob(getattr(conf, "model_blob", None))["model_dims"][3])   # (the controller is not built yet)
+            scan = 0 if ter is None else int(ter[_lib.POL_TER_SCAN_NX] * ter[_lib.POL_TER_SCAN_NY])
+            self.obs_history_sources = self.obs_history_spec.resolve(dict(
+                obs=_lib.pol_nobs(na), priv=_lib.POL_NPRIV, command=3, height_scan=scan or "it needs terrain= with scan_x and scan_y",
+                teacher_obs=_lib.pol_teach_nobs(na) if tsid is not None else "it needs tsid = 'stand' or 'walk'"))
         # the controller
         self.wc = wc = WalkController(conf, num_envs=num_envs, device=device)
         self.num_envs, self.device, self.dtype, self.NA = wc.num_envs, wc.device, wc.dtype, wc.NA
@@ -447,7 +514,9 @@ class PolicyEnv:
                 self.episode_run, self.episode_start_xy, self.episode_last, self.episode_sum, self.terrain_level,
                 self.teacher_terms if tsid is not None else None)))
             wc._call("tsidb_policy_episode_config", *vec(epp))
-        self.reset()   # (episode 1 starts)
+        if obs_history is not None:
+            self._build_obs_history()
+        self.reset()   # (episode 1 starts: every env's history is filled with its first observation)
 
     @staticmethod
     def _base_params(decimation, action_clip, filter_alpha, sigma, t_air, deadband, max_episode_steps, seed, command_range, reward_weights):
@@ -488,6 +557,21 @@ class PolicyEnv:
         if fraction is not None:
             self.sched.enable_touchdown_feedback(fraction)     # (reset() plans: every env is restarted before the first step)
 
+    def _build_obs_history(self):
+        """the history tensor and the block the launch takes: each source a column range of one of the env's tensors"""
+        item = self._rows.element_size()
+        frame = {"obs": (self._rows, 0), "priv": (self._rows, self.NOBS), "command": (self.command, 0),
+                 "height_scan": (self.height_scan, 0), "teacher_obs": (getattr(self, "teacher_obs", None), 0)}
+        h = _lib.PolicyObsHistory()
+        h.frames, h.n_src = int(self.obs_history_spec.frames), len(self.obs_history_sources)
+        for i, (name, lo, hi) in enumerate(self.obs_history_sources):
+            t, first = frame[name]
+            h.src[i], h.src_ld[i], h.src_cols[i] = t.data_ptr() + (first + lo) * item, int(t.stride(0)), hi - lo
+        K = sum(hi - lo for _, lo, hi in self.obs_history_sources)
+        self.obs_history = torch.zeros(self.num_envs, h.frames * K, dtype=self.wc.dtype, device=self.wc.device)
+        h.history = self.obs_history.data_ptr()
+        self._obs_history = h
+
     def written(self):
         """Every tensor a step() writes: what a caller that captures steps in a graph rewinds after its warm-up and keeps
         alive (WalkController._written lists the controller's)."""
@@ -507,6 +591,8 @@ class PolicyEnv:
             yield from (self.episode_run, self.episode_start_xy, self.episode_last, self.episode_sum)
             if self.curriculum is not None:
                 yield self.terrain_level
+        if self._obs_history is not None:
+            yield self.obs_history
 
     def _act(self, action):
         self.wc._call("tsidb_policy_act", C.byref(self._bufs), _ptr(action), self.wc._stream())
@@ -582,6 +668,10 @@ class PolicyEnv:
         wc._call("tsidb_policy_episode_begin", C.byref(self._bufs), C.byref(self._episode), _ptr(wc.rows), wc.NROW, _ptr(wc.qpos),
                  wc._stream())
 
+    def _push_obs_history(self, push):
+        wc = self.wc
+        wc._call("tsidb_policy_obs_history", C.byref(self._obs_history), _ptr(wc.rows), wc.NROW, int(push), wc._stream())
+
     def episode_stats(self, clear=True):
         """What the episodes that finished since the last clear amount to, as 0-dim float64 device tensors (no host read):
         episodes and timeouts (counts), then means over the finished episodes (divisor max(episodes, 1)): length [policy steps],
@@ -621,9 +711,11 @@ class PolicyEnv:
         self._teacher_beta.fill_(float(teacher_beta))
         return self._teacher_beta
 
-    def _after_reset_done(self):
+    def _after_reset_done(self, push=1):
         """what reset() and step() launch behind reset_done, each only while its group is on: a new plan, reset noise and new
-        tables for the envs just restarted, then the observation, the height scan and the teacher's observation of every env"""
+        tables for the envs just restarted, then the observation, the height scan and the teacher's observation of every env,
+        and last the observation history - push = 1 from step(): a new frame for every env; 0 from reset(): only the
+        restarted envs are refilled"""
         if self.sched is not None:
             self._replan()
         if self._dr_reset:
@@ -637,6 +729,8 @@ class PolicyEnv:
             self._height_scan()
         if self.tsid is not None:
             self._teacher_obs()
+        if self._obs_history is not None:
+            self._push_obs_history(push)
 
     def reset(self, env_ids=None):
         """Restart the envs env_ids (None = all) as a done flag would: standing state, zeroed action history and air times, ctrl
@@ -653,7 +747,7 @@ class PolicyEnv:
         wc.reset_done()
         if self.sched is not None and env_ids is None:
             self.clock.zero_()
-        self._after_reset_done()
+        self._after_reset_done(push=0)
         wc.done.zero_()
         self.timeout.zero_()
         return self.obs
@@ -667,7 +761,8 @@ class PolicyEnv:
         step applied (0 for an env it restarted: the reset clears the wrenches).  With tsid set, info also holds teacher_terms
         [N, 4] (unweighted; already in reward with teacher_weights), teacher_action [N, NA] and teacher_obs [N, 14 + NA].  With
         terrain set, height_scan [N, nx * ny], env_params [N, 8] (the sim's table, as the restarts left it) and terrain_level.
-        With episode_stats or a curriculum, episode_last and episode_sum [N, NREC] float64 (see the class)."""
+        With episode_stats or a curriculum, episode_last and episode_sum [N, NREC] float64 (see the class).  With obs_history
+        set, obs_history [N, frames * K]: the step's observation is its newest frame."""
         wc = self.wc
         if action is None:
             raise _lib.TsidbError("PolicyEnv.step: action is None")
@@ -693,6 +788,8 @@ class PolicyEnv:
             info.update(height_scan=self.height_scan, env_params=wc.env_params, terrain_level=self.terrain_level)
         if self.tsid is not None:
             info.update(teacher_terms=self.teacher_terms, teacher_action=self.teacher_action, teacher_obs=self.teacher_obs)
+        if self._obs_history is not None:
+            info["obs_history"] = self.obs_history
         if self._dr_push:
             info["push"] = wc.xfrc[:, 0, :3]
         return self.obs, self.reward, self.done, info
