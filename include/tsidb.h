@@ -995,6 +995,51 @@ int tsidb_policy_learn_imit(tsidb_handle h, const tsidb_policy_net *actor, const
                             const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit, float *workspace,
                             size_t workspace_bytes, float *stats, void *stream);
 
+/* tsidb_policy_learn with the robot's left / right symmetry (rsl_rl's symmetry_cfg: use_data_augmentation, use_mirror_loss,
+ * mirror_loss_coeff).  Everything of tsidb_policy_learn holds - three launches, no atomics, one fixed order of every sum, no
+ * host read, no allocation, capturable - with these additions.  A mirror map is a signed permutation of a row,
+ * mirror(x)[c] = sign[c] * x[perm[c]]: S_o of the actor's input row (actor_perm, actor_sign [K_actor]), S_c of the critic's
+ * (critic_perm, critic_sign [K_critic]; unused without a critic), S_a of the action (action_perm, action_sign [NA]); int32 and
+ * float32 device arrays.  A perm entry outside its row makes that mirrored column 0; nothing is read out of bounds.
+ * For minibatch row m with j = index[m] valid: x' = S_o x, a' = S_a action[j]; logp_old, value, advantage and returns of the
+ * mirrored row are its original's.
+ *   augment != 0: L_pi, L_v, stats[3], stats[4] are means over the 2 M virtual rows (the M originals and their M mirrors, each
+ *     weighted 1 / (2 M)), the critic sees S_c of its own input, dlog_std sums over the 2 M rows, stats[6] counts the virtual rows
+ *     used, stats[7] counts each bad index once.
+ *   L_sym = 1 / (M NA) sum_m | mu(x'_m) - S_a mu(x_m) |^2;   loss = (the above) + mirror_coef L_sym.  The target S_a mu(x_m) is
+ *     a constant: the gradient flows through mu(x'_m) alone (dmu' gains mirror_coef 2 d / (M NA)); log_std gets nothing from it.
+ *   augment == 0: the mirrored rows carry the mirror term alone - no mirrored rows for the critic, the means stay over M.
+ * sym->stats [TSIDB_POL_SYM_NSTATS] float32: 0 L_sym (formed at mirror_coef = 0 too)   1 mirrored rows used.
+ * With augment == 0 and mirror_coef == 0 the mirrored rows add exact zeros: the gradients are tsidb_policy_learn's bit for bit.
+ * With augment != 0, mirror_coef == 0 and M a multiple of 16 they are, bit for bit, tsidb_policy_learn's on a storage of twice
+ * the rows whose second half holds the mirrored rows, with index2 = (index, index + rows).
+ * workspace: at least tsidb_policy_learn_sym_workspace's bytes.  With Mp = M rounded up to a multiple of 16 every per-row array
+ * has 2 Mp rows, the originals in [0, Mp), the mirrors in [Mp, 2 Mp): the first 2 Mp * NA floats are mu, the next 2 Mp are v
+ * (with a critic; its mirrored half is 0 without augment).  The weight gradient runs over the 2 Mp rows in segments of
+ * TSIDB_POL_LEARN_SEG_ROWS in that order.
+ * Rejects: what tsidb_policy_learn rejects; a NULL actor or action table, a NULL critic table with a critic, a NULL sym->stats;
+ * a negative or non-finite mirror_coef; M above 2^29.  sym NULL is tsidb_policy_learn (tsidb_policy_learn_workspace's bytes). */
+enum { TSIDB_POL_SYM_NSTATS = 2 };
+typedef struct tsidb_policy_symmetry {
+  const int32_t *actor_perm;
+  const float *actor_sign;
+  const int32_t *critic_perm;
+  const float *critic_sign;
+  const int32_t *action_perm;
+  const float *action_sign;
+  int augment;
+  float mirror_coef;              /* >= 0 */
+  float *stats;                   /* [TSIDB_POL_SYM_NSTATS] */
+} tsidb_policy_symmetry;
+
+int tsidb_policy_learn_sym_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes);
+
+int tsidb_policy_learn_sym(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                           const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                           const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                           const tsidb_policy_learn_cfg *cfg, const tsidb_policy_symmetry *sym, float *workspace,
+                           size_t workspace_bytes, float *stats, void *stream);
+
 /* ---- the step's side of a PPO iteration: what rsl_rl runs per minibatch behind the loss - its adaptive step size from the
  * exact Gaussian KL (schedule = "adaptive"), torch's clip_grad_norm_ over all parameters, and torch.optim.Adam's default
  * single-tensor step - as three plain asynchronous launches on the given stream: no atomics, no counters, no allocation, no

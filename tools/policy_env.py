@@ -72,7 +72,12 @@ at 4096 and 512 envs, decimation 4 and 10, timed windows alternating between the
               (TorchHistory below: cat, where on done, repeat), in alternating windows, at 4096 and 512 envs, decimation 4; whether
               the two stacks end bit-identical; then eager 16-step rollouts of an actor on the stacked row against the same actor
               on obs alone (H x 71 <= 512); default profiles/policy_obs_history.json.  Kernel time: rocprofv3 --kernel-trace
-              --stats -- python tools/policy_env.py --history H --trace ENVS STEPS (which prints the bytes a launch moves)"""
+              --stats -- python tools/policy_env.py --history H --trace ENVS STEPS (which prints the bytes a launch moves)
+    python tools/policy_env.py --symmetry [out.json]   the learner's mirror symmetry (PolicyLearner(symmetry=PolicySymmetry(env, actor))):
+              backward() on one minibatch of --learn's recorded rollout with augmentation alone, with the mirror term alone and with
+              both, against the plain backward() and against the same loss in eager torch (gather, mirror, concatenate, autograd),
+              in alternating windows, at 4096 x 16 and 512 x 16 rows (a process per case); the first minibatch's loss, L_sym and
+              gradients from both; default profiles/policy_symmetry.json"""
 import json
 import sys
 import time
@@ -933,6 +938,101 @@ def main_history(args):
     report(out_path, obs_history=dict(frames=frames, sources=["obs"]), runs=[measure_history(n, frames) for n in (4096, 512)])
 
 
+class TorchSymmetryLearner(TorchLearner):
+    """TorchLearner with rsl_rl's symmetry in eager torch: the minibatch gathered, mirrored and concatenated into one batch of 2 M
+    rows for the surrogate and the value loss (augment), and the mirror loss against the detached, mirrored mean"""
+
+    def __init__(self, sym, augment, mirror_coef, *a, **kw):
+        super().__init__(*a, **kw)
+        self.augment, self.mirror_coef = augment, mirror_coef
+        tables = dict(actor=(sym.actor_perm, sym.actor_sign), critic=(sym.critic_perm, sym.critic_sign), action=(sym.action_perm, sym.action_sign))
+        self.tables = {k: (p.long(), s) for k, (p, s) in tables.items()}     # (int64 once: torch's index wants it)
+
+    def mirror(self, x, which):
+        perm, sign = self.tables[which]
+        return x[:, perm] * sign
+
+    def loss(self, st, index):
+        rows, c, ls = st.logp.numel(), self.clip, self.log_std
+        j = index.long()
+        m = j.shape[0]
+        flat = lambda t: t.reshape(rows, -1)[j]
+        x, xc, a = flat(st.actor_input), flat(st.critic_input), flat(st.action)
+        mu_all = self.actor(torch.cat([x, self.mirror(x, "actor")]))
+        n = 2 * m if self.augment else m
+        rep = (lambda t: torch.cat([t, t])) if self.augment else (lambda t: t)
+        v = self.critic(torch.cat([xc, self.mirror(xc, "critic")])[:n]).squeeze(1)
+        z = (torch.cat([a, self.mirror(a, "action")])[:n] - mu_all[:n]) / ls.exp()
+        logp = -(0.5 * z * z + ls).sum(1) - 0.5 * a.shape[1] * 1.8378770664093453
+        r = (logp - rep(st.logp.reshape(-1)[j])).exp()
+        adv = rep((st.advantage.reshape(-1)[j] - self.adv_stats[0]) * self.adv_stats[1])
+        l_pi = torch.max(-adv * r, -adv * r.clamp(1 - c, 1 + c)).mean()
+        old, ret = rep(st.value[:-1].reshape(-1)[j]), rep(st.returns.reshape(-1)[j])
+        l_v = torch.max((v - ret) ** 2, (old + (v - old).clamp(-c, c) - ret) ** 2).mean()
+        entropy = (ls + 0.5 * (1 + 1.8378770664093453)).sum()
+        self.l_sym = ((mu_all[m:] - self.mirror(mu_all[:m].detach(), "action")) ** 2).mean()
+        return l_pi + self.value_coef * l_v - self.entropy_coef * entropy + self.mirror_coef * self.l_sym
+
+
+def measure_symmetry(n, minibatches=4, window=40, windows=4, preroll=3, mirror_coef=0.5):
+    """backward() calls/s on one minibatch of a recorded rollout, in alternating windows of one process: the plain learner; the
+    learner with a symmetry - augmentation alone, the mirror term alone, both; and the loss of `both` in eager torch with
+    autograd.  Also the first minibatch's loss and L_sym from the fused and the torch learner before either has moved a weight."""
+    from tsid_control_amd import PolicyLearner, PolicySymmetry
+    st, plain, copies = learn_setup(n)
+    pa = plain.actor
+    sy = PolicySymmetry(pa.env, pa)
+    kw = dict(clip=0.2, value_coef=1.0, entropy_coef=0.01)
+    fused = {name: PolicyLearner(pa, symmetry=sy, symmetry_augment=aug, mirror_coef=coef, **kw)
+             for name, aug, coef in (("augment", True, 0.0), ("mirror", False, mirror_coef), ("both", True, mirror_coef))}
+    eager = TorchSymmetryLearner(sy, True, mirror_coef, copies.actor, copies.critic, pa.log_std.detach(), **kw)
+    rows = st.logp.numel()
+    index = torch.randperm(rows, generator=torch.Generator(device="cuda:0").manual_seed(3), dtype=torch.int32, device="cuda:0")[:rows // minibatches].contiguous()
+    plain.fill_adv_stats(st)
+    eager.adv_stats = plain.adv_stats.clone()
+    for pl in fused.values():
+        pl.adv_stats.copy_(plain.adv_stats)
+    stats = fused["both"].backward(st, index, adv_stats=fused["both"].adv_stats).clone()
+    grad_torch = torch.autograd.grad(eager.loss(st, index), eager.parameters())
+    grad_rel = max(float((a.grad - b).abs().max() / b.abs().max()) for a, b in zip(fused["both"].parameters(), grad_torch))
+    with torch.no_grad():
+        loss_torch = float(eager.loss(st, index))
+
+    def torch_backward(k):
+        for _ in range(k):
+            for p in eager.parameters():
+                p.grad = None
+            eager.loss(st, index).backward()
+    run = dict(plain=lambda k: [plain.backward(st, index, adv_stats=plain.adv_stats) for _ in range(k)], torch_both=torch_backward)
+    for name, pl in fused.items():
+        run[name] = lambda k, pl=pl: [pl.backward(st, index, adv_stats=pl.adv_stats) for _ in range(k)]
+    r = alternate(run, window, windows, preroll)
+    med = r["policy_steps_per_s_median"]
+    return dict(envs=n, rollout_steps=st.steps, rows=rows, minibatch_rows=int(index.shape[0]), mirror_coef=mirror_coef, window_calls=window, windows=windows,
+                backward_per_s_median=med, backward_per_s_all=r["all"], us_per_backward={k: 1e6 / v for k, v in med.items()},
+                over_plain={k: med["plain"] / med[k] for k in fused}, both_over_torch=med["both"] / med["torch_both"],
+                first_minibatch=dict(loss_fused=float(stats[5]), loss_torch=loss_torch, mirror_loss_fused=float(fused["both"].sym_stats[0]),
+                                     mirror_loss_torch=float(eager.l_sym), largest_gradient_difference_over_largest_entry=grad_rel,
+                                     rows_used=float(stats[6]), mirrored_rows=float(fused["both"].sym_stats[1])))
+
+
+def main_symmetry(args):
+    """--symmetry: backward() with augmentation and with the mirror term against the plain backward() and against eager torch, at
+    4096 x 16 and 512 x 16 rows with the 256-128 networks; a process per case"""
+    import subprocess
+    if args and args[0] == "--case":
+        print(json.dumps(measure_symmetry(int(args[1]))))
+        return
+    out_path = args[0] if args else "profiles/policy_symmetry.json"
+    runs = []
+    for n in (4096, 512):
+        r = subprocess.run([sys.executable, sys.argv[0], "--symmetry", "--case", str(n)], capture_output=True, text=True, check=True)
+        runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    report(out_path, actor="obs -> 256 -> 128 -> NA, ELU", critic="obs | priv -> 256 -> 128 -> 1, ELU",
+           loss="clip 0.2, value_coef 1, entropy_coef 0.01, clipped value loss, normalised advantages; mirror_coef 0.5",
+           tables="derived from the model blob: obs and obs | priv of the v1 robot, mirror normal x", runs=runs)
+
+
 def main_normalize(which, args):
     """--actor --normalize / --learn --normalize: the section's method (a process per case, four alternating windows, medians,
     4096 and 512 envs) with the normaliser on; each run replaces its own entry of profiles/policy_norm.json"""
@@ -973,6 +1073,9 @@ def main_normalize(which, args):
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--history":
         main_history(sys.argv[2:])
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--symmetry":
+        main_symmetry(sys.argv[2:])
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--episodes":
         main_episodes(sys.argv[2:])

@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "PolicyLearner":
         from .policy_learner import PolicyLearner
         return PolicyLearner
+    if name == "PolicySymmetry":
+        from .policy_symmetry import PolicySymmetry
+        return PolicySymmetry
     if name == "PolicyOptimizer":
         from .policy_optimizer import PolicyOptimizer
         return PolicyOptimizer

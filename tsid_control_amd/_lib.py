@@ -22,7 +22,7 @@ SYMBOLS = ["tsidb_dims", "tsidb_create", "tsidb_destroy", "tsidb_last_error", "t
            "tsidb_policy_opt_workspace", "tsidb_policy_opt_step",
            "tsidb_policy_teacher_mix", "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit",
            "tsidb_policy_episode_config", "tsidb_policy_episode_end", "tsidb_policy_episode_begin",
-           "tsidb_policy_obs_history"]
+           "tsidb_policy_obs_history", "tsidb_policy_learn_sym_workspace", "tsidb_policy_learn_sym"]
 
 # tsidb_set_option / tsidb_get_option numbers (include/tsidb.h TSIDB_OPT_*; 4 is retired) and tsidb_stream_create roles
 OPT_SIM_WAVES, OPT_LDS_PAD, OPT_CU_SPLIT, OPT_QP_FAST_EQ = 1, 2, 3, 5
@@ -84,6 +84,8 @@ POL_LEARN_STATS = ("policy_loss", "value_loss", "entropy", "approx_kl", "clip_fr
 POL_TEACHER_MIX_STREAM = 23
 POL_IMIT_LOSSES = ("mse", "huber")
 POL_IMIT_STATS = ("imitation_loss", "weight_sum", "weighted_rows", "skipped_rows")
+# the mirror symmetry (include/tsidb.h tsidb_policy_learn_sym): its stats
+POL_SYM_STATS = ("mirror_loss", "mirrored_rows")
 # episode statistics and the terrain curriculum (include/tsidb.h TSIDB_POL_EP_*, TSIDB_POL_EPP_*): the columns of an episode's
 # record, tsidb_policy_episode_config's parameter vector, PolicyCurriculum's fields and the stream of a graduate's level
 POL_EP_COUNT, POL_EP_TIMEOUT, POL_EP_LENGTH, POL_EP_RETURN, POL_EP_DISPLACEMENT, POL_EP_LEVEL, POL_EP_TERMS, POL_EP_TEACH, POL_EP_NREC = \
@@ -182,6 +184,13 @@ class PolicyGrads(C.Structure):
 class PolicyLearnCfg(C.Structure):
     """tsidb_policy_learn_cfg (include/tsidb.h)"""
     _fields_ = [("clip", C.c_float), ("value_coef", C.c_float), ("entropy_coef", C.c_float), ("value_clip", C.c_int)]
+
+
+class PolicySymmetryTables(C.Structure):
+    """tsidb_policy_symmetry (include/tsidb.h): the signed permutations of tsidb_policy_learn_sym and its two switches"""
+    _fields_ = [("actor_perm", C.c_void_p), ("actor_sign", C.c_void_p), ("critic_perm", C.c_void_p), ("critic_sign", C.c_void_p),
+                ("action_perm", C.c_void_p), ("action_sign", C.c_void_p), ("augment", C.c_int), ("mirror_coef", C.c_float),
+                ("stats", C.c_void_p)]
 
 
 class PolicyImit(C.Structure):
@@ -288,6 +297,8 @@ def load(path=None):
     L.tsidb_policy_obs_history.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     L.tsidb_policy_learn_imit_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
     L.tsidb_policy_learn_imit.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.tsidb_policy_learn_sym_workspace.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+    L.tsidb_policy_learn_sym.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     L.tsidb_policy_norm_workspace.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t)]
     L.tsidb_policy_norm_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.tsidb_policy_actor_norm.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp]

@@ -738,6 +738,7 @@ struct tsidb_ctx {
   double pol_ep[TSIDB_POL_EPP_NPARAMS] = {};
   bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
   bool learn_imit_big_lds = false;           // tsidb_policy_learn_imit: k_policy_learn_rows_imit's likewise
+  bool learn_sym_big_lds = false;            // tsidb_policy_learn_sym: k_policy_learn_rows_sym's likewise
   bool actor_norm_big_lds = false;           // tsidb_policy_actor_norm: k_policy_actor_norm's likewise
   bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
   std::string err;
@@ -1869,25 +1870,30 @@ static int learn_blocks(const WgradArgs &w) {
   return j.blk0 + ((j.gw + 15) / 16) * j.nkg;
 }
 
-// tsidb_policy_learn_workspace and tsidb_policy_learn_imit_workspace: one body
+// The rows of the symmetry variant's per-row arrays: the originals' Mp, then as many for their mirrors
+static int learn_sym_rows(int M) { return 2 * ((M + ACT_TILE - 1) / ACT_TILE) * ACT_TILE; }
+
+// tsidb_policy_learn_workspace, tsidb_policy_learn_imit_workspace and tsidb_policy_learn_sym_workspace: one body
 static int learn_workspace_call(tsidb_handle h, const char *who, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes,
-                                int nr) {
+                                int nr, bool sym = false) {
   GUARD_BEGIN
   if (!actor) throw std::string(who) + "null actor";
   if (!bytes) throw std::string(who) + "null bytes";
   if (M < 1) throw std::string(who) + "M must be >= 1";
+  if (sym && M > (1 << 29)) throw std::string(who) + "M is too large";
   LearnNet nets[2] = {};
   nets[0] = learn_net(actor, who, "actor", NA, "NA");
   if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
-  *bytes = learn_layout(nets, M, nullptr, nullptr, nullptr, nr) * sizeof(float);
+  *bytes = learn_layout(nets, sym ? learn_sym_rows(M) : M, nullptr, nullptr, nullptr, nr) * sizeof(float);
   GUARD_END
 }
 
-// tsidb_policy_learn and tsidb_policy_learn_imit: one body; without imit the launches are the three kernels' as ever
+// tsidb_policy_learn, tsidb_policy_learn_imit and tsidb_policy_learn_sym: one body; without imit and sym the launches are the
+// three kernels' as ever
 static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads,
                       const float *log_std, float *log_std_grad, const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit,
-                      float *workspace, size_t workspace_bytes, float *stats, void *stream) {
+                      float *workspace, size_t workspace_bytes, float *stats, void *stream, const tsidb_policy_symmetry *sym = nullptr) {
   GUARD_BEGIN
   hipStream_t s = (hipStream_t)stream;
   if (!actor) throw std::string(who) + "null actor";
@@ -1913,13 +1919,20 @@ static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *a
     if (!imit->stats) throw std::string(who) + "null imit stats";
     if (imit->loss != TSIDB_POL_IMIT_MSE && imit->loss != TSIDB_POL_IMIT_HUBER) throw std::string(who) + "unknown loss (TSIDB_POL_IMIT_MSE or _HUBER)";
   }
-  const int nr = imit ? LRN_NR + LRN_NI : LRN_NR;
+  if (sym) {
+    if (!sym->actor_perm || !sym->actor_sign || !sym->action_perm || !sym->action_sign) throw std::string(who) + "null actor or action table";
+    if (critic && (!sym->critic_perm || !sym->critic_sign)) throw std::string(who) + "a critic needs critic_perm and critic_sign";
+    if (!(sym->mirror_coef >= 0.f) || !std::isfinite(sym->mirror_coef)) throw std::string(who) + "mirror_coef is negative or not finite";
+    if (!sym->stats) throw std::string(who) + "null sym stats";
+    if (batch->M > (1 << 29)) throw std::string(who) + "M is too large";
+  }
+  const int nr = imit ? LRN_NR + LRN_NI : sym ? LRN_NR + LRN_NS : LRN_NR;
   LearnArgs a = {};
   a.net[0] = learn_net(actor, who, "actor", NA, "NA");
   if (critic) a.net[1] = learn_net(critic, who, "critic", 1, "1");
   WgradArgs w = {};
   ReduceArgs r = {};
-  const size_t need = learn_layout(a.net, batch->M, &w, &r, &a.r, nr) * sizeof(float);
+  const size_t need = learn_layout(a.net, sym ? learn_sym_rows(batch->M) : batch->M, &w, &r, &a.r, nr) * sizeof(float);
   if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
   int np = 0, widest = 0;
   for (int y = 0; y < 2; y++) {
@@ -1945,15 +1958,26 @@ static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *a
   r.ws = workspace; r.log_std = log_std; r.log_std_grad = log_std_grad; r.stats = stats;
   r.value_coef = cfg->value_coef; r.entropy_coef = cfg->entropy_coef;
   const size_t lds = act_lds_bytes(a.LD);
-  bool &big = imit ? h->learn_imit_big_lds : h->learn_big_lds;
+  bool &big = imit ? h->learn_imit_big_lds : sym ? h->learn_sym_big_lds : h->learn_big_lds;
   if (lds > 65536 && !big) {     // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle and kernel)
-    const void *fn = imit ? reinterpret_cast<const void *>(&k_policy_learn_rows_imit) : reinterpret_cast<const void *>(&k_policy_learn_rows);
+    const void *fn = imit ? reinterpret_cast<const void *>(&k_policy_learn_rows_imit)
+                     : sym ? reinterpret_cast<const void *>(&k_policy_learn_rows_sym) : reinterpret_cast<const void *>(&k_policy_learn_rows);
     HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
     big = true;
   }
   h->note_stream(s);
-  const dim3 rows_grid(w.Mp / ACT_TILE, critic ? 2 : 1), reduce_grid((unsigned)((r.rp + NA + (imit ? LRN_NI : 1) + 255) / 256));
-  if (imit) {
+  const int tiles = sym ? w.Mp / (2 * ACT_TILE) : w.Mp / ACT_TILE;     // (sym: a workgroup runs its tile and the tile's mirror)
+  const dim3 rows_grid(tiles, critic ? 2 : 1), reduce_grid((unsigned)((r.rp + NA + (imit ? LRN_NI : sym ? LRN_NS : 1) + 255) / 256));
+  if (sym) {
+    const int augment = sym->augment != 0;
+    const LearnSym ls = {{sym->actor_perm, sym->critic_perm}, {sym->actor_sign, sym->critic_sign}, sym->action_perm, sym->action_sign,
+                         augment, w.Mp / 2, sym->mirror_coef};
+    const ReduceSym rs = {sym->mirror_coef, batch->M, sym->stats};
+    r.M = augment ? 2 * batch->M : batch->M;                           // the rows the means are over
+    hipLaunchKernelGGL(k_policy_learn_rows_sym, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a, ls);
+    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
+    hipLaunchKernelGGL(k_policy_learn_reduce_sym, reduce_grid, dim3(256), 0, s, r, rs);
+  } else if (imit) {
     const LearnImit li = {imit->target, imit->weight, imit->skip_surrogate, imit->imitation_coef, imit->surrogate_coef,
                           imit->loss == TSIDB_POL_IMIT_HUBER};
     const ReduceImit ri = {imit->imitation_coef, imit->surrogate_coef, imit->stats};
@@ -1985,6 +2009,21 @@ int tsidb_policy_learn(tsidb_handle h, const tsidb_policy_net *actor, const tsid
                        const tsidb_policy_learn_cfg *cfg, float *workspace, size_t workspace_bytes, float *stats, void *stream) {
   return learn_call(h, "tsidb_policy_learn: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr, workspace,
                     workspace_bytes, stats, stream);
+}
+
+int tsidb_policy_learn_sym_workspace(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic, int M, size_t *bytes) {
+  return learn_workspace_call(h, "tsidb_policy_learn_sym_workspace: ", actor, critic, M, bytes, LRN_NR + LRN_NS, true);
+}
+
+int tsidb_policy_learn_sym(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
+                           const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads,
+                           const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
+                           const tsidb_policy_learn_cfg *cfg, const tsidb_policy_symmetry *sym, float *workspace, size_t workspace_bytes,
+                           float *stats, void *stream) {
+  if (!sym) return learn_call(h, "tsidb_policy_learn_sym: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr,
+                              workspace, workspace_bytes, stats, stream);
+  return learn_call(h, "tsidb_policy_learn_sym: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr, workspace,
+                    workspace_bytes, stats, stream, sym);
 }
 
 int tsidb_policy_learn_imit(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,

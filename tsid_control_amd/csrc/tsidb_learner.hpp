@@ -27,7 +27,15 @@
 // scales the surrogate's dlogp, zeroes the surrogate pieces of a row the policy did not act on, and writes LRN_NI more per-row
 // pieces behind the six; the row-piece job of the weight gradient sums them with the others, in the same fixed order.  The
 // IMIT = false instantiations are the kernels as they were: same names, same arguments, same code.
+//
+// The symmetry variant (tsidb_policy_learn_sym): k_policy_learn_rows_sym and k_policy_learn_reduce_sym are the SYM = true
+// instantiations.  A workgroup runs its tile twice: pass 0 is the plain one, pass 1 gathers the same stored rows through the
+// network's signed permutation (x'[c] = sign[c] x[perm[c]]), runs the forward pass again and writes every per-row array at rows
+// Mp + m0 + r - the originals keep rows [0, Mp) of arrays of 2 Mp rows, the mirrors take [Mp, 2 Mp), the weight gradient runs
+// over 2 Mp rows.  Pass 0 leaves mu of its 16 rows in a 16 x NA LDS image: S_a mu is the constant target of pass 1's mirror term.
+// LRN_NS more per-row pieces sit behind the six.  The SYM = false instantiations are the kernels as they were.
 #pragma once
+#include <type_traits>
 #include "tsidb_actor.hpp"
 
 namespace tsidb {
@@ -38,6 +46,8 @@ constexpr int LRN_NR = NA + 6;             // per-row pieces: dlogp (z_a^2 - 1) 
 enum { LRN_R_LPI = 0, LRN_R_LV, LRN_R_KL, LRN_R_CLIPPED, LRN_R_USED, LRN_R_BAD };
 constexpr int LRN_NI = 4;                  // the imitation variant's pieces, behind the six: w l_m, w, w > 0, surrogate skipped
 enum { LRN_I_LIM = 0, LRN_I_WSUM, LRN_I_WPOS, LRN_I_SKIPPED };
+constexpr int LRN_NS = 2;                  // the symmetry variant's pieces, behind the six: |mu(x') - S_a mu(x)|^2, mirrored row used
+enum { LRN_S_LSYM = 0, LRN_S_USED };
 constexpr int LRN_MAXJOBS = 2 * ACT_MAXL + 1;
 
 struct LearnNet {
@@ -64,17 +74,33 @@ struct LearnImit {
   int huber;
 };
 
+// tsidb_policy_learn_sym's additions to the rows kernel.  A perm entry outside its row reads as a 0 column.
+struct LearnSym {
+  const int *perm[2];                      // actor input [K_actor], critic input [K_critic] (NULL without a critic)
+  const float *sign[2];
+  const int *aperm;                        // action [NA]
+  const float *asign;
+  int augment, Mp;                         // Mp: the first workspace row of the mirrors
+  float coef;                              // the mirror term's weight
+};
+
 __device__ __forceinline__ float act_prime(int kind, float y) {   // the activation's derivative from its output
   if (kind == ACT_ELU) return y > 0.f ? 1.f : y + 1.f;
   if (kind == ACT_TANH) return 1.f - y * y;
   return y > 0.f ? 1.f : 0.f;
 }
 
-template <bool IMIT>
-__device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const LearnImit &im) {
-  constexpr int NR = IMIT ? LRN_NR + LRN_NI : LRN_NR;   // the stride of the per-row pieces
+template <bool IMIT, bool SYM = false>
+__device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const LearnImit &im, [[maybe_unused]] const LearnSym &sy = LearnSym{}) {
+  static_assert(!(IMIT && SYM), "the symmetry variant has no imitation term");
+  constexpr int NR = IMIT ? LRN_NR + LRN_NI : SYM ? LRN_NR + LRN_NS : LRN_NR;   // the stride of the per-row pieces
   extern __shared__ float lrn_lds[];
   __shared__ int lrn_row[ACT_TILE];        // the stored row of each tile row, -1 = none
+  [[maybe_unused]] float *lrn_mu = nullptr;   // SYM: mu of pass 0 [ACT_TILE, NA]
+  if constexpr (SYM) {
+    __shared__ float lrn_mu_image[ACT_TILE * NA];
+    lrn_mu = lrn_mu_image;
+  }
   const int which = blockIdx.y;
   const LearnNet &ln = a.net[which];
   const ActorNet &net = ln.net;
@@ -94,12 +120,40 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
   }
   __syncthreads();
 
+  // one pass over the tile; mir (a compile-time constant): the tile's mirror image, at workspace rows Mp + m0 ..
+  auto run_pass = [&](auto mirrored) {
+  constexpr bool mir = decltype(mirrored)::value;
+  [[maybe_unused]] const bool surr = !mir || sy.augment;   // the pass carries the surrogate and the value loss
+  const int w0 = mir ? sy.Mp + m0 : m0;    // the tile's first workspace row
+
+  if constexpr (mir) {
+    if (!surr && which == 1) {             // no mirrored rows for the critic: exact zeros where the weight gradient reads
+      float *R = ws + a.r;
+      for (int idx = tid; idx < ACT_TILE * net.K; idx += WAVE * ACT_WAVES) ws[ln.x + (size_t)w0 * net.K + idx] = 0.f;
+      for (int L = 0; L < net.n_layers; L++) {
+        const int width = net.width[L];
+        for (int idx = tid; idx < ACT_TILE * width; idx += WAVE * ACT_WAVES) {
+          ws[ln.h[L] + (size_t)w0 * width + idx] = 0.f;
+          ws[ln.g[L] + (size_t)w0 * width + idx] = 0.f;
+        }
+      }
+      if (tid < ACT_TILE) R[(size_t)(w0 + tid) * NR + NA + LRN_R_LV] = 0.f;
+      return;                              // (block-uniform)
+    }
+  }
+
   // ---- the input rows, gathered; a row without a stored row and the columns up to the next multiple of 4 are 0
   for (int idx = tid; idx < ACT_TILE * net.K; idx += WAVE * ACT_WAVES) {
     const int r = idx / net.K, c = idx - r * net.K, j = lrn_row[r];
-    const float v = j >= 0 ? ln.in[(size_t)j * net.K + c] : 0.f;
+    float v;
+    if constexpr (!mir) {
+      v = j >= 0 ? ln.in[(size_t)j * net.K + c] : 0.f;
+    } else {
+      const int src = sy.perm[which][c];
+      v = j >= 0 && src >= 0 && src < net.K ? sy.sign[which][c] * ln.in[(size_t)j * net.K + src] : 0.f;
+    }
     X[0][r * LD + c] = v;
-    ws[ln.x + (size_t)(m0 + r) * net.K + c] = v;
+    ws[ln.x + (size_t)(w0 + r) * net.K + c] = v;
   }
   if (tid < ACT_TILE * 4) {
     const int r = tid >> 2, c = net.K + (tid & 3);
@@ -111,7 +165,7 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
   act_layers(net, X, LD, i, g, wave, [&](int L, const float *H, int width) {
     for (int idx = tid; idx < ACT_TILE * width; idx += WAVE * ACT_WAVES) {
       const int r = idx / width, c = idx - r * width;
-      ws[ln.h[L] + (size_t)(m0 + r) * width + c] = H[r * LD + c];
+      ws[ln.h[L] + (size_t)(w0 + r) * width + c] = H[r * LD + c];
     }
   });
 
@@ -119,7 +173,7 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
   const int last = net.n_layers - 1;
   const float *Y = X[net.n_layers & 1];
   float *G = X[(net.n_layers + 1) & 1];
-  const float invM = 1.f / (float)a.M;
+  const float invM = 1.f / (float)(SYM && sy.augment ? 2 * a.M : a.M);
   float *R = ws + a.r;
   if (which == 1) {
     if (tid < ACT_TILE) {
@@ -139,23 +193,44 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
         }
         dv = raw * a.value_coef * invM;
       }
-      R[(size_t)(m0 + tid) * NR + NA + LRN_R_LV] = lv;
+      R[(size_t)(w0 + tid) * NR + NA + LRN_R_LV] = lv;
       G[tid * LD] = dv;
       G[tid * LD + 1] = G[tid * LD + 2] = G[tid * LD + 3] = 0.f;
-      ws[ln.g[last] + (size_t)(m0 + tid)] = dv;
+      ws[ln.g[last] + (size_t)(w0 + tid)] = dv;
     }
   } else {
     float *DL = G + LD - 1;                // dlogp of row r at G[r * LD + LD - 1]: past every column a layer uses
     for (int idx = tid; idx < ACT_TILE * NA; idx += WAVE * ACT_WAVES) {
       const int r = idx / NA, c = idx - r * NA, j = lrn_row[r];
-      G[r * LD + c] = j >= 0 ? (a.action[(size_t)j * NA + c] - Y[r * LD + c]) / expf(a.log_std[c]) : 0.f;   // z
+      if constexpr (!mir) {
+        G[r * LD + c] = j >= 0 ? (a.action[(size_t)j * NA + c] - Y[r * LD + c]) / expf(a.log_std[c]) : 0.f;   // z
+        if constexpr (SYM) lrn_mu[r * NA + c] = Y[r * LD + c];
+      } else {                             // z of the mirrored action; 0 where the pass has no surrogate
+        const int src = sy.aperm[c];
+        const float act = j >= 0 && src >= 0 && src < NA ? sy.asign[c] * a.action[(size_t)j * NA + src] : 0.f;
+        G[r * LD + c] = j >= 0 && surr ? (act - Y[r * LD + c]) / expf(a.log_std[c]) : 0.f;
+      }
     }
     __syncthreads();
     if (tid < ACT_TILE) {
       const int j = lrn_row[tid];
       float piece[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dlogp = 0.f;
       [[maybe_unused]] float ipiece[LRN_NI] = {0.f, 0.f, 0.f, 0.f};
-      if (j >= 0) {
+      [[maybe_unused]] float spiece[LRN_NS] = {0.f, 0.f};
+      if constexpr (mir) {
+        if (j >= 0) {                      // the mirror term's row: |mu(x') - S_a mu(x)|^2, S_a mu(x) from pass 0's image
+          float ls = 0.f;
+          for (int c = 0; c < NA; c++) {
+            const int src = sy.aperm[c];
+            const float t = src >= 0 && src < NA ? sy.asign[c] * lrn_mu[tid * NA + src] : 0.f;
+            const float d = Y[tid * LD + c] - t;
+            ls += d * d;
+          }
+          spiece[LRN_S_LSYM] = ls;
+          spiece[LRN_S_USED] = 1.f;
+        }
+      }
+      if (j >= 0 && surr) {
         float s = 0.f;
         for (int c = 0; c < NA; c++) {
           const float z = G[tid * LD + c];
@@ -194,15 +269,17 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
             ipiece[LRN_I_LIM] = w * (li / (float)NA);
           }
         }
-      } else if (m0 + tid < a.M) {
+      } else if (j < 0 && !mir && m0 + tid < a.M) {   // (a bad index is counted once, by pass 0)
         piece[LRN_R_BAD] = 1.f;
       }
       DL[tid * LD] = dlogp;
-      float *Rr = R + (size_t)(m0 + tid) * NR + NA;
+      float *Rr = R + (size_t)(w0 + tid) * NR + NA;
       for (int c = 0; c < 6; c++)
         if (c != LRN_R_LV || a.net[1].net.n_layers == 0) Rr[c] = piece[c];   // (LV is the critic's workgroup's; 0 without one)
       if constexpr (IMIT)
         for (int c = 0; c < LRN_NI; c++) Rr[6 + c] = ipiece[c];
+      if constexpr (SYM)
+        for (int c = 0; c < LRN_NS; c++) Rr[6 + c] = spiece[c];
     }
     __syncthreads();
     for (int idx = tid; idx < ACT_TILE * NA; idx += WAVE * ACT_WAVES) {
@@ -221,9 +298,18 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
           }
         }
       }
+      if constexpr (mir) {                   // the mirror term: on the mean of the mirrored row alone, its target a constant
+        if (sy.coef > 0.f && lrn_row[r] >= 0) {
+          const int src = sy.aperm[c];
+          const float t = src >= 0 && src < NA ? sy.asign[c] * lrn_mu[r * NA + src] : 0.f;
+          const float d = Y[r * LD + c] - t;
+          const float gs = sy.coef * (2.f / (float)(a.M * NA)) * d;
+          dmu = dmu + gs;
+        }
+      }
       G[r * LD + c] = dmu;
-      ws[ln.g[last] + (size_t)(m0 + r) * NA + c] = dmu;
-      R[(size_t)(m0 + r) * NR + c] = dlogp * (z * z - 1.f);
+      ws[ln.g[last] + (size_t)(w0 + r) * NA + c] = dmu;
+      R[(size_t)(w0 + r) * NR + c] = dlogp * (z * z - 1.f);
     }
     if (tid < ACT_TILE * 4) {
       const int r = tid >> 2, c = NA + (tid & 3);
@@ -267,8 +353,8 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
             const int row = 4 * g + r;
             float y = 0.f;
             if (k < Kk) {
-              y = acc[j][r] * act_prime(net.activation, Hprev[(size_t)(m0 + row) * Kk + k]);
-              Gprev[(size_t)(m0 + row) * Kk + k] = y;
+              y = acc[j][r] * act_prime(net.activation, Hprev[(size_t)(w0 + row) * Kk + k]);
+              Gprev[(size_t)(w0 + row) * Kk + k] = y;
             }
             D[row * LD + k] = y;                       // (k < round_up(Kk, 16) <= LD: the pad columns get 0)
           }
@@ -277,10 +363,14 @@ __device__ __forceinline__ void policy_learn_rows_body(const LearnArgs &a, const
     }
     __syncthreads();
   }
+  };                                       // run_pass
+  run_pass(std::false_type{});
+  if constexpr (SYM) run_pass(std::true_type{});
 }
 
 __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows(LearnArgs a) { policy_learn_rows_body<false>(a, LearnImit{}); }
 __global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows_imit(LearnArgs a, LearnImit im) { policy_learn_rows_body<true>(a, im); }
+__global__ __launch_bounds__(WAVE * ACT_WAVES) void k_policy_learn_rows_sym(LearnArgs a, LearnSym sy) { policy_learn_rows_body<false, true>(a, LearnImit{}, sy); }
 
 // ---------------------------------------------------------------------------- the weight gradients, segment by segment
 struct WgradJob {
@@ -358,8 +448,15 @@ struct ReduceImit {
   float *stats;          // [TSIDB_POL_IMIT_NSTATS]
 };
 
-template <bool IMIT>
-__device__ __forceinline__ void policy_learn_reduce_body(const ReduceArgs &a, const ReduceImit &im) {
+// tsidb_policy_learn_sym's additions to the reduction; ReduceArgs.M is then the rows the means are over (2 M with augment)
+struct ReduceSym {
+  float coef;
+  int M;                 // the minibatch's rows: L_sym = sum / (M NA)
+  float *stats;          // [TSIDB_POL_SYM_NSTATS]
+};
+
+template <bool IMIT, bool SYM = false>
+__device__ __forceinline__ void policy_learn_reduce_body(const ReduceArgs &a, const ReduceImit &im, [[maybe_unused]] const ReduceSym &sy = ReduceSym{}) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   const float *P = a.ws + a.part;
   auto total_of = [&](size_t off) {
@@ -389,7 +486,16 @@ __device__ __forceinline__ void policy_learn_reduce_body(const ReduceArgs &a, co
     a.stats[2] = ent;
     a.stats[3] = total_of(a.rp + NA + LRN_R_KL) * invM;
     a.stats[4] = total_of(a.rp + NA + LRN_R_CLIPPED) * invM;
-    if constexpr (!IMIT) {
+    if constexpr (SYM) {
+      const float lsym = total_of(a.rp + NA + 6 + LRN_S_LSYM) / (float)(sy.M * NA);
+      float loss = lpi + a.value_coef * lv - a.entropy_coef * ent;
+      if (sy.coef > 0.f) {
+        const float t = sy.coef * lsym;
+        loss = loss + t;
+      }
+      a.stats[5] = loss;
+      sy.stats[0] = lsym;
+    } else if constexpr (!IMIT) {
       a.stats[5] = lpi + a.value_coef * lv - a.entropy_coef * ent;
     } else {
       const float lim = total_of(a.rp + NA + 6 + LRN_I_LIM) * invM;
@@ -407,10 +513,13 @@ __device__ __forceinline__ void policy_learn_reduce_body(const ReduceArgs &a, co
   } else if (IMIT && e < a.rp + NA + LRN_NI) {   // the three other sums, a thread each: a segment-ordered sum is a serial chain of loads
     const int k = (int)(e - (a.rp + NA));        // 1 .. LRN_NI - 1
     im.stats[k] = total_of(a.rp + NA + 6 + k);
+  } else if (SYM && e == a.rp + NA + 1) {        // the mirrored rows used
+    sy.stats[1] = total_of(a.rp + NA + 6 + LRN_S_USED);
   }
 }
 
 __global__ __launch_bounds__(256) void k_policy_learn_reduce(ReduceArgs a) { policy_learn_reduce_body<false>(a, ReduceImit{}); }
 __global__ __launch_bounds__(256) void k_policy_learn_reduce_imit(ReduceArgs a, ReduceImit im) { policy_learn_reduce_body<true>(a, im); }
+__global__ __launch_bounds__(256) void k_policy_learn_reduce_sym(ReduceArgs a, ReduceSym sy) { policy_learn_reduce_body<false, true>(a, ReduceImit{}, sy); }
 
 } // namespace tsidb

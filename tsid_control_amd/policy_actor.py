@@ -70,7 +70,7 @@ class _Net:
             inputs = (inputs,)
         if not 1 <= len(inputs) <= _lib.POL_NET_MAXBLOCKS:
             raise _bad(f"{name}_inputs: 1 .. {_lib.POL_NET_MAXBLOCKS} blocks, got {len(inputs)}")
-        self.blocks = []
+        self.blocks, self.block_names = [], [b if isinstance(b, str) else None for b in inputs]   # (the names: PolicySymmetry's tables)
         for b in inputs:
             if isinstance(b, str):
                 if b not in _INPUT_NAMES:

@@ -51,12 +51,17 @@ class PolicyLearner:
     entropy + imitation_coef L_im, so surrogate_coef = value_coef = entropy_coef = 0 is pure distillation (rsl_rl's Distillation)
     and the defaults are PPO as it is, with the calls it made before the term existed.  imit_stats [4] float32
     (_lib.POL_IMIT_STATS): L_im, the sum of the weights, the rows with a weight, the rows whose surrogate was skipped.
+    symmetry: a PolicySymmetry of the actor (policy_symmetry.py; None = none, the calls and the bits as ever) - backward() goes
+    through tsidb_policy_learn_sym (include/tsidb.h).  symmetry_augment: every row also counts as its mirror image (rsl_rl's
+    use_data_augmentation); mirror_coef (>= 0): the weight of L_sym = mean |mu(S_o x) - S_a mu(x)|^2 (rsl_rl's mirror loss).
+    sym_stats [2] float32 (_lib.POL_SYM_STATS): L_sym - formed at mirror_coef = 0 too - and the mirrored rows used.  Not with
+    the imitation term.
 
     Tensors: stats [8] float32, written by backward() - policy_loss, value_loss, entropy, approx_kl, clip_fraction, loss, rows,
     bad_indices (_lib.POL_LEARN_STATS); adv_stats [2] (mean, 1 / std); workspace (grown to the largest minibatch seen)."""
 
     def __init__(self, actor, clip=0.2, value_coef=1.0, entropy_coef=0.0, value_clip=True, normalize_advantage=True, imitation_coef=0.0,
-                 imitation_loss="mse", surrogate_coef=1.0):
+                 imitation_loss="mse", surrogate_coef=1.0, symmetry=None, symmetry_augment=True, mirror_coef=0.0):
         if not isinstance(actor, PolicyActor):
             raise _bad(f"actor must be a PolicyActor, got {type(actor).__name__}")
         self.actor, self.env = actor, actor.env
@@ -70,12 +75,41 @@ class PolicyLearner:
         if imitation_loss not in _lib.POL_IMIT_LOSSES:
             raise _bad(f"imitation_loss must be one of {_lib.POL_IMIT_LOSSES}, got {imitation_loss!r}")
         self.imitation_loss = imitation_loss
+        self.symmetry, self.mirror_coef = symmetry, _number("mirror_coef", mirror_coef, 0.0)
+        if not isinstance(symmetry_augment, bool):
+            raise _bad(f"symmetry_augment must be a bool, got {symmetry_augment!r}")
+        self.symmetry_augment = symmetry_augment
+        if symmetry is not None:
+            self._check_symmetry(symmetry)
+        elif self.mirror_coef != 0.0:
+            raise _bad("mirror_coef needs a symmetry")
         dev = self.env.wc.device
         self.stats = torch.zeros(len(_lib.POL_LEARN_STATS), dtype=torch.float32, device=dev)
         self.adv_stats = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
         self.imit_stats = torch.zeros(len(_lib.POL_IMIT_STATS), dtype=torch.float32, device=dev)
+        self.sym_stats = torch.zeros(len(_lib.POL_SYM_STATS), dtype=torch.float32, device=dev) if symmetry is not None else None
         self.workspace, self._ws_rows = None, 0
         self._cfg = _lib.PolicyLearnCfg(self.clip, self.value_coef, self.entropy_coef, int(value_clip))
+
+    def _check_symmetry(self, sym):
+        """the tables before they reach the library: of this actor, on the device, every perm inside its row"""
+        from .policy_symmetry import PolicySymmetry
+        a, dev = self.actor, self.env.wc.device
+        if not isinstance(sym, PolicySymmetry) or sym.actor is not a:
+            raise _bad("symmetry must be a PolicySymmetry of this learner's actor")
+        if self._imit_on:
+            raise _bad("a symmetry with the imitation term (imitation_coef != 0 or surrogate_coef != 1) is not supported")
+        if a.normalizer is not None:
+            raise _bad("a symmetry with a PolicyNormalizer is not supported")
+        sizes = [("actor", sym.actor_perm, sym.actor_sign, a.actor_net.K), ("action", sym.action_perm, sym.action_sign, self.env.NA)]
+        if a.critic_net is not None:
+            sizes.append(("critic", sym.critic_perm, sym.critic_sign, a.critic_net.K))
+        for name, perm, sign, k in sizes:
+            for t, dt in ((perm, torch.int32), (sign, torch.float32)):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (k,) or t.device != dev or not t.is_contiguous():
+                    raise _bad(f"symmetry: the {name} table must be contiguous [{k}] int32 and float32 tensors on {dev}")
+            if int(perm.min()) < 0 or int(perm.max()) >= k:
+                raise _bad(f"symmetry: the {name} perm must stay inside [0, {k})")
 
     @property
     def _imit_on(self):
@@ -108,7 +142,9 @@ class PolicyLearner:
         if self.workspace is None or M > self._ws_rows:
             wc, a = self.env.wc, self.actor
             n = C.c_size_t(0)
-            wc._call("tsidb_policy_learn_imit_workspace" if self._imit_on else "tsidb_policy_learn_workspace", C.byref(a.actor_net.struct),
+            query = "tsidb_policy_learn_sym_workspace" if self.symmetry is not None else \
+                "tsidb_policy_learn_imit_workspace" if self._imit_on else "tsidb_policy_learn_workspace"
+            wc._call(query, C.byref(a.actor_net.struct),
                      C.byref(a.critic_net.struct) if a.critic_net is not None else None, M, C.byref(n))
             self.workspace = torch.empty(max(1, (n.value + 3) // 4), dtype=torch.float32, device=wc.device)
             self._ws_rows, self._ws_bytes = M, n.value
@@ -156,6 +192,13 @@ class PolicyLearner:
                 C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()), C.c_void_p(self._grad(a.log_std).data_ptr()),
                 C.byref(self._cfg))
         tail = (C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel() * 4), C.c_void_p(stats.data_ptr()), wc._stream())
+        if self.symmetry is not None:
+            sy, q = self.symmetry, lambda t: t.data_ptr() if t is not None else None
+            tables = _lib.PolicySymmetryTables(q(sy.actor_perm), q(sy.actor_sign), q(sy.critic_perm), q(sy.critic_sign), q(sy.action_perm),
+                                               q(sy.action_sign), int(self.symmetry_augment), self.mirror_coef, q(self.sym_stats))
+            self._last_sym = tables        # (alive until the next call, as the batch)
+            wc._call("tsidb_policy_learn_sym", *head, C.byref(tables), *tail)
+            return stats
         if not self._imit_on:
             wc._call("tsidb_policy_learn", *head, *tail)
             return stats
@@ -167,10 +210,11 @@ class PolicyLearner:
 
     def outputs(self, M):
         """(mu [M, NA], v [M] or None): the actor's and the critic's outputs on the rows of the last backward() of M rows, views
-        of the workspace (include/tsidb.h: its first floats)"""
+        of the workspace (include/tsidb.h: its first floats; with a symmetry the arrays hold 2 Mp rows, the originals first)"""
         Mp, NA = (M + 15) // 16 * 16, self.env.NA
         mu = self.workspace[:Mp * NA].view(Mp, NA)[:M]
-        return mu, (self.workspace[Mp * NA:Mp * NA + M] if self.actor.critic_net is not None else None)
+        v0 = (2 * Mp if self.symmetry is not None else Mp) * NA
+        return mu, (self.workspace[v0:v0 + M] if self.actor.critic_net is not None else None)
 
     def update(self, storage, optimizer, epochs=5, minibatches=4, generator=None):
         """One PPO update on a storage whose gae() has run: per epoch a torch.randperm(T * N) on the device (generator: a
@@ -200,4 +244,4 @@ class PolicyLearner:
     def written(self):
         """the tensors backward() writes: what a caller that captures it in a graph keeps alive (imit_stats while the imitation
         term or a surrogate_coef is on: the plain call does not write it)"""
-        return [self._grad(p) for p in self.parameters()] + [self.stats, self.adv_stats] + ([self.imit_stats] if self._imit_on else []) + ([self.workspace] if self.workspace is not None else [])
+        return [self._grad(p) for p in self.parameters()] + [self.stats, self.adv_stats] + ([self.imit_stats] if self._imit_on else []) + ([self.sym_stats] if self.symmetry is not None else []) + ([self.workspace] if self.workspace is not None else [])
