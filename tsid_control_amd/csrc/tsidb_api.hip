@@ -10,6 +10,8 @@
 #include "tsidb_norm.hpp"
 #include "tsidb_optim.hpp"
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -736,11 +738,7 @@ struct tsidb_ctx {
   double teach[TSIDB_POL_TEACH_NPARAMS] = {};
   bool ep_set = false;                       // tsidb_policy_episode_config: episode statistics, the terrain curriculum
   double pol_ep[TSIDB_POL_EPP_NPARAMS] = {};
-  bool learn_big_lds = false;                // tsidb_policy_learn: k_policy_learn_rows' likewise
-  bool learn_imit_big_lds = false;           // tsidb_policy_learn_imit: k_policy_learn_rows_imit's likewise
-  bool learn_sym_big_lds = false;            // tsidb_policy_learn_sym: k_policy_learn_rows_sym's likewise
-  bool actor_norm_big_lds = false;           // tsidb_policy_actor_norm: k_policy_actor_norm's likewise
-  bool actor_big_lds = false;                // tsidb_policy_actor: k_policy_actor's dynamic LDS limit has been raised above 64 KB
+  std::vector<const void *> big_lds;         // the kernels whose dynamic LDS limit has been raised above 64 KB (allow_dynamic_lds)
   std::string err;
 };
 
@@ -1281,21 +1279,63 @@ static bool whole_below(const double *p, std::initializer_list<int> slots, doubl
   return true;
 }
 
-// The frame of every tsidb_policy_* launch: the guard, the path's type T, what policy_bufs checks, then body(T(), b, launch)
-// with the entry's own checks.  launch(kernel, args...) puts the kernel on the stream with the policy grid and block; a body
-// that returns without calling it launches nothing.
+// The frame of every entry that launches on the caller's stream: the guard, then body(launch) with the entry's checks.
+// launch(kernel, grid, block, lds, args...) notes the stream and puts the kernel on it; a body that returns without calling it
+// launches nothing.
 template <typename Body>
-static int policy_call(tsidb_ctx *h, const tsidb_policy_bufs *bufs, const char *who, void *stream, Body body) {
+static int stream_call(tsidb_ctx *h, void *stream, Body body) {
   GUARD_BEGIN
   hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
-    const auto b = policy_bufs<decltype(t)>(h, bufs, who);
-    body(t, b, [&](auto kernel, auto... args) {
-      h->note_stream(s);
-      hipLaunchKernelGGL(kernel, dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s, args...);
-    });
+  body([&](auto kernel, dim3 grid, dim3 block, size_t lds, auto... args) {
+    h->note_stream(s);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
   });
   HIP_OK(hipGetLastError());
+  GUARD_END
+}
+
+// The frame of every tsidb_policy_* launch over the envs: stream_call's, the path's type T, then body(T(), launch) with
+// launch(kernel, args...) on the policy grid and block
+template <typename Body>
+static int policy_call(tsidb_ctx *h, void *stream, Body body) {
+  return stream_call(h, stream, [&](auto launch) {
+    with_dtype(h->dtype, [&](auto t) {
+      body(t, [&](auto kernel, auto... args) {
+        launch(kernel, dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, args...);
+      });
+    });
+  });
+}
+
+// ... with what policy_bufs checks first: body(T(), b, launch)
+template <typename Body>
+static int policy_call(tsidb_ctx *h, const tsidb_policy_bufs *bufs, const char *who, void *stream, Body body) {
+  return policy_call(h, stream, [&](auto t, auto launch) { body(t, policy_bufs<decltype(t)>(h, bufs, who), launch); });
+}
+
+// The frame of a tsidb_policy_*_config entry: the guard; a library without the sim stage refuses; `params` is N finite numbers
+// (`needs`: the message if not; optional: NULL, 0 switches the slice off and stores zeros; negative: the message for a number
+// below 0, where none may be); checks(p) with the entry's own; then, behind the handle's kernels in flight, p goes to the
+// handle's member dest and its member set (if any) says whether the slice is on.
+template <size_t N, typename Checks>
+static int store_params(tsidb_ctx *h, const char *who, const double *params, int n, const char *needs, double (tsidb_ctx::*dest)[N],
+                        bool tsidb_ctx::*set, bool optional, const char *negative, Checks checks) {
+  GUARD_BEGIN
+  if (lacks_sim(h, true, who)) throw h->err;
+  double p[N] = {};
+  const bool on = !optional || params || n;
+  if (on) {
+    if (!params || n != (int)N) throw std::string(who) + needs;
+    for (int i = 0; i < n; i++) {
+      if (!std::isfinite(params[i])) throw std::string(who) + "non-finite parameter";
+      if (negative && params[i] < 0) throw std::string(who) + negative;
+      p[i] = params[i];
+    }
+    checks(p);
+  }
+  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
+  memcpy(h->*dest, p, sizeof p);
+  if (set) h->*set = on;
   GUARD_END
 }
 
@@ -1303,27 +1343,24 @@ extern "C" {
 
 int tsidb_policy_config(tsidb_handle h, const double *pol_params, int n_params, const double *scale, const double *default_pos,
                         uint32_t term_body_mask) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_config: ";
-  if (lacks_sim(h, true, who)) throw h->err;
-  if (!pol_params || n_params != TSIDB_POL_NPARAMS || !scale || !default_pos) throw std::string(who) + "needs TSIDB_POL_NPARAMS parameters, scale [NA] and default_pos [NA]";
-  for (int i = 0; i < n_params; i++) if (!std::isfinite(pol_params[i])) throw std::string(who) + "non-finite parameter";
-  for (int a = 0; a < NA; a++) if (!std::isfinite(scale[a]) || !std::isfinite(default_pos[a])) throw std::string(who) + "non-finite scale or default position";
-  const double *p = pol_params;
-  if (p[TSIDB_POL_P_CLIP] < 0) throw std::string(who) + "clip must be >= 0";
-  if (!(p[TSIDB_POL_P_ALPHA] > 0 && p[TSIDB_POL_P_ALPHA] <= 1)) throw std::string(who) + "alpha must be in (0, 1]";
-  if (!(p[TSIDB_POL_P_SIGMA] > 0)) throw std::string(who) + "sigma must be positive";
-  if (p[TSIDB_POL_P_DECIMATION] < 1 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] < 0 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] > 2147483647.0 || p[TSIDB_POL_P_SEED] < 0)
-    throw std::string(who) + "decimation must be >= 1, max_episode_steps 0 .. 2^31 - 1, seed >= 0";
-  for (int i = 0; i < 3; i++) if (p[TSIDB_POL_P_CMD_LO + i] > p[TSIDB_POL_P_CMD_HI + i]) throw std::string(who) + "command range: lo > hi";
-  if (NB < 32 && (term_body_mask >> NB)) throw std::string(who) + "term_body_mask names a body the robot does not have";
-  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
-  memcpy(h->pol, pol_params, sizeof h->pol);
+  // (without scale or default_pos the parameters count as missing: one message for the three)
+  const int rc = store_params(h, who, scale && default_pos ? pol_params : nullptr, n_params, "needs TSIDB_POL_NPARAMS parameters, scale [NA] and default_pos [NA]",
+                              &tsidb_ctx::pol, &tsidb_ctx::pol_set, false, nullptr, [&](const double *p) {
+    for (int a = 0; a < NA; a++) if (!std::isfinite(scale[a]) || !std::isfinite(default_pos[a])) throw std::string(who) + "non-finite scale or default position";
+    if (p[TSIDB_POL_P_CLIP] < 0) throw std::string(who) + "clip must be >= 0";
+    if (!(p[TSIDB_POL_P_ALPHA] > 0 && p[TSIDB_POL_P_ALPHA] <= 1)) throw std::string(who) + "alpha must be in (0, 1]";
+    if (!(p[TSIDB_POL_P_SIGMA] > 0)) throw std::string(who) + "sigma must be positive";
+    if (p[TSIDB_POL_P_DECIMATION] < 1 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] < 0 || p[TSIDB_POL_P_MAX_EPISODE_STEPS] > 2147483647.0 || p[TSIDB_POL_P_SEED] < 0)
+      throw std::string(who) + "decimation must be >= 1, max_episode_steps 0 .. 2^31 - 1, seed >= 0";
+    for (int i = 0; i < 3; i++) if (p[TSIDB_POL_P_CMD_LO + i] > p[TSIDB_POL_P_CMD_HI + i]) throw std::string(who) + "command range: lo > hi";
+    if (NB < 32 && (term_body_mask >> NB)) throw std::string(who) + "term_body_mask names a body the robot does not have";
+  });
+  if (rc) return rc;
   memcpy(h->pol_scale, scale, sizeof h->pol_scale);
   memcpy(h->pol_def, default_pos, sizeof h->pol_def);
   h->pol_mask = term_body_mask;
-  h->pol_set = true;
-  GUARD_END
+  return 0;
 }
 
 int tsidb_policy_act(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *action, void *stream) {
@@ -1358,17 +1395,9 @@ int tsidb_policy_obs(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *
 }
 
 int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_randomize: ";
-  if (lacks_sim(h, true, who)) throw h->err;
-  double p[TSIDB_POL_DR_NPARAMS] = {};
-  if (dr_params || n_params) {
-    if (!dr_params || n_params != TSIDB_POL_DR_NPARAMS) throw std::string(who) + "needs TSIDB_POL_DR_NPARAMS parameters (or NULL, 0: everything off)";
-    for (int i = 0; i < n_params; i++) {
-      if (!std::isfinite(dr_params[i])) throw std::string(who) + "non-finite parameter";
-      if (dr_params[i] < 0) throw std::string(who) + "negative parameter (amplitudes, forces, intervals, seed, offset and probability are all >= 0)";
-      p[i] = dr_params[i];
-    }
+  return store_params(h, who, dr_params, n_params, "needs TSIDB_POL_DR_NPARAMS parameters (or NULL, 0: everything off)", &tsidb_ctx::pol_dr, nullptr, true,
+                      "negative parameter (amplitudes, forces, intervals, seed, offset and probability are all >= 0)", [&](const double *p) {
     if (!whole_below(p, {TSIDB_POL_DR_SEED, TSIDB_POL_DR_ENV_OFFSET, TSIDB_POL_DR_PUSH_INTERVAL, TSIDB_POL_DR_PUSH_DURATION, TSIDB_POL_DR_COMMAND_INTERVAL}))
       throw std::string(who) + "seed, env_offset and the intervals must be whole numbers";
     if (!whole_below(p, {TSIDB_POL_DR_SEED}, 4294967296.0)) throw std::string(who) + "seed must be below 2^32";
@@ -1377,10 +1406,7 @@ int tsidb_policy_randomize(tsidb_handle h, const double *dr_params, int n_params
     if (p[TSIDB_POL_DR_PUSH_DURATION] > p[TSIDB_POL_DR_PUSH_INTERVAL]) throw std::string(who) + "push_duration > push_interval";
     if (p[TSIDB_POL_DR_PUSH_FORCE_LO] > p[TSIDB_POL_DR_PUSH_FORCE_HI]) throw std::string(who) + "push_force_lo > push_force_hi";
     if (p[TSIDB_POL_DR_COMMAND_ZERO_PROB] > 1) throw std::string(who) + "command_zero_prob must be in [0, 1]";
-  }
-  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
-  memcpy(h->pol_dr, p, sizeof h->pol_dr);
-  GUARD_END
+  });
 }
 
 int tsidb_policy_perturb(tsidb_handle h, const tsidb_policy_bufs *bufs, void *stream) {
@@ -1405,17 +1431,9 @@ int tsidb_policy_reset_noise(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
 }
 
 int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_params) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_terrain_config: ";
-  if (lacks_sim(h, true, who)) throw h->err;
-  double p[TSIDB_POL_TER_NPARAMS] = {};
-  const bool on = ter_params || n_params;
-  if (on) {
-    if (!ter_params || n_params != TSIDB_POL_TER_NPARAMS) throw std::string(who) + "needs TSIDB_POL_TER_NPARAMS parameters (or NULL, 0: everything off)";
-    for (int i = 0; i < n_params; i++) {
-      if (!std::isfinite(ter_params[i])) throw std::string(who) + "non-finite parameter";
-      p[i] = ter_params[i];
-    }
+  return store_params(h, who, ter_params, n_params, "needs TSIDB_POL_TER_NPARAMS parameters (or NULL, 0: everything off)", &tsidb_ctx::pol_ter,
+                      &tsidb_ctx::ter_set, true, nullptr, [&](const double *p) {
     if (!whole_below(p, {TSIDB_POL_TER_SEED, TSIDB_POL_TER_ENV_OFFSET, TSIDB_POL_TER_FLAT_CELLS, TSIDB_POL_TER_NUM_LEVELS, TSIDB_POL_TER_SCAN_NX, TSIDB_POL_TER_SCAN_NY}))
       throw std::string(who) + "seed, env_offset, flat_cells, num_levels, scan_nx and scan_ny must be whole numbers >= 0";
     if (!whole_below(p, {TSIDB_POL_TER_SEED}, 4294967296.0)) throw std::string(who) + "seed must be below 2^32";
@@ -1434,11 +1452,7 @@ int tsidb_policy_terrain_config(tsidb_handle h, const double *ter_params, int n_
     if ((nx == 0) != (ny == 0)) throw std::string(who) + "scan_nx and scan_ny must both be 0 (no scan) or both positive";
     if (p[TSIDB_POL_TER_SCAN_CLIP_LO] > p[TSIDB_POL_TER_SCAN_CLIP_HI]) throw std::string(who) + "scan clip_lo > clip_hi";
     if (p[TSIDB_POL_TER_SCAN_NOISE] < 0) throw std::string(who) + "scan_noise must be >= 0";
-  }
-  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
-  memcpy(h->pol_ter, p, sizeof h->pol_ter);
-  h->ter_set = on;
-  GUARD_END
+  });
 }
 
 int tsidb_policy_terrain_reset(tsidb_handle h, const tsidb_policy_bufs *bufs, const void *done_rows, int rows_ld, const void *qpos,
@@ -1469,16 +1483,11 @@ int tsidb_policy_height_scan(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
 }
 
 int tsidb_policy_teacher_config(tsidb_handle h, const double *teach_params, int n_params) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_teacher_config: ";
-  if (lacks_sim(h, true, who)) throw h->err;
-  if (!teach_params || n_params != TSIDB_POL_TEACH_NPARAMS) throw std::string(who) + "needs TSIDB_POL_TEACH_NPARAMS parameters";
-  for (int i = 0; i < n_params; i++) if (!std::isfinite(teach_params[i])) throw std::string(who) + "non-finite parameter";
-  if (!(teach_params[TSIDB_POL_TEACH_SIGMA_COM] > 0) || !(teach_params[TSIDB_POL_TEACH_SIGMA_FOOT] > 0)) throw std::string(who) + "sigma_com and sigma_foot must be positive";
-  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
-  memcpy(h->teach, teach_params, sizeof h->teach);
-  h->teach_set = true;
-  GUARD_END
+  return store_params(h, who, teach_params, n_params, "needs TSIDB_POL_TEACH_NPARAMS parameters", &tsidb_ctx::teach, &tsidb_ctx::teach_set, false, nullptr,
+                      [&](const double *p) {
+    if (!(p[TSIDB_POL_TEACH_SIGMA_COM] > 0) || !(p[TSIDB_POL_TEACH_SIGMA_FOOT] > 0)) throw std::string(who) + "sigma_com and sigma_foot must be positive";
+  });
 }
 
 int tsidb_policy_teacher(tsidb_handle h, const tsidb_policy_bufs *bufs, void *rows, int rows_ld, const void *q, const void *tau,
@@ -1522,26 +1531,14 @@ int tsidb_policy_teacher_mix(tsidb_handle h, const tsidb_policy_bufs *bufs, cons
 }
 
 int tsidb_policy_episode_config(tsidb_handle h, const double *ep_params, int n_params) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_episode_config: ";
-  if (lacks_sim(h, true, who)) throw h->err;
-  double p[TSIDB_POL_EPP_NPARAMS] = {};
-  const bool on = ep_params || n_params;
-  if (on) {
-    if (!ep_params || n_params != TSIDB_POL_EPP_NPARAMS) throw std::string(who) + "needs TSIDB_POL_EPP_NPARAMS parameters (or NULL, 0: the slice off)";
-    for (int i = 0; i < n_params; i++) {
-      if (!std::isfinite(ep_params[i])) throw std::string(who) + "non-finite parameter";
-      p[i] = ep_params[i];
-    }
+  return store_params(h, who, ep_params, n_params, "needs TSIDB_POL_EPP_NPARAMS parameters (or NULL, 0: the slice off)", &tsidb_ctx::pol_ep,
+                      &tsidb_ctx::ep_set, true, nullptr, [&](const double *p) {
     for (int i : {(int)TSIDB_POL_EPP_CURRICULUM, (int)TSIDB_POL_EPP_RANDOM_TOP})
       if (p[i] != 0 && p[i] != 1) throw std::string(who) + "curriculum and random_top are flags: 0 or 1";
     if (p[TSIDB_POL_EPP_CURRICULUM] == 1 && !(p[TSIDB_POL_EPP_UP_DISTANCE] > 0)) throw std::string(who) + "up_distance must be positive with the curriculum on";
     if (p[TSIDB_POL_EPP_DOWN_FRACTION] < 0) throw std::string(who) + "down_fraction must be >= 0";
-  }
-  wait_for_own_streams(h); // (kernels in flight were launched with the old values)
-  memcpy(h->pol_ep, p, sizeof h->pol_ep);
-  h->ep_set = on;
-  GUARD_END
+  });
 }
 
 int tsidb_policy_episode_end(tsidb_handle h, const tsidb_policy_bufs *bufs, const tsidb_policy_episode *ep, const void *qpos, const void *reward,
@@ -1579,11 +1576,11 @@ int tsidb_policy_episode_begin(tsidb_handle h, const tsidb_policy_bufs *bufs, co
   });
 }
 
-// (no tsidb_policy_bufs: the sources are whatever the caller names, so the frame is the guard's, not policy_call's)
+// (no tsidb_policy_bufs: the sources are whatever the caller names)
 int tsidb_policy_obs_history(tsidb_handle h, const struct tsidb_policy_obs_history *hist, const void *done_rows, int rows_ld, int push,
                              void *stream) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_obs_history: ";
+  return policy_call(h, stream, [&](auto t, auto launch) {
   static_assert(TSIDB_POL_OBSH_MAXSRC == POL_OBSH_MAXSRC && TSIDB_POL_OBSH_MAXFRAMES == POL_OBSH_MAXFRAMES && TSIDB_POL_OBSH_MAXCOLS == POL_OBSH_MAXCOLS);
   if (!hist || !hist->history) throw std::string(who) + "null struct tsidb_policy_obs_history or history buffer";
   if (hist->frames < 1 || hist->frames > POL_OBSH_MAXFRAMES) throw std::string(who) + "frames must be 1 .. TSIDB_POL_OBSH_MAXFRAMES";
@@ -1598,48 +1595,78 @@ int tsidb_policy_obs_history(tsidb_handle h, const struct tsidb_policy_obs_histo
   if (hist->frames * K > POL_OBSH_MAXCOLS) throw std::string(who) + "frames * K exceeds TSIDB_POL_OBSH_MAXCOLS";
   need_rows(who, done_rows, rows_ld);
   if (push != 0 && push != 1) throw std::string(who) + "push is a flag: 0 or 1";
-  hipStream_t s = (hipStream_t)stream;
-  with_dtype(h->dtype, [&](auto t) {
-    using T = decltype(t);
-    PolicyObsHistory<T> a = {};
-    a.history = (T *)hist->history; a.frames = hist->frames; a.n_src = hist->n_src; a.K = K;
-    for (int i = 0; i < hist->n_src; i++) { a.src[i] = (const T *)hist->src[i]; a.src_ld[i] = hist->src_ld[i]; a.src_cols[i] = hist->src_cols[i]; }
-    h->note_stream(s);
-    hipLaunchKernelGGL(k_policy_obs_history<T>, dim3((h->num_envs + POL_ENVS_PER_BLOCK - 1) / POL_ENVS_PER_BLOCK), dim3(WAVE * POL_ENVS_PER_BLOCK), 0, s,
-                       h->num_envs, a, (const T *)done_rows, rows_ld, push);
+  using T = decltype(t);
+  PolicyObsHistory<T> a = {};
+  a.history = (T *)hist->history; a.frames = hist->frames; a.n_src = hist->n_src; a.K = K;
+  for (int i = 0; i < hist->n_src; i++) { a.src[i] = (const T *)hist->src[i]; a.src_ld[i] = hist->src_ld[i]; a.src_cols[i] = hist->src_cols[i]; }
+  launch(k_policy_obs_history<T>, h->num_envs, a, (const T *)done_rows, rows_ld, push);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 } // extern "C"
 
-// tsidb_policy_net as the kernel takes it, checked; `name` = "actor" / "critic", last = the width its last layer must have
-static ActorNet actor_net(const tsidb_policy_net *p, const char *who, const char *name, int last, const char *last_name, float *input) {
-  const std::string pre = std::string(who) + name + ": ";
-  if (p->n_layers < 1 || p->n_layers > ACT_MAXL) throw pre + "n_layers must be 1 .. 4";
+// The checks of a tsidb_policy_net, in the order they fire; pre = "<entry>: <actor | critic>: ".  First the counts (whole =
+// false: the block count alone, for an entry that reads nothing else of the struct)
+static void net_counts(const tsidb_policy_net *p, const std::string &pre, bool whole = true) {
+  if (whole && (p->n_layers < 1 || p->n_layers > ACT_MAXL)) throw pre + "n_layers must be 1 .. 4";
   if (p->n_blocks < 1 || p->n_blocks > ACT_MAXB) throw pre + "n_blocks must be 1 .. 4";
-  if (p->activation != ACT_ELU && p->activation != ACT_TANH && p->activation != ACT_RELU)
+  if (whole && p->activation != ACT_ELU && p->activation != ACT_TANH && p->activation != ACT_RELU)
     throw pre + "unknown activation (TSIDB_POL_ACT_ELU, _TANH or _RELU)";
-  ActorNet n = {};
-  n.n_layers = p->n_layers; n.n_blocks = p->n_blocks; n.activation = p->activation; n.input = input;
+}
+
+// ... then the input blocks, copied to blk, blk_ld and blk_cols; returns K, the columns in total.  blk = NULL: the column
+// counts alone (the learner's rows are the batch's: it reads no block pointer or stride)
+static int net_blocks(const tsidb_policy_net *p, const std::string &pre, const void **blk, int *blk_ld, int *blk_cols) {
   long total = 0;
   for (int i = 0; i < p->n_blocks; i++) {
-    if (!p->block[i]) throw pre + "null input block";
+    if (blk && !p->block[i]) throw pre + "null input block";
     if (p->block_cols[i] < 1 || p->block_cols[i] > ACT_MAXW) throw pre + "block_cols must be 1 .. 512";
-    if (p->block_ld[i] < p->block_cols[i]) throw pre + "block_ld < block_cols";
-    n.blk[i] = p->block[i]; n.blk_ld[i] = p->block_ld[i]; n.blk_cols[i] = p->block_cols[i];
+    if (blk && p->block_ld[i] < p->block_cols[i]) throw pre + "block_ld < block_cols";
+    if (blk) { blk[i] = p->block[i]; blk_ld[i] = p->block_ld[i]; }
+    blk_cols[i] = p->block_cols[i];
     total += p->block_cols[i];
   }
   if (total < 1 || total > ACT_MAXW) throw pre + "the input blocks must hold 1 .. 512 columns in total";
-  n.K = (int)total;
+  return (int)total;
+}
+
+// ... then the layers, copied to n; last = the width the last layer must have
+static void net_layers(const tsidb_policy_net *p, const std::string &pre, int last, const char *last_name, ActorNet &n) {
+  n.n_layers = p->n_layers; n.activation = p->activation;
   for (int l = 0; l < p->n_layers; l++) {
     if (p->width[l] < 1 || p->width[l] > ACT_MAXW) throw pre + "width must be 1 .. 512";
     if (!p->weight[l]) throw pre + "null weight";
     n.width[l] = p->width[l]; n.W[l] = p->weight[l]; n.b[l] = p->bias[l];
   }
   if (p->width[p->n_layers - 1] != last) throw pre + "the last width must be " + last_name;
+}
+
+// tsidb_policy_net as the kernel takes it, checked; `name` = "actor" / "critic"
+static ActorNet actor_net(const tsidb_policy_net *p, const char *who, const char *name, int last, const char *last_name, float *input) {
+  const std::string pre = std::string(who) + name + ": ";
+  ActorNet n = {};
+  net_counts(p, pre);
+  n.n_blocks = p->n_blocks; n.input = input;
+  n.K = net_blocks(p, pre, n.blk, n.blk_ld, n.blk_cols);
+  net_layers(p, pre, last, last_name, n);
   return n;
+}
+
+// the widest row, input or layer, of a call's two networks (an absent one has K = 0 and no layers)
+static int widest_of(const ActorNet &a, const ActorNet &b) {
+  int widest = 0;
+  for (const ActorNet *n : {&a, &b}) {
+    if (n->K > widest) widest = n->K;
+    for (int l = 0; l < n->n_layers; l++) if (n->width[l] > widest) widest = n->width[l];
+  }
+  return widest;
+}
+
+// Dynamic LDS beyond the default 64 KB (rows wider than 480) has to be allowed per kernel: once per handle and kernel
+static void allow_dynamic_lds(tsidb_ctx *h, const void *kernel, size_t lds) {
+  if (lds <= 65536 || std::find(h->big_lds.begin(), h->big_lds.end(), kernel) != h->big_lds.end()) return;
+  HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
+  h->big_lds.push_back(kernel);
 }
 
 // tsidb_policy_actor and tsidb_policy_actor_norm: one body; without a normaliser the launch is k_policy_actor's, as ever
@@ -1647,8 +1674,7 @@ static int policy_actor_call(tsidb_handle h, const char *who, const tsidb_policy
                              const tsidb_policy_net *critic, const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm,
                              const tsidb_policy_actor_out *out, const void *log_std, uint64_t seed, uint64_t env_offset, int flags,
                              void *stream) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
+  return stream_call(h, stream, [&](auto launch) {
   if (!actor && !critic) throw std::string(who) + "null actor (only a call with a critic may leave it out)";
   if (!out) throw std::string(who) + "null out";
   ActorArgs a = {};
@@ -1662,12 +1688,7 @@ static int policy_actor_call(tsidb_handle h, const char *who, const tsidb_policy
     if (!log_std) throw std::string(who) + "sampling needs log_std";
     a.episode = bufs->episode; a.ep_len = bufs->ep_len;
   }
-  int widest = 0;
-  for (int y = 0; y < 2; y++) {
-    if (a.net[y].K > widest) widest = a.net[y].K;
-    for (int l = 0; l < a.net[y].n_layers; l++) if (a.net[y].width[l] > widest) widest = a.net[y].width[l];
-  }
-  a.n = h->num_envs; a.LD = act_ld(widest);
+  a.n = h->num_envs; a.LD = act_ld(widest_of(a.net[0], a.net[1]));
   a.action = out->action; a.action32 = out->action32; a.mean = out->mean; a.logp = out->logp; a.value = out->value;
   a.log_std = (const float *)log_std; a.seed = seed; a.env_offset = env_offset;
   ActorNorm nm = {};
@@ -1681,39 +1702,23 @@ static int policy_actor_call(tsidb_handle h, const char *who, const tsidb_policy
   }
   const bool normed = nm.affine[0] || nm.affine[1];
   const size_t lds = act_lds_bytes(a.LD);
-  const dim3 grid((h->num_envs + ACT_TILE - 1) / ACT_TILE, actor && critic ? 2 : 1);
+  const dim3 grid((h->num_envs + ACT_TILE - 1) / ACT_TILE, actor && critic ? 2 : 1), block(WAVE * ACT_WAVES);
   with_dtype(h->dtype, [&](auto t) {
     using T = decltype(t);
-    bool &big = normed ? h->actor_norm_big_lds : h->actor_big_lds;
-    if (lds > 65536 && !big) {   // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle and kernel)
-      const void *fn = normed ? reinterpret_cast<const void *>(&k_policy_actor_norm<T>) : reinterpret_cast<const void *>(&k_policy_actor<T>);
-      HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
-      big = true;
-    }
-    h->note_stream(s);
-    if (normed) hipLaunchKernelGGL(k_policy_actor_norm<T>, grid, dim3(WAVE * ACT_WAVES), lds, s, a, nm);
-    else hipLaunchKernelGGL(k_policy_actor<T>, grid, dim3(WAVE * ACT_WAVES), lds, s, a);
+    allow_dynamic_lds(h, normed ? (const void *)&k_policy_actor_norm<T> : (const void *)&k_policy_actor<T>, lds);
+    if (normed) launch(k_policy_actor_norm<T>, grid, block, lds, a, nm);
+    else launch(k_policy_actor<T>, grid, block, lds, a);
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
+  });
 }
 
 // the block fields of a network as the normaliser's update takes them: actor_net's checks of them, nothing else of the struct
 static NormNet norm_net(const tsidb_policy_net *p, const char *who, const char *name) {
   const std::string pre = std::string(who) + name + ": ";
-  if (p->n_blocks < 1 || p->n_blocks > ACT_MAXB) throw pre + "n_blocks must be 1 .. 4";
   NormNet n = {};
+  net_counts(p, pre, false);
   n.n_blocks = p->n_blocks;
-  long total = 0;
-  for (int i = 0; i < p->n_blocks; i++) {
-    if (!p->block[i]) throw pre + "null input block";
-    if (p->block_cols[i] < 1 || p->block_cols[i] > ACT_MAXW) throw pre + "block_cols must be 1 .. 512";
-    if (p->block_ld[i] < p->block_cols[i]) throw pre + "block_ld < block_cols";
-    n.blk[i] = p->block[i]; n.blk_ld[i] = p->block_ld[i]; n.blk_cols[i] = p->block_cols[i];
-    total += p->block_cols[i];
-  }
-  if (total < 1 || total > ACT_MAXW) throw pre + "the input blocks must hold 1 .. 512 columns in total";
-  n.K = (int)total;
+  n.K = net_blocks(p, pre, n.blk, n.blk_ld, n.blk_cols);
   return n;
 }
 
@@ -1750,9 +1755,8 @@ int tsidb_policy_norm_workspace(tsidb_handle h, const tsidb_policy_net *actor, c
 int tsidb_policy_norm_update(tsidb_handle h, const tsidb_policy_net *actor, const tsidb_policy_net *critic,
                              const tsidb_policy_norm *actor_norm, const tsidb_policy_norm *critic_norm, void *workspace,
                              size_t workspace_bytes, void *stream) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_norm_update: ";
-  hipStream_t s = (hipStream_t)stream;
+  return stream_call(h, stream, [&](auto launch) {
   if (!actor && !critic) throw std::string(who) + "null actor and critic";
   NormArgs a = {};
   a.n = h->num_envs; a.nseg = norm_segments(h->num_envs); a.first = actor ? 0 : 1;
@@ -1776,31 +1780,23 @@ int tsidb_policy_norm_update(tsidb_handle h, const tsidb_policy_net *actor, cons
   if (!workspace) throw std::string(who) + "null workspace";
   if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
   const int nets = actor && critic ? 2 : 1;
-  h->note_stream(s);
-  with_dtype(h->dtype, [&](auto t) {
-    using T = decltype(t);
-    hipLaunchKernelGGL(k_policy_norm_partial<T>, dim3((widest + 15) / 16, a.nseg, nets), dim3(256), 0, s, a);
+  with_dtype(h->dtype, [&](auto t) { launch(k_policy_norm_partial<decltype(t)>, dim3((widest + 15) / 16, a.nseg, nets), dim3(256), 0, a); });
+  launch(k_policy_norm_merge, dim3(1, nets), dim3(NORM_MERGE_LANES), 0, a);
   });
-  hipLaunchKernelGGL(k_policy_norm_merge, dim3(1, nets), dim3(NORM_MERGE_LANES), 0, s, a);
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done, const int32_t *timeout, const float *value,
                      float gamma, float lam, float *advantage, float *returns, void *stream) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_gae: ";
-  hipStream_t s = (hipStream_t)stream;
-  if (T < 1) throw std::string(who) + "T must be >= 1";
-  if (!reward || !done || !timeout || !value || !advantage || !returns) throw std::string(who) + "null buffer";
-  h->note_stream(s);
-  with_dtype(h->dtype, [&](auto t) {
-    using F = decltype(t);
-    hipLaunchKernelGGL(k_policy_gae<F>, dim3((h->num_envs + 255) / 256), dim3(256), 0, s, h->num_envs, T, (const F *)reward, (const F *)done,
-                       timeout, value, gamma, lam, advantage, returns);
+  return stream_call(h, stream, [&](auto launch) {
+    if (T < 1) throw std::string(who) + "T must be >= 1";
+    if (!reward || !done || !timeout || !value || !advantage || !returns) throw std::string(who) + "null buffer";
+    with_dtype(h->dtype, [&](auto t) {
+      using F = decltype(t);
+      launch(k_policy_gae<F>, dim3((h->num_envs + 255) / 256), dim3(256), 0, h->num_envs, T, (const F *)reward, (const F *)done, timeout, value, gamma,
+             lam, advantage, returns);
+    });
   });
-  HIP_OK(hipGetLastError());
-  GUARD_END
 }
 
 } // extern "C"
@@ -1808,14 +1804,33 @@ int tsidb_policy_gae(tsidb_handle h, int T, const void *reward, const void *done
 // tsidb_policy_net as the learner takes it: the actor's checks apart from the block pointers and strides; the input rows are
 // the batch's
 static LearnNet learn_net(const tsidb_policy_net *p, const char *who, const char *name, int last, const char *last_name) {
-  tsidb_policy_net q = *p;
-  static const float dummy = 0.f;
-  for (int i = 0; i < ACT_MAXB; i++) { q.block[i] = &dummy; q.block_ld[i] = ACT_MAXW; }   // (never read: only n_blocks and block_cols count)
+  const std::string pre = std::string(who) + name + ": ";
   LearnNet n = {};
-  n.net = actor_net(&q, who, name, last, last_name, nullptr);
-  n.net.n_blocks = 0;
-  for (int i = 0; i < ACT_MAXB; i++) n.net.blk[i] = nullptr;
+  net_counts(p, pre);
+  n.net.K = net_blocks(p, pre, nullptr, nullptr, n.net.blk_cols);
+  net_layers(p, pre, last, last_name, n.net);
   return n;
+}
+
+// both networks of a training call (no critic: net.n_layers = 0)
+static std::array<LearnNet, 2> learn_nets(const tsidb_policy_net *actor, const tsidb_policy_net *critic, const char *who) {
+  return {learn_net(actor, who, "actor", NA, "NA"), critic ? learn_net(critic, who, "critic", 1, "1") : LearnNet{}};
+}
+
+// The walk over (actor | critic) x layer of a training call's gradient pointers, checked: fn(W, dW, b, db), b and db NULL for a
+// layer without bias
+template <typename F>
+static void each_layer_grad(const char *who, const tsidb_policy_net *actor, const tsidb_policy_net *critic, const tsidb_policy_grads *actor_grads,
+                            const tsidb_policy_grads *critic_grads, const LearnNet *nets, F fn) {
+  for (int y = 0; y < 2; y++) {
+    const tsidb_policy_net *p = y ? critic : actor;
+    const tsidb_policy_grads *gr = y ? critic_grads : actor_grads;
+    for (int l = 0; l < nets[y].net.n_layers; l++) {
+      if (!gr->weight[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null weight gradient";
+      if (p->bias[l] && !gr->bias[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null bias gradient where the bias exists";
+      fn(p->weight[l], gr->weight[l], p->bias[l], p->bias[l] ? gr->bias[l] : nullptr);
+    }
+  }
 }
 
 // The workspace of a call, in floats: mu [Mp, NA], v [Mp]; per network the gathered rows, the hidden H_l and every G_l; the
@@ -1881,10 +1896,8 @@ static int learn_workspace_call(tsidb_handle h, const char *who, const tsidb_pol
   if (!bytes) throw std::string(who) + "null bytes";
   if (M < 1) throw std::string(who) + "M must be >= 1";
   if (sym && M > (1 << 29)) throw std::string(who) + "M is too large";
-  LearnNet nets[2] = {};
-  nets[0] = learn_net(actor, who, "actor", NA, "NA");
-  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
-  *bytes = learn_layout(nets, sym ? learn_sym_rows(M) : M, nullptr, nullptr, nullptr, nr) * sizeof(float);
+  auto nets = learn_nets(actor, critic, who);
+  *bytes = learn_layout(nets.data(), sym ? learn_sym_rows(M) : M, nullptr, nullptr, nullptr, nr) * sizeof(float);
   GUARD_END
 }
 
@@ -1894,8 +1907,7 @@ static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *a
                       const tsidb_policy_learn_batch *batch, const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads,
                       const float *log_std, float *log_std_grad, const tsidb_policy_learn_cfg *cfg, const tsidb_policy_imit *imit,
                       float *workspace, size_t workspace_bytes, float *stats, void *stream, const tsidb_policy_symmetry *sym = nullptr) {
-  GUARD_BEGIN
-  hipStream_t s = (hipStream_t)stream;
+  return stream_call(h, stream, [&](auto launch) {
   if (!actor) throw std::string(who) + "null actor";
   if (!batch) throw std::string(who) + "null batch";
   if (!actor_grads) throw std::string(who) + "null actor_grads";
@@ -1928,29 +1940,18 @@ static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *a
   }
   const int nr = imit ? LRN_NR + LRN_NI : sym ? LRN_NR + LRN_NS : LRN_NR;
   LearnArgs a = {};
-  a.net[0] = learn_net(actor, who, "actor", NA, "NA");
-  if (critic) a.net[1] = learn_net(critic, who, "critic", 1, "1");
+  const auto nets = learn_nets(actor, critic, who);
+  a.net[0] = nets[0]; a.net[1] = nets[1];
   WgradArgs w = {};
   ReduceArgs r = {};
   const size_t need = learn_layout(a.net, sym ? learn_sym_rows(batch->M) : batch->M, &w, &r, &a.r, nr) * sizeof(float);
   if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
-  int np = 0, widest = 0;
-  for (int y = 0; y < 2; y++) {
-    const tsidb_policy_net *p = y ? critic : actor;
-    const tsidb_policy_grads *gr = y ? critic_grads : actor_grads;
-    const ActorNet &n = a.net[y].net;
-    if (n.K > widest) widest = n.K;
-    for (int l = 0; l < n.n_layers; l++) {
-      if (n.width[l] > widest) widest = n.width[l];
-      if (!gr->weight[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null weight gradient";
-      if (p->bias[l] && !gr->bias[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null bias gradient where the bias exists";
-      r.piece[np].dW = gr->weight[l];
-      r.piece[np].db = p->bias[l] ? gr->bias[l] : nullptr;
-      np++;
-    }
-  }
+  int np = 0;
+  each_layer_grad(who, actor, critic, actor_grads, critic_grads, a.net, [&](const float *, float *dW, const float *, float *db) {
+    r.piece[np].dW = dW; r.piece[np++].db = db;
+  });
   a.net[0].in = batch->actor_input; a.net[1].in = batch->critic_input;
-  a.M = batch->M; a.rows = batch->rows; a.LD = act_ld(widest); a.value_clip = cfg->value_clip;
+  a.M = batch->M; a.rows = batch->rows; a.LD = act_ld(widest_of(a.net[0].net, a.net[1].net)); a.value_clip = cfg->value_clip;
   a.index = batch->index; a.action = batch->action; a.logp = batch->logp; a.value = batch->value; a.advantage = batch->advantage;
   a.returns = batch->returns; a.adv_stats = batch->adv_stats; a.log_std = log_std;
   a.clip = cfg->clip; a.value_coef = cfg->value_coef; a.ws = workspace;
@@ -1958,39 +1959,27 @@ static int learn_call(tsidb_handle h, const char *who, const tsidb_policy_net *a
   r.ws = workspace; r.log_std = log_std; r.log_std_grad = log_std_grad; r.stats = stats;
   r.value_coef = cfg->value_coef; r.entropy_coef = cfg->entropy_coef;
   const size_t lds = act_lds_bytes(a.LD);
-  bool &big = imit ? h->learn_imit_big_lds : sym ? h->learn_sym_big_lds : h->learn_big_lds;
-  if (lds > 65536 && !big) {     // (rows wider than 480: more than the default 64 KB of dynamic LDS; once per handle and kernel)
-    const void *fn = imit ? reinterpret_cast<const void *>(&k_policy_learn_rows_imit)
-                     : sym ? reinterpret_cast<const void *>(&k_policy_learn_rows_sym) : reinterpret_cast<const void *>(&k_policy_learn_rows);
-    HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes(act_ld(ACT_MAXW))));
-    big = true;
-  }
-  h->note_stream(s);
+  allow_dynamic_lds(h, imit ? (const void *)&k_policy_learn_rows_imit : sym ? (const void *)&k_policy_learn_rows_sym : (const void *)&k_policy_learn_rows, lds);
   const int tiles = sym ? w.Mp / (2 * ACT_TILE) : w.Mp / ACT_TILE;     // (sym: a workgroup runs its tile and the tile's mirror)
-  const dim3 rows_grid(tiles, critic ? 2 : 1), reduce_grid((unsigned)((r.rp + NA + (imit ? LRN_NI : sym ? LRN_NS : 1) + 255) / 256));
+  const dim3 rows_grid(tiles, critic ? 2 : 1), rows_block(WAVE * ACT_WAVES);
+  const dim3 reduce_grid((unsigned)((r.rp + NA + (imit ? LRN_NI : sym ? LRN_NS : 1) + 255) / 256));
+  const int augment = sym && sym->augment != 0;
   if (sym) {
-    const int augment = sym->augment != 0;
-    const LearnSym ls = {{sym->actor_perm, sym->critic_perm}, {sym->actor_sign, sym->critic_sign}, sym->action_perm, sym->action_sign,
-                         augment, w.Mp / 2, sym->mirror_coef};
-    const ReduceSym rs = {sym->mirror_coef, batch->M, sym->stats};
     r.M = augment ? 2 * batch->M : batch->M;                           // the rows the means are over
-    hipLaunchKernelGGL(k_policy_learn_rows_sym, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a, ls);
-    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
-    hipLaunchKernelGGL(k_policy_learn_reduce_sym, reduce_grid, dim3(256), 0, s, r, rs);
+    launch(k_policy_learn_rows_sym, rows_grid, rows_block, lds, a,
+           LearnSym{{sym->actor_perm, sym->critic_perm}, {sym->actor_sign, sym->critic_sign}, sym->action_perm, sym->action_sign, augment, w.Mp / 2,
+                    sym->mirror_coef});
   } else if (imit) {
-    const LearnImit li = {imit->target, imit->weight, imit->skip_surrogate, imit->imitation_coef, imit->surrogate_coef,
-                          imit->loss == TSIDB_POL_IMIT_HUBER};
-    const ReduceImit ri = {imit->imitation_coef, imit->surrogate_coef, imit->stats};
-    hipLaunchKernelGGL(k_policy_learn_rows_imit, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a, li);
-    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
-    hipLaunchKernelGGL(k_policy_learn_reduce_imit, reduce_grid, dim3(256), 0, s, r, ri);
+    launch(k_policy_learn_rows_imit, rows_grid, rows_block, lds, a,
+           LearnImit{imit->target, imit->weight, imit->skip_surrogate, imit->imitation_coef, imit->surrogate_coef, imit->loss == TSIDB_POL_IMIT_HUBER});
   } else {
-    hipLaunchKernelGGL(k_policy_learn_rows, rows_grid, dim3(WAVE * ACT_WAVES), lds, s, a);
-    hipLaunchKernelGGL(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, s, w);
-    hipLaunchKernelGGL(k_policy_learn_reduce, reduce_grid, dim3(256), 0, s, r);
+    launch(k_policy_learn_rows, rows_grid, rows_block, lds, a);
   }
-  HIP_OK(hipGetLastError());
-  GUARD_END
+  launch(k_policy_learn_wgrad, dim3(learn_blocks(w), r.nseg), dim3(WAVE), 0, w);
+  if (sym) launch(k_policy_learn_reduce_sym, reduce_grid, dim3(256), 0, r, ReduceSym{sym->mirror_coef, batch->M, sym->stats});
+  else if (imit) launch(k_policy_learn_reduce_imit, reduce_grid, dim3(256), 0, r, ReduceImit{imit->imitation_coef, imit->surrogate_coef, imit->stats});
+  else launch(k_policy_learn_reduce, reduce_grid, dim3(256), 0, r);
+  });
 }
 
 extern "C" {
@@ -2020,8 +2009,6 @@ int tsidb_policy_learn_sym(tsidb_handle h, const tsidb_policy_net *actor, const 
                            const tsidb_policy_grads *critic_grads, const float *log_std, float *log_std_grad,
                            const tsidb_policy_learn_cfg *cfg, const tsidb_policy_symmetry *sym, float *workspace, size_t workspace_bytes,
                            float *stats, void *stream) {
-  if (!sym) return learn_call(h, "tsidb_policy_learn_sym: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr,
-                              workspace, workspace_bytes, stats, stream);
   return learn_call(h, "tsidb_policy_learn_sym: ", actor, critic, batch, actor_grads, critic_grads, log_std, log_std_grad, cfg, nullptr, workspace,
                     workspace_bytes, stats, stream, sym);
 }
@@ -2072,12 +2059,9 @@ int tsidb_policy_opt_workspace(tsidb_handle h, const tsidb_policy_net *actor, co
   if (!actor) throw std::string(who) + "null actor";
   if (!bytes) throw std::string(who) + "null bytes";
   if (M < 0) throw std::string(who) + "M must be >= 0 (0 = no schedule)";
-  LearnNet nets[2] = {};
-  nets[0] = learn_net(actor, who, "actor", NA, "NA");
-  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
   OptArgs a = {};
   size_t off[OPT_MAXPIECES];
-  opt_layout(nets, a, off);
+  opt_layout(learn_nets(actor, critic, who).data(), a, off);
   *bytes = opt_workspace_bytes(a.nchunks, opt_segments(M));
   GUARD_END
 }
@@ -2086,9 +2070,8 @@ int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const t
                           const tsidb_policy_grads *actor_grads, const tsidb_policy_grads *critic_grads, float *log_std,
                           const float *log_std_grad, const tsidb_policy_opt_cfg *cfg, const tsidb_policy_opt_state *state,
                           const tsidb_policy_opt_kl *kl, void *workspace, size_t workspace_bytes, void *stream) {
-  GUARD_BEGIN
   const char *who = "tsidb_policy_opt_step: ";
-  hipStream_t s = (hipStream_t)stream;
+  return stream_call(h, stream, [&](auto launch) {
   if (!actor) throw std::string(who) + "null actor";
   if (!actor_grads) throw std::string(who) + "null actor_grads";
   if (critic && !critic_grads) throw std::string(who) + "null critic_grads";
@@ -2109,12 +2092,10 @@ int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const t
     if (kl->M < 1) throw std::string(who) + "M must be >= 1";
     if (kl->rows < 1) throw std::string(who) + "rows must be >= 1";
   }
-  LearnNet nets[2] = {};
-  nets[0] = learn_net(actor, who, "actor", NA, "NA");
-  if (critic) nets[1] = learn_net(critic, who, "critic", 1, "1");
+  const auto nets = learn_nets(actor, critic, who);
   OptArgs a = {};
   size_t off[OPT_MAXPIECES];
-  opt_layout(nets, a, off);
+  opt_layout(nets.data(), a, off);
   a.nseg = sched ? opt_segments(kl->M) : 0;
   const size_t need = opt_workspace_bytes(a.nchunks, a.nseg);
   if (workspace_bytes < need) throw std::string(who) + "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) + " needed";
@@ -2125,17 +2106,10 @@ int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const t
     pc.m = state->moments + off[np++];
     pc.vec = (((uintptr_t)pc.p | (uintptr_t)pc.g | (uintptr_t)pc.m | (uintptr_t)(pc.m + a.P)) & 15) == 0;
   };
-  for (int y = 0; y < 2; y++) {
-    const tsidb_policy_net *p = y ? critic : actor;
-    const tsidb_policy_grads *gr = y ? critic_grads : actor_grads;
-    const ActorNet &n = nets[y].net;
-    for (int l = 0; l < n.n_layers; l++) {
-      if (!gr->weight[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null weight gradient";
-      if (p->bias[l] && !gr->bias[l]) throw std::string(who) + (y ? "critic" : "actor") + ": null bias gradient where the bias exists";
-      fill(p->weight[l], gr->weight[l]);
-      if (p->bias[l]) fill(p->bias[l], gr->bias[l]);
-    }
-  }
+  each_layer_grad(who, actor, critic, actor_grads, critic_grads, nets.data(), [&](const float *W, const float *dW, const float *b, const float *db) {
+    fill(W, dW);
+    if (b) fill(b, db);
+  });
   fill(log_std, log_std_grad);
   if (sched) { a.mu = kl->mu; a.mean = kl->mean; a.index = kl->index; a.rows = kl->rows; a.M = kl->M; a.log_std_old = state->log_std_old; }
   a.log_std = log_std;
@@ -2145,12 +2119,10 @@ int tsidb_policy_opt_step(tsidb_handle h, const tsidb_policy_net *actor, const t
   a.lr = state->lr; a.step = (long long *)state->step; a.stats = state->stats;
   a.part = (double *)workspace;
   a.sc = (OptScalars *)(a.part + a.nchunks + 2 * a.nseg);
-  h->note_stream(s);
-  hipLaunchKernelGGL(k_policy_opt_partial, dim3(a.nchunks + a.nseg), dim3(OPT_LANES), 0, s, a);
-  hipLaunchKernelGGL(k_policy_opt_scalars, dim3(1), dim3(OPT_LANES), 0, s, a);
-  hipLaunchKernelGGL(k_policy_opt_apply, dim3(a.nchunks), dim3(OPT_LANES), 0, s, a);
-  HIP_OK(hipGetLastError());
-  GUARD_END
+  launch(k_policy_opt_partial, dim3(a.nchunks + a.nseg), dim3(OPT_LANES), 0, a);
+  launch(k_policy_opt_scalars, dim3(1), dim3(OPT_LANES), 0, a);
+  launch(k_policy_opt_apply, dim3(a.nchunks), dim3(OPT_LANES), 0, a);
+  });
 }
 
 } // extern "C"

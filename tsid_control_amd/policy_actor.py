@@ -14,13 +14,11 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._policy_util import bad, device_tensor, flag, net_refs, ptr
 from .policy_env import _whole_below
 
 _INPUT_NAMES = ("obs", "priv", "height_scan", "teacher_obs", "command", "obs_history")
-
-
-def _bad(msg):
-    return _lib.TsidbError("PolicyActor: " + msg)
+_bad = bad("PolicyActor")
 
 
 def _layers_of(net, activation, name):
@@ -94,10 +92,9 @@ class _Net:
             if w is None:
                 raise _bad(f"{name}: layer {i} has no weight")
             for t, what in ((w, "weight"), (b, "bias")):
-                if t is None:
-                    continue
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != wc.device or not t.is_contiguous():
-                    raise _bad(f"{name}: layer {i} {what} must be a contiguous float32 tensor on {wc.device}")
+                if t is not None:
+                    device_tensor("PolicyActor", f"{name}: layer {i} {what} must be a contiguous float32 tensor on {wc.device}", t, None,
+                                  torch.float32, wc.device)
             if w.dim() != 2 or w.shape[1] != fan_in:
                 raise _bad(f"{name}: layer {i} weight must be [width, {fan_in}] (its input has {fan_in} columns), got {tuple(w.shape)}")
             width = int(w.shape[0])
@@ -146,10 +143,8 @@ class PolicyActor:
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=wc.device)
         if log_std is None:
             log_std = f32(NA)
-        if not isinstance(log_std, torch.Tensor) or tuple(log_std.shape) != (NA,) or log_std.dtype != torch.float32 \
-                or log_std.device != wc.device or not log_std.is_contiguous():
-            raise _bad(f"log_std must be a contiguous ({NA},) float32 tensor on {wc.device}")
-        self.log_std = log_std
+        self.log_std = device_tensor("PolicyActor", f"log_std must be a contiguous ({NA},) float32 tensor on {wc.device}", log_std, (NA,),
+                                     torch.float32, wc.device)
         if seed is None:
             seed = int(env.params[_lib.POL_P_SEED]) if getattr(env, "params", None) is not None else 0
         if env_offset is None:
@@ -173,19 +168,18 @@ class PolicyActor:
                 critic_input=None):
         """one tsidb_policy_actor call writing the given tensors (None = not written)"""
         wc = self.env.wc
-        p = lambda t: t.data_ptr() if t is not None else None
-        out = _lib.PolicyActorOut(p(action), p(action32), p(mean), p(logp), p(value), p(actor_input), p(critic_input))
+        out = _lib.PolicyActorOut(*(ptr(t) for t in (action, action32, mean, logp, value, actor_input, critic_input)))
         self._out = out      # (alive until the next call: the library copies it during the call, a recorder may look later)
-        cn = self.critic_net if critic else None
-        nets = (C.byref(self.actor_net.struct) if actor else None, C.byref(cn.struct) if cn is not None else None)
-        rest = (C.byref(out), C.c_void_p(self.log_std.data_ptr()), C.c_uint64(self.seed), C.c_uint64(self.env_offset),
+        a, c = net_refs(self)
+        nets = (a if actor else None, c if critic else None)
+        rest = (C.byref(out), ptr(self.log_std), C.c_uint64(self.seed), C.c_uint64(self.env_offset),
                 _lib.POL_ACTOR_SAMPLE if sample else 0, wc._stream())
         nz = self.normalizer
         if nz is None:
             wc._call("tsidb_policy_actor", C.byref(self.env._bufs), *nets, *rest)
         else:
             wc._call("tsidb_policy_actor_norm", C.byref(self.env._bufs), *nets, C.byref(nz.actor.struct) if actor else None,
-                     C.byref(nz.critic.struct) if cn is not None and nz.critic is not None else None, *rest)
+                     C.byref(nz.critic.struct) if nets[1] is not None and nz.critic is not None else None, *rest)
 
     def observe(self):
         """with a normaliser in training mode: its update() on the env's current tensors - what act() and every step of
@@ -233,9 +227,7 @@ class RolloutStorage:
         self.value = z(T + 1, N)
         self.reward, self.done, self.timeout = z(T, N, dt=wc.dtype), z(T, N, dt=wc.dtype), z(T, N, dt=torch.int32)
         self.advantage = self.returns = None
-        if not isinstance(teacher, bool):
-            raise _lib.TsidbError(f"RolloutStorage: teacher must be a bool, got {teacher!r}")
-        if teacher:
+        if flag("RolloutStorage", "teacher", teacher):
             if getattr(env, "tsid", None) is None:
                 raise _lib.TsidbError("RolloutStorage: teacher = True needs an env with tsid = 'stand' or 'walk': there is no teacher to label with")
             if getattr(env, "mode", None) not in ("position", "motor"):
@@ -255,9 +247,8 @@ class RolloutStorage:
         wc = self.env.wc
         if self.advantage is None:
             self.advantage, self.returns = torch.zeros_like(self.logp), torch.zeros_like(self.logp)
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        wc._call("tsidb_policy_gae", self.steps, vp(self.reward), vp(self.done), vp(self.timeout), vp(self.value), C.c_float(gamma),
-                 C.c_float(lam), vp(self.advantage), vp(self.returns), wc._stream())
+        wc._call("tsidb_policy_gae", self.steps, ptr(self.reward), ptr(self.done), ptr(self.timeout), ptr(self.value), C.c_float(gamma),
+                 C.c_float(lam), ptr(self.advantage), ptr(self.returns), wc._stream())
         return self.advantage, self.returns
 
 

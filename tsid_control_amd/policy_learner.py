@@ -15,29 +15,16 @@ its own, reads the pointers again at every call (zero_grad(set_to_none=True) is 
 parameter that has a .grad.  A .grad the caller set is used as it is if it is float32, contiguous and on the device.
 """
 import ctypes as C
+from functools import partial
 
 import torch
 
 from . import _lib
+from ._policy_util import bad, count, device_tensor, flag, grown_workspace, net_refs, number, ptr
 from .policy_actor import PolicyActor, RolloutStorage
 
-
-def _bad(msg):
-    return _lib.TsidbError("PolicyLearner: " + msg)
-
-
-def _number(name, x, lo=None, strict=False):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x or x in (float("inf"), float("-inf")):
-        raise _bad(f"{name} must be a finite number, got {x!r}")
-    if lo is not None and (x <= lo if strict else x < lo):
-        raise _bad(f"{name} must be {'>' if strict else '>='} {lo}, got {x!r}")
-    return float(x)
-
-
-def _count(name, x):
-    if isinstance(x, bool) or not isinstance(x, int) or x < 1:
-        raise _bad(f"{name} must be a whole number >= 1, got {x!r}")
-    return x
+_WHO = "PolicyLearner"
+_bad, _number, _count, _flag, _tensor = bad(_WHO), partial(number, _WHO), partial(count, _WHO), partial(flag, _WHO), partial(device_tensor, _WHO)
 
 
 class PolicyLearner:
@@ -67,18 +54,13 @@ class PolicyLearner:
         self.actor, self.env = actor, actor.env
         self.clip = _number("clip", clip, 0.0, strict=True)
         self.value_coef, self.entropy_coef = _number("value_coef", value_coef, 0.0), _number("entropy_coef", entropy_coef, 0.0)
-        for name, x in (("value_clip", value_clip), ("normalize_advantage", normalize_advantage)):
-            if not isinstance(x, bool):
-                raise _bad(f"{name} must be a bool, got {x!r}")
-        self.value_clip, self.normalize_advantage = value_clip, normalize_advantage
+        self.value_clip, self.normalize_advantage = _flag("value_clip", value_clip), _flag("normalize_advantage", normalize_advantage)
         self.imitation_coef, self.surrogate_coef = _number("imitation_coef", imitation_coef, 0.0), _number("surrogate_coef", surrogate_coef, 0.0)
         if imitation_loss not in _lib.POL_IMIT_LOSSES:
             raise _bad(f"imitation_loss must be one of {_lib.POL_IMIT_LOSSES}, got {imitation_loss!r}")
         self.imitation_loss = imitation_loss
         self.symmetry, self.mirror_coef = symmetry, _number("mirror_coef", mirror_coef, 0.0)
-        if not isinstance(symmetry_augment, bool):
-            raise _bad(f"symmetry_augment must be a bool, got {symmetry_augment!r}")
-        self.symmetry_augment = symmetry_augment
+        self.symmetry_augment = _flag("symmetry_augment", symmetry_augment)
         if symmetry is not None:
             self._check_symmetry(symmetry)
         elif self.mirror_coef != 0.0:
@@ -106,8 +88,7 @@ class PolicyLearner:
             sizes.append(("critic", sym.critic_perm, sym.critic_sign, a.critic_net.K))
         for name, perm, sign, k in sizes:
             for t, dt in ((perm, torch.int32), (sign, torch.float32)):
-                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (k,) or t.device != dev or not t.is_contiguous():
-                    raise _bad(f"symmetry: the {name} table must be contiguous [{k}] int32 and float32 tensors on {dev}")
+                _tensor(f"symmetry: the {name} table must be contiguous [{k}] int32 and float32 tensors on {dev}", t, (k,), dt, dev)
             if int(perm.min()) < 0 or int(perm.max()) >= k:
                 raise _bad(f"symmetry: the {name} perm must stay inside [0, {k})")
 
@@ -126,10 +107,8 @@ class PolicyLearner:
         g = p.grad
         if g is None:
             p.grad = g = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
-        elif g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape or not g.is_contiguous():
-            raise _bad(f"a .grad must be a contiguous float32 tensor of its parameter's shape on {p.device}, got "
-                       f"{(tuple(g.shape), g.dtype, g.device, g.stride())}")
-        return g
+        return _tensor(lambda: f"a .grad must be a contiguous float32 tensor of its parameter's shape on {p.device}, got "
+                             f"{(tuple(g.shape), g.dtype, g.device, g.stride())}", g, tuple(p.shape), torch.float32, p.device)
 
     def _grads_of(self, net):
         s = _lib.PolicyGrads()
@@ -138,17 +117,26 @@ class PolicyLearner:
             s.bias[i] = self._grad(b).data_ptr() if b is not None else None
         return s
 
-    def _workspace_for(self, M):
-        if self.workspace is None or M > self._ws_rows:
-            wc, a = self.env.wc, self.actor
-            n = C.c_size_t(0)
-            query = "tsidb_policy_learn_sym_workspace" if self.symmetry is not None else \
-                "tsidb_policy_learn_imit_workspace" if self._imit_on else "tsidb_policy_learn_workspace"
-            wc._call(query, C.byref(a.actor_net.struct),
-                     C.byref(a.critic_net.struct) if a.critic_net is not None else None, M, C.byref(n))
-            self.workspace = torch.empty(max(1, (n.value + 3) // 4), dtype=torch.float32, device=wc.device)
-            self._ws_rows, self._ws_bytes = M, n.value
-        return self.workspace
+    def _variant(self):
+        """(workspace query, entry, maker of the entry's extra struct or None) of this learner's backward()"""
+        if self.symmetry is not None:
+            return "tsidb_policy_learn_sym_workspace", "tsidb_policy_learn_sym", self._sym_struct
+        if self._imit_on:
+            return "tsidb_policy_learn_imit_workspace", "tsidb_policy_learn_imit", self._imit_struct
+        return "tsidb_policy_learn_workspace", "tsidb_policy_learn", None
+
+    def _sym_struct(self, storage):
+        sy = self.symmetry
+        self._last_sym = _lib.PolicySymmetryTables(ptr(sy.actor_perm), ptr(sy.actor_sign), ptr(sy.critic_perm), ptr(sy.critic_sign),
+                                                   ptr(sy.action_perm), ptr(sy.action_sign), int(self.symmetry_augment), self.mirror_coef,
+                                                   ptr(self.sym_stats))
+        return self._last_sym              # (alive until the next call, as the batch)
+
+    def _imit_struct(self, storage):
+        self._last_imit = _lib.PolicyImit(ptr(storage.teacher_action), ptr(storage.teacher_weight), ptr(storage.teacher_executed),
+                                          self.imitation_coef, self.surrogate_coef, _lib.POL_IMIT_LOSSES.index(self.imitation_loss),
+                                          ptr(self.imit_stats))
+        return self._last_imit             # (alive until the next call, as the batch)
 
     def fill_adv_stats(self, storage):
         """adv_stats = (mean, 1 / (std + 1e-8)) of storage.advantage, with torch ops on the current stream: no host sync"""
@@ -167,45 +155,30 @@ class PolicyLearner:
             raise _bad("storage.gae() has not run: there are no advantages and returns")
         if self.imitation_coef > 0 and storage.teacher_action is None:
             raise _bad("imitation_coef > 0 needs a storage with the teacher's labels (RolloutStorage(..., teacher=True))")
-        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or index.shape[0] < 1 \
-                or index.device != wc.device or not index.is_contiguous():
-            what = (tuple(index.shape), index.dtype, index.device) if isinstance(index, torch.Tensor) else type(index).__name__
-            raise _bad(f"index must be a contiguous [M >= 1] int32 tensor on {wc.device}, got {what}")
+        got = lambda: (tuple(index.shape), index.dtype, index.device) if isinstance(index, torch.Tensor) else type(index).__name__
+        bad_index = lambda: f"index must be a contiguous [M >= 1] int32 tensor on {wc.device}, got {got()}"
+        if _tensor(bad_index, index, (None,), torch.int32, wc.device).shape[0] < 1:
+            raise _bad(bad_index())
         if stats is None:
             stats = self.stats
-        elif not isinstance(stats, torch.Tensor) or stats.dtype != torch.float32 or tuple(stats.shape) != (len(_lib.POL_LEARN_STATS),) \
-                or stats.device != wc.device or not stats.is_contiguous():
-            raise _bad(f"stats must be a contiguous [{len(_lib.POL_LEARN_STATS)}] float32 tensor on {wc.device}")
+        else:
+            _tensor(f"stats must be a contiguous [{len(_lib.POL_LEARN_STATS)}] float32 tensor on {wc.device}", stats, (len(_lib.POL_LEARN_STATS),),
+                    torch.float32, wc.device)
         if adv_stats is None and self.normalize_advantage:
             self.fill_adv_stats(storage)
         M = int(index.shape[0])
-        ws = self._workspace_for(M)
-        p = lambda t: t.data_ptr() if t is not None else None
-        batch = _lib.PolicyLearnBatch(p(storage.actor_input), p(storage.critic_input), p(storage.action), p(storage.logp), p(storage.value),
-                                      p(storage.advantage), p(storage.returns), p(index), storage.steps * self.env.num_envs, M,
-                                      p(self.adv_stats) if self.normalize_advantage else None)
+        query, entry, extra = self._variant()
+        ws = grown_workspace(self, wc, query, a, M, torch.float32)
+        batch = _lib.PolicyLearnBatch(*(ptr(t) for t in (storage.actor_input, storage.critic_input, storage.action, storage.logp, storage.value,
+                                                         storage.advantage, storage.returns, index)), storage.steps * self.env.num_envs, M,
+                                      ptr(self.adv_stats) if self.normalize_advantage else None)
         ag = self._grads_of(a.actor_net)
         cg = self._grads_of(a.critic_net) if a.critic_net is not None else None
         self._last = (batch, ag, cg)       # (alive until the next call: the library copies them during the call, a recorder may look later)
         self._last_storage, self._last_index = storage, index    # (what a PolicyOptimizer's KL is taken over)
-        head = (C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None, C.byref(batch), C.byref(ag),
-                C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()), C.c_void_p(self._grad(a.log_std).data_ptr()),
-                C.byref(self._cfg))
-        tail = (C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel() * 4), C.c_void_p(stats.data_ptr()), wc._stream())
-        if self.symmetry is not None:
-            sy, q = self.symmetry, lambda t: t.data_ptr() if t is not None else None
-            tables = _lib.PolicySymmetryTables(q(sy.actor_perm), q(sy.actor_sign), q(sy.critic_perm), q(sy.critic_sign), q(sy.action_perm),
-                                               q(sy.action_sign), int(self.symmetry_augment), self.mirror_coef, q(self.sym_stats))
-            self._last_sym = tables        # (alive until the next call, as the batch)
-            wc._call("tsidb_policy_learn_sym", *head, C.byref(tables), *tail)
-            return stats
-        if not self._imit_on:
-            wc._call("tsidb_policy_learn", *head, *tail)
-            return stats
-        imit = _lib.PolicyImit(p(storage.teacher_action), p(storage.teacher_weight), p(storage.teacher_executed), self.imitation_coef,
-                               self.surrogate_coef, _lib.POL_IMIT_LOSSES.index(self.imitation_loss), p(self.imit_stats))
-        self._last_imit = imit             # (alive until the next call, as the batch)
-        wc._call("tsidb_policy_learn_imit", *head, C.byref(imit), *tail)
+        wc._call(entry, *net_refs(a), C.byref(batch), C.byref(ag), C.byref(cg) if cg is not None else None, ptr(a.log_std),
+                 C.c_void_p(self._grad(a.log_std).data_ptr()), C.byref(self._cfg), *((C.byref(extra(storage)),) if extra is not None else ()),
+                 ptr(ws), C.c_size_t(ws.numel() * 4), ptr(stats), wc._stream())
         return stats
 
     def outputs(self, M):

@@ -15,25 +15,14 @@ sums into the actor launch and normalises with the previous step's statistics wo
 order; it is not built.
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import _lib
+from ._policy_util import bad, flag, net_refs, number, ptr
 
 _NETS = (("actor", "obs_normalizer"), ("critic", "critic_obs_normalizer"))
-
-
-def _bad(msg):
-    return _lib.TsidbError("PolicyNormalizer: " + msg)
-
-
-def _number(name, x):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
-        raise _bad(f"{name} must be a finite number, got {x!r}")
-    if x <= 0:
-        raise _bad(f"{name} must be > 0, got {x!r}")
-    return float(x)
+_bad = bad("PolicyNormalizer")
 
 
 class _State:
@@ -68,14 +57,12 @@ class PolicyNormalizer:
     at first), count [1] int64, affine [2, K] float32 (shift, scale: all the actor's launch reads); workspace."""
 
     def __init__(self, eps=1e-2, clip=None, until=None, critic=True):
-        self.eps = _number("eps", eps)
-        self.clip = None if clip is None else _number("clip", clip)
+        self.eps = number("PolicyNormalizer", "eps", eps, 0, strict=True)
+        self.clip = None if clip is None else number("PolicyNormalizer", "clip", clip, 0, strict=True)
         if until is not None and (isinstance(until, bool) or not isinstance(until, int) or until < 1):
             raise _bad(f"until must be a whole number >= 1 or None, got {until!r}")
         self.until = until
-        if not isinstance(critic, bool):
-            raise _bad(f"critic must be a bool, got {critic!r}")
-        self.with_critic = critic
+        self.with_critic = flag("PolicyNormalizer", "critic", critic)
         self.training = True
         self.policy = None
         self.actor = self.critic = self.workspace = None
@@ -101,9 +88,7 @@ class PolicyNormalizer:
 
     def train(self, mode=True):
         """act() and rollout() update the statistics before they evaluate (the default)"""
-        if not isinstance(mode, bool):
-            raise _bad(f"mode must be a bool, got {mode!r}")
-        self.training = mode
+        self.training = flag("PolicyNormalizer", "mode", mode)
         return self
 
     def eval(self):
@@ -114,10 +99,11 @@ class PolicyNormalizer:
         """one tsidb_policy_norm_update call on the env's current tensors (two launches on the current stream, both networks in
         each): the N rows enter each network's statistics and its affine pair is rewritten"""
         self._need()
-        p, wc = self.policy, self.policy.env.wc
-        wc._call("tsidb_policy_norm_update", C.byref(p.actor_net.struct), C.byref(p.critic_net.struct) if self.critic is not None else None,
+        wc = self.policy.env.wc
+        a, c = net_refs(self.policy)
+        wc._call("tsidb_policy_norm_update", a, c if self.critic is not None else None,
                  C.byref(self.actor.struct), C.byref(self.critic.struct) if self.critic is not None else None,
-                 C.c_void_p(self.workspace.data_ptr()), C.c_size_t(self.workspace.numel() * 8), wc._stream())
+                 ptr(self.workspace), C.c_size_t(self.workspace.numel() * 8), wc._stream())
 
     def written(self):
         """stats, count, affine of each network and the workspace: what update() writes"""

@@ -11,25 +11,16 @@ the next backward() compute with the step; .grad is read, never written - the cl
 Not built: weight decay, amsgrad; a rank all-reduce (all-reduce .grad before step(); the KL is this rank's); per-row sigma.
 """
 import ctypes as C
+from functools import partial
 
 import torch
 
 from . import _lib
+from ._policy_util import bad, device_tensor, flag, grown_workspace, net_refs, number, ptr
 from .policy_learner import PolicyLearner
 
 _NSTATS = len(_lib.POL_OPT_STATS)
-
-
-def _bad(msg):
-    return _lib.TsidbError("PolicyOptimizer: " + msg)
-
-
-def _number(name, x, lo=None, strict=False):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x or x in (float("inf"), float("-inf")):
-        raise _bad(f"{name} must be a finite number, got {x!r}")
-    if lo is not None and (x <= lo if strict else x < lo):
-        raise _bad(f"{name} must be {'>' if strict else '>='} {lo}, got {x!r}")
-    return float(x)
+_bad, _number = bad("PolicyOptimizer"), partial(number, "PolicyOptimizer")
 
 
 def _betas(betas):
@@ -65,9 +56,7 @@ class PolicyOptimizer:
         self.lr_min, self.lr_max = _number("lr_min", lr_min, 0.0, strict=True), _number("lr_max", lr_max, 0.0, strict=True)
         if self.lr_min > self.lr_max:
             raise _bad(f"lr_min must be <= lr_max, got {lr_min!r} and {lr_max!r}")
-        if not isinstance(skip_nonfinite, bool):
-            raise _bad(f"skip_nonfinite must be a bool, got {skip_nonfinite!r}")
-        self.skip_nonfinite = skip_nonfinite
+        self.skip_nonfinite = flag("PolicyOptimizer", "skip_nonfinite", skip_nonfinite)
         dev = learner.env.wc.device
         self._params = learner.parameters()
         self._offsets, n = [], 0
@@ -112,9 +101,9 @@ class PolicyOptimizer:
 
     @log.setter
     def log(self, t):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != _NSTATS
-                              or t.device != self.lr.device or not t.is_contiguous()):
-            raise _bad(f"log must be None or a contiguous [k, {_NSTATS}] float32 tensor on {self.lr.device}")
+        if t is not None:
+            device_tensor("PolicyOptimizer", f"log must be None or a contiguous [k, {_NSTATS}] float32 tensor on {self.lr.device}", t,
+                          (None, _NSTATS), torch.float32, self.lr.device)
         self._log, self._log_i = t, 0
 
     def written(self):
@@ -127,16 +116,6 @@ class PolicyOptimizer:
     def snapshot(self):
         """log_std_old = log_std, a torch copy on the current stream: the rollout's policy, before the first step of an update()"""
         self.log_std_old.copy_(self.learner.actor.log_std)
-
-    def _workspace_for(self, M):
-        if self.workspace is None or M > self._ws_rows:
-            wc, a = self.learner.env.wc, self.learner.actor
-            n = C.c_size_t(0)
-            wc._call("tsidb_policy_opt_workspace", C.byref(a.actor_net.struct),
-                     C.byref(a.critic_net.struct) if a.critic_net is not None else None, M, C.byref(n))
-            self.workspace = torch.empty(max(1, (n.value + 7) // 8), dtype=torch.float64, device=wc.device)
-            self._ws_rows, self._ws_bytes = M, n.value
-        return self.workspace
 
     def step(self):
         """One step on the .grad tensors as they are now, in three launches on the current stream.  With desired_kl the KL is taken
@@ -152,7 +131,7 @@ class PolicyOptimizer:
             storage, index = l._last_storage, l._last_index
             M = int(index.shape[0])
             kl = _lib.PolicyOptKl(l.workspace.data_ptr(), storage.mean.data_ptr(), index.data_ptr(), storage.steps * l.env.num_envs, M)
-        ws = self._workspace_for(M)
+        ws = grown_workspace(self, wc, "tsidb_policy_opt_workspace", a, M, torch.float64)
         self._last_M = M
         stats = self.stats
         if self._log is not None and self._log_i < self._log.shape[0]:
@@ -161,10 +140,9 @@ class PolicyOptimizer:
         state = _lib.PolicyOptState(self.moments.data_ptr(), self.lr.data_ptr(), self.step_count.data_ptr(), self.log_std_old.data_ptr(),
                                     stats.data_ptr())
         self._last = (ag, cg, state, kl)   # (alive until the next call: the library copies them during the call, a recorder may look later)
-        wc._call("tsidb_policy_opt_step", C.byref(a.actor_net.struct), C.byref(a.critic_net.struct) if a.critic_net is not None else None,
-                 C.byref(ag), C.byref(cg) if cg is not None else None, C.c_void_p(a.log_std.data_ptr()),
+        wc._call("tsidb_policy_opt_step", *net_refs(a), C.byref(ag), C.byref(cg) if cg is not None else None, ptr(a.log_std),
                  C.c_void_p(l._grad(a.log_std).data_ptr()), C.byref(self._cfg), C.byref(state), C.byref(kl) if kl is not None else None,
-                 C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel() * 8), wc._stream())
+                 ptr(ws), C.c_size_t(ws.numel() * 8), wc._stream())
         return stats
 
     def norm_kl64(self):

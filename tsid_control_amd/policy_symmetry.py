@@ -15,11 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._policy_util import bad
 from .policy_actor import PolicyActor
 
-
-def _bad(msg):
-    return _lib.TsidbError("PolicySymmetry: " + msg)
+_bad = bad("PolicySymmetry")
 
 
 def _quat_mat(q):

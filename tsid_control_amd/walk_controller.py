@@ -17,16 +17,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._policy_util import ptr as _ptr
 from .conf import RobotConfig
 from .model import ModelBlob
 from .params import P_COUNT, pack_params
 from .sim_pipeline import SimPipeline, StreamTable, streams_overlap
 
 MAXCON = 32
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class TrajectorySample:
